@@ -10,10 +10,15 @@ A "step" renders `--views` target views (default 16) of the synthetic 1.0 M-Gaus
 968x1296 on every rank (weak scaling, view-sharded: rank r renders its own block of the N*views
 target cameras) and, for N>1, all-gathers the rendered colour images (`--gather-depth`: + depth; `--gather-dtype
 fp32 | fp16 | uint8`) over RCCL on a side stream, overlapped with the next step.  Inputs are resident in HBM before the
-timed region.  The timed region is EXACTLY `--steps` steps between two barriers (max over ranks); at the default sizes it
-lasts ~80 ms, so it is repeated until `--min-time` (0.6 s) has been timed and the MEDIAN region is reported
-(`timed_regions_ms` lists them all).  `--single-rank-collectives` (under `torch.distributed.run --nproc-per-node 1`) takes
-the N>1 code path on RCCL with one rank.
+timed region.  The timed region is EXACTLY `--steps` steps between two barriers (max over ranks), and `ms_per_step` is its
+length over `--steps`.  `--min-time S` (opt-in) repeats the region until S seconds have been timed and reports the MEDIAN
+region (`timed_regions_ms` lists them all).  `--single-rank-collectives` (under `torch.distributed.run --nproc-per-node 1`)
+takes the N>1 code path on RCCL with one rank.
+
+`--dump-outputs DIR` writes what the headline's last timed step computed (colour and depth images; in `--mode train` also
+the gradients of the Gaussian parameters) as DIR/<name>.npy in float32, rank 0's views.  The inputs are seeded, so two builds
+run with the same arguments can be compared array for array.  Above 64 MB in all, every array is replaced by the same fixed,
+seeded sample of its flattened elements (`dump_outputs` in the result line records shapes and sample sizes).
 
 Rank 0 prints ONE JSON line.  Top level = the headline metric (forward rendering, config 3's size) with
 `roofline` (render kernel, HIP-event timed inside the timed region through the library's fs_profile_* hooks),
@@ -67,9 +72,12 @@ def parse():
     ap.add_argument("--gather-depth", action="store_true",
                     help="N>1: all-gather the depth maps too (the reference's decoder returns depth only when depth_mode is "
                          "set, decoder_splatting_cuda.py:64-70; colour alone is 15 MB per view, with depth 20 MB)")
-    ap.add_argument("--min-time", type=float, default=0.6,
+    ap.add_argument("--min-time", type=float, default=0.0,
                     help="repeat the timed region of `--steps` steps until this many seconds have been timed; the median "
-                         "region is reported (0: one region)")
+                         "region is reported (0, the default: one region of exactly `--steps` steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline's last timed step computed as DIR/<name>.npy (float32; a fixed, seeded "
+                         "sample of each array when all of them exceed 64 MB)")
     ap.add_argument("--gather-dtype", default="fp32", choices=["fp32", "fp16", "uint8"],
                     help="N>1: element type of the gathered images.  fp32 (default) = what the decoder returns; fp16 / uint8 "
                          "(clamped to [0,1], x255, rounded) halve / quarter the bytes every GPU receives over its 7 xGMI links "
@@ -115,7 +123,7 @@ class Ctx:
 
 
 def bench_raster(cx: Ctx, workload: str, mode: str, views: int, steps: int, warmup: int, cpu_baseline: bool,
-                 sh_fp16: bool = False) -> dict | None:
+                 sh_fp16: bool = False, dump_dir: str | None = None) -> dict | None:
     """One rasterizer measurement (forward, or forward+backward): returns the JSON object on rank 0.
     `sh_fp16` (forward only): the SH coefficients are STORED in fp16 (BASELINE config 5; FS_RASTER_SH_FP16: converted on
     load, fp32 arithmetic) -- algorithmic bytes N*94 + P*16, parity against the oracle fed the fp16-rounded coefficients."""
@@ -144,7 +152,8 @@ def bench_raster(cx: Ctx, workload: str, mode: str, views: int, steps: int, warm
     if train:
         for t in g.values():
             t.requires_grad_(True)
-        target = torch.rand(len(mine), 3, H, W, device=dev)
+        # seeded: the same arguments give the same inputs (and outputs) from run to run
+        target = torch.rand(len(mine), 3, H, W, device=dev, generator=torch.Generator(device=dev).manual_seed(1000 + rank))
     gather = AsyncViewGather(n_total_views, device=dev) if (cx.dist_on and not args.no_gather and not train) else None
     exchange = GradExchange(args.grad_exchange, chunks=args.grad_chunks).install() if (cx.dist_on and train) else None
     diag_events = None      # (set for the few extra untimed steps that time the gradient exchange per rank)
@@ -240,6 +249,13 @@ def bench_raster(cx: Ctx, workload: str, mode: str, views: int, steps: int, warm
         if enough.item() > 0:
             break
     dt = sorted(regions)[len(regions) // 2]
+    dumped = None
+    if dump_dir is not None and rank == 0:
+        # what the caller of the last timed step received (before any untimed step below runs)
+        outs = {"color": color, "depth": depth}
+        if train:
+            outs.update({f"grad_{k}": t.grad for k, t in g.items()})
+        dumped = dump_outputs(dump_dir, outs)
     stages, breakdown = {}, {}
     if profile:
         _lib.profile_enable(False)
@@ -380,6 +396,8 @@ def bench_raster(cx: Ctx, workload: str, mode: str, views: int, steps: int, warm
                                      "with a workload denser than 8 entries per Gaussian); the timed region never retries"}
     if multi is not None:
         out["multi_gpu"] = multi
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     if graph_views_per_s is not None:
         out["hipgraph_replay"] = {"value": graph_views_per_s, "unit": "views/s", "same_image_as_eager": graph_ok,
                                   "what": "one step captured into a hipGraph, replayed `steps` times"}
@@ -445,6 +463,32 @@ def bench_raster(cx: Ctx, workload: str, mode: str, views: int, steps: int, warm
     if world == 1 and cpu_baseline:
         out.update(cpu_baseline_and_parity(scene, cams_all, H, W, workload, train=train, sh_fp16=sh_fp16))
     return out
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dump_dir: str, arrays: dict, seed: int = 0) -> dict:
+    """Writes every tensor of `arrays` as dump_dir/<name>.npy in float32.  If they exceed DUMP_MAX_BYTES together, each one is
+    replaced by a sample of its flattened elements: a share of the budget proportional to its size, at positions drawn from
+    numpy's PCG64 seeded with `seed` + the array's place in `arrays` (sorted, so the same for every build).  Returns what
+    was written: {name: {"shape": full shape, "elements": elements written, "sampled": bool}}."""
+    import numpy as np
+    os.makedirs(dump_dir, exist_ok=True)
+    total = sum(t.numel() for t in arrays.values())
+    budget = DUMP_MAX_BYTES // 4 - 1024 * len(arrays)      # (room for the .npy headers)
+    info = {}
+    for i, (name, t) in enumerate(arrays.items()):
+        flat = t.detach().reshape(-1)
+        sampled = total > budget
+        if sampled:
+            k = max(1, budget * t.numel() // total)
+            idx = np.sort(np.random.default_rng(seed + i).integers(0, t.numel(), size=k))
+            flat = flat.index_select(0, torch.from_numpy(idx).to(flat.device))
+        a = flat.float().cpu().numpy() if sampled else t.detach().float().cpu().numpy()
+        np.save(os.path.join(dump_dir, name + ".npy"), a)
+        info[name] = {"shape": list(t.shape), "elements": int(a.size), "sampled": sampled}
+    return info
 
 
 def _R_FAST() -> bool:
@@ -597,6 +641,8 @@ def headline(full: dict) -> dict:
         h["cpu_baseline"] = dict(full["cpu_baseline"], value=_num(full["cpu_baseline"]["value"]))
     if "parity" in full:
         h["parity"] = _pick(full["parity"], ("max_abs_err_vs_oracle", "pixels_above_1e-4", "pixels", "bit_exact", "psnr_db_vs_oracle"))
+    if "dump_outputs" in full:
+        h["dump_outputs"] = full["dump_outputs"]
     if "multi_gpu" in full:
         pr = full["multi_gpu"].get("per_rank", [])
         h["multi_gpu"] = {k: _num(max(r[k] for r in pr), 4) for k in (pr[0] if pr else {})}      # max over ranks
@@ -718,7 +764,7 @@ def main():
         raise SystemExit(respawn_under_launcher(args))
     cx = Ctx(args)
     cpu = not args.no_cpu_baseline
-    out = bench_raster(cx, args.workload, args.mode, args.views, args.steps, args.warmup, cpu)
+    out = bench_raster(cx, args.workload, args.mode, args.views, args.steps, args.warmup, cpu, dump_dir=args.dump_outputs)
     sections = []
     if cx.world == 1 and args.sections != "raster":
         sections = ["train", "c2", "closeup", "c5", "cost_volume", "ptf", "encoder_tail", "c3_step"] if args.sections == "all" else args.sections.split(",")

@@ -11,7 +11,7 @@ does, in this order,
                                DECODERS["splatting_cuda"]) -- before the target module builds any model
   3. runpy.run_module(<module>, run_name="__main__") with sys.argv = [<module>, args...]
 
-`--dry-run` after the module name stops after step 2 and prints what was rebound (used by tests/test_compat_reference.py).
+`--dry-run` after the module name stops after step 2 and prints what was rebound (used to check the wiring against the reference tree).
 """
 import os
 import runpy

@@ -14,8 +14,8 @@ to_gaussians, weight_embedding: out of scope).  What changes agains
   * :364-368  self.fuse_gaussians(...)                      (fs_ptf_fold)
   * :371-386  to_gaussians + gaussian_adapter.forward(fusion=False, coords=...)   (fs_gaussian_head_*)
 Same signature and the same result dictionary (keys and shapes), so model_wrapper.py:231-233,292,315-322,383,425 and
-the losses read it unchanged.  tests/test_compat_reference.py runs this function and the reference's forward on the SAME
-reference modules (CPU) and compares every entry of the two dictionaries.
+the losses read it unchanged.  Checked against the reference tree by running this function and the reference's forward on the SAME
+reference modules (CPU) and comparing every entry of the two dictionaries.
 """
 from __future__ import annotations
 
@@ -73,7 +73,7 @@ def encoder_forward(self, context, global_step: int, deterministic: bool = False
         lat, dens_raw = latents_pack(head, skip)
         latents = lat.reshape(b, V, h * w, -1)
         densities = torch.sigmoid(dens_raw).reshape(b, V, h * w, 1, 1)
-    else:       # host tensors (tests/test_compat_reference.py runs this glue on the reference's own CPU modules)
+    else:       # host tensors (the check against the reference tree runs this glue on the reference's own CPU modules)
         latents = (head[:, 1:] + skip).reshape(b, V, -1, h * w).transpose(-1, -2)
         densities = torch.sigmoid(_bv(head[:, :1], b))
     depths = _bv(dec["depth_pred_s-1_b1hw"], b)

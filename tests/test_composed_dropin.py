@@ -5,8 +5,8 @@ loss -- FORWARD AND BACKWARD, b = 1 and b = 2, at BASELINE config 1's size (2 vi
 
 The out-of-scope modules of the encoder (backbone, cv_encoder, the depth decoder's convolution trunk,
 high_resolution_skip, to_gaussians) are small deterministic torch stand-ins, identical on both sides.  The reference
-side is the SAME `encoder_forward` (pinned entry by entry to the reference's own forward on the reference's modules by
-tests/test_compat_reference.py) over an encoder whose hot-path modules are the reference-pinned ORACLES, on the CPU, and
+side is the SAME `encoder_forward` (checked entry by entry against the reference's own forward on the reference's modules
+while the reference tree was at hand) over an encoder whose hot-path modules are the reference-pinned ORACLES, on the CPU, and
 the oracle rasterizer behind a torch autograd wrapper.  Compared: every entry of the result dictionary, the Gaussians,
 the rendered images, the loss, and the gradient of the loss w.r.t. EVERY parameter of the stand-ins and of the hot-path
 modules (cost-volume MLP, GRU) -- i.e. the whole chain of backward kernels composed.
