@@ -19,26 +19,18 @@
 //     - K >= 2, cost_volume16_kernel: 16-pixel wavefronts, lane = (pixel, channel quarter) with the four lanes of a pixel
 //       adjacent, so that a tap load reads 64 contiguous bytes per quad (the sweep is bound by the delivery of its taps:
 //       1.7x fewer cycles per load instruction than with (pixel, parity) lanes), v_mfma_f32_16x16x4_f32;
-//     - backward (round 4: two passes, no global float atomics on the source maps): pass 1 -- cost_volume16_bwd_kernel (round 6:
-//       the forward's 16-pixel lane orders, v_mfma_f32_16x16x4_f32, natural-order records; FS_CV_BWD16=0 or a saved-activation
-//       call: cost_volume_bwd_kernel, 32 pixels x parity on texel-major [y][x][parity][C/2] records) -- recomputes the forward per
-//       plane and forms the six MLP gradients on the matrix cores, d cur, and one record per (pixel, plane) point -- then
-//       cv_src_grad_kernel, whose single-wavefront workgroups
-//       own 8 x 8 tiles of SOURCE texels and collect, plane by plane, from the pixels whose taps cover them (found through
-//       the inverse plane homography), accumulating in LDS.  (Per-pixel plane depths or K > 16: the round-3 one-kernel
-//       form, which scatters with 192-byte atomic records.)
+//     - backward (two passes, no global float atomics on the source maps): pass 1 -- cost_volume16_bwd_kernel (the forward's
+//       16-pixel lane orders, v_mfma_f32_16x16x4_f32; after a training forward it starts from the saved MLP inputs instead of
+//       the gather) -- recomputes the forward per plane and forms the six MLP gradients on the matrix cores, d cur, and one
+//       record per (pixel, plane) point -- then cv_src_grad_kernel, whose single-wavefront workgroups own 8 x 8 tiles of SOURCE
+//       texels and collect, plane by plane, from the pixels whose taps cover them (found through the inverse plane homography).
+//       (Per-pixel plane depths or K > 16: the round-3 one-kernel form, cost_volume_bwd_kernel, 32 pixels x parity on
+//       texel-major [y][x][parity][C/2] records, which scatters with 192-byte atomic records.)
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
 
 #include "fs_common.h"
-
-#ifndef FS_BWD16_SAVED_PREFETCH
-#define FS_BWD16_SAVED_PREFETCH 1
-#endif
-#ifndef FS_REC_PIXEL_MAJOR
-#define FS_REC_PIXEL_MAJOR 1     // records of the 16-pixel backward pass 1: [view, plane][pixel][C/4 float4 chunks] (0, A/B: chunk-planar)
-#endif
 
 namespace fs {
 
@@ -194,17 +186,6 @@ __global__ void cv_proj_kernel(int n, const float* __restrict__ src_Ks, const fl
 struct CvBlock { int b, grp, slice; bool ok; };
 __device__ __forceinline__ CvBlock cv_block(int B, int groups, int slices)
 {
-#ifdef FS_CV_LINEAR_GRID   // (A/B builds: round 2's order -- group fastest, then batch row, then slice)
-    {
-        CvBlock o;
-        const int id = (int)blockIdx.x, per = B * groups;
-        o.slice = id / per;
-        o.b = (id - o.slice * per) / groups;
-        o.grp = id - o.slice * per - o.b * groups;
-        o.ok = o.slice < slices;
-        return o;
-    }
-#endif
     const int xcd = (int)(blockIdx.x & 7u), j = (int)(blockIdx.x >> 3);
     const int gb = (groups + 7) >> 3;          // pixel groups per band
     const int per_b = slices * gb;
@@ -252,9 +233,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // registers, FOUR wavefronts per SIMD -- best at K <= 2, where a wavefront's chain of 8 dependent tap round trips per plane is what
 // the other wavefronts hide.  TAPS = 4: all four taps' loads in flight before the first is blended, 152 registers, three wavefronts --
 // best from K = 3 up, where the L1 / texture path is the bound and a deeper queue per wavefront feeds it better.
-#ifndef FS_FWD16_W_LDS
-#define FS_FWD16_W_LDS 2       // 0: W1 / W2 operands in registers (42); 1: W2's 16 from an LDS image; 2: both from LDS images
-#endif
 template <int C, bool SAVE, int TAPS, int WAVES>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void cost_volume16_kernel(
     int B, int K, int h, int w, int D, int slices, const float* __restrict__ curN, const float* __restrict__ srcN,
@@ -284,32 +262,31 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES, WAVE
     const int pix_m = grp * 16 + n;
     const int pull = (4 * n + g) * 4;   // ds_bpermute address: operand lane (n, g) takes gather lane 4 n + g
 
-    // ---- MLP weights in registers, in MFMA A-operand order (lane = (row n of the block, k = g)) ----
-    // (round 6: FS_FWD16_W_LDS >= 1 keeps W2's -- 2: also W1's -- operands as per-lane LDS images shared by the four wavefronts, one
-    //  ds_read_b32 where the MFMA is: the registers go to tap loads in flight, profiles/r6_cv_fwd_taps_ab.txt)
-    constexpr bool kW2Lds = FS_FWD16_W_LDS >= 1, kW1Lds = FS_FWD16_W_LDS >= 2;
-    __shared__ float s_w[(kW2Lds ? 16 : 0) * 64 + (kW1Lds ? 2 * NT : 0) * 64 + 64];
+    // ---- MLP weights in MFMA A-operand order (lane = (row n of the block, k = g)) ----
+    // (round 6: W1's and W2's operands are per-lane LDS images shared by the four wavefronts, one ds_read_b32 where the MFMA is:
+    //  the registers go to tap loads in flight, profiles/r6_cv_fwd_taps_ab.txt)
+    __shared__ float s_w[16 * 64 + 2 * NT * 64 + 64];
     float* const sA2 = s_w + lane;                          // [(blk * 8 + t) * 64]
-    float* const sA1 = s_w + (kW2Lds ? 16 * 64 : 0) + lane; // [(blk * NT + t) * 64]
-    float a1[kW1Lds ? 1 : 2][kW1Lds ? 1 : NT], a2[kW2Lds ? 1 : 2][kW2Lds ? 1 : 8], w3v[2][4], b2v[2][4];
+    float* const sA1 = s_w + 16 * 64 + lane;                // [(blk * NT + t) * 64]
+    float w3v[2][4], b2v[2][4];
 #pragma unroll
     for (int blk = 0; blk < 2; ++blk) {
         const int u = 16 * blk + n;
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             const float v = t < NR ? w1[u * (C + 1) + 16 * (t >> 2) + 4 * g + (t & 3)] : (g == 0 ? w1[u * (C + 1) + C] : (g == 1 ? b1[u] : 0.0f));
-            if constexpr (kW1Lds) { if (wave == 0) sA1[(blk * NT + t) * 64] = v; } else a1[blk][t] = v;
+            if (wave == 0) sA1[(blk * NT + t) * 64] = v;
         }
 #pragma unroll
         for (int t = 0; t < 8; ++t) {
             const float v = w2[u * 32 + 16 * (t >> 2) + 4 * g + (t & 3)];
-            if constexpr (kW2Lds) { if (wave == 0) sA2[(blk * 8 + t) * 64] = v; } else a2[blk][t] = v;
+            if (wave == 0) sA2[(blk * 8 + t) * 64] = v;
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) { w3v[blk][r] = w3[16 * blk + 4 * g + r]; b2v[blk][r] = b2[16 * blk + 4 * g + r]; }
     }
     const float b3v = b3[0];
-    if constexpr (kW2Lds) __syncthreads();
+    __syncthreads();
 
     // ---- current-view feature: this lane's quarter of its pixel's channels ----
     float cur[NR];
@@ -351,7 +328,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES, WAVE
         depth_next = pl[min(d + 1, d1 - 1) * ps_d];
         // (one LDS store per plane into the image array's padding, through an index the compiler cannot relate to the operand reads:
         //  without it the loop-invariant ds_reads are hoisted out of the plane loop -- back into the registers they were to free)
-        if constexpr (kW2Lds) s_w[(kW2Lds ? 16 : 0) * 64 + (kW1Lds ? 2 * NT : 0) * 64 + (lane ^ 1)] = depth;
+        s_w[16 * 64 + 2 * NT * 64 + (lane ^ 1)] = depth;
         float favg[NR];
 #pragma unroll
         for (int r = 0; r < NR; ++r) favg[r] = 0.0f;
@@ -512,7 +489,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES, WAVE
             h1[blk] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
             for (int t = 0; t < NT; ++t)
-                h1[blk] = __builtin_amdgcn_mfma_f32_16x16x4f32(kW1Lds ? sA1[(blk * NT + t) * 64] : a1[kW1Lds ? 0 : blk][kW1Lds ? 0 : t], xop[t], h1[blk], 0, 0, 0);
+                h1[blk] = __builtin_amdgcn_mfma_f32_16x16x4f32(sA1[(blk * NT + t) * 64], xop[t], h1[blk], 0, 0, 0);
         }
         // ---- layer 2 ----
         f32x4 h2[2];
@@ -521,7 +498,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES, WAVE
             h2[blk] = f32x4{b2v[blk][0], b2v[blk][1], b2v[blk][2], b2v[blk][3]};
 #pragma unroll
             for (int t = 0; t < 8; ++t)
-                h2[blk] = __builtin_amdgcn_mfma_f32_16x16x4f32(kW2Lds ? sA2[(blk * 8 + t) * 64] : a2[kW2Lds ? 0 : blk][kW2Lds ? 0 : t], lrelu(h1[t >> 2][t & 3]), h2[blk], 0, 0, 0);
+                h2[blk] = __builtin_amdgcn_mfma_f32_16x16x4f32(sA2[(blk * 8 + t) * 64], lrelu(h1[t >> 2][t & 3]), h2[blk], 0, 0, 0);
         }
         // ---- layer 3 ----
         float o = 0.0f;
@@ -755,8 +732,8 @@ __global__ __launch_bounds__(256) void cost_volume_proj_kernel(
 
 
 // ==========================================================================================
-// Backward.  Same work decomposition as the forward (a wavefront = 32 pixels x a chunk of planes,
-// lane = (pixel, channel parity)); the forward is recomputed per plane, then
+// Backward in one kernel (per-pixel plane depths or K > 16; the two-pass form below covers the rest).  A wavefront = 32 pixels
+// x a chunk of planes, lane = (pixel, channel parity); the forward is recomputed per plane, then
 //   dz2 = g * w3 * lrelu'(z2);  dh1^T = W2^T dz2^T (16 MFMA);  dz1 = dh1 * lrelu'(z1);
 //   dx^T = W1^T dz1^T with the rows of W1^T permuted so that every lane receives the gradient of
 //   exactly the channels it owns (2 x 16 MFMA) -- again no cross-lane traffic;
@@ -839,7 +816,7 @@ __device__ __forceinline__ constexpr int row_half(int i) { return (i >> 2) & 1; 
 //     adds the 16 entries of its unit that it reads as MFMA operands) and of a half-height tile of g * h2 (neighbouring
 //     pixels pre-added with one DPP step) -- two accumulators instead of 32, and z2 is dead as soon as it is computed;
 //   * dW2 and dW1 are accumulated in two phases that share the dz tile (dz2, then dz1); lrelu'(z1) is kept as a bit mask.
-template <int HC, bool SPLIT>
+template <int HC>
 __global__ __launch_bounds__(256, 2) void cost_volume_bwd_kernel(
     int B, int K, int h, int w, int D, int slices, const float* __restrict__ curT, const float* __restrict__ srcT,
     const float* __restrict__ Pmat,
@@ -848,7 +825,7 @@ __global__ __launch_bounds__(256, 2) void cost_volume_bwd_kernel(
     const float* __restrict__ w2, const float* __restrict__ b2, const float* __restrict__ w3,
     const float* __restrict__ g_out, float* __restrict__ d_curT, float* __restrict__ d_srcT,
     float* __restrict__ gw1, float* __restrict__ gb1, float* __restrict__ gw2, float* __restrict__ gb2,
-    float* __restrict__ gw3, float* __restrict__ gb3, float4* __restrict__ recS, float2* __restrict__ recM)
+    float* __restrict__ gw3, float* __restrict__ gb3)
 {
     constexpr int C = 2 * HC;
     constexpr int NBLK = (HC + 1 + 15) / 16;  // row blocks of the permuted W1^T
@@ -936,7 +913,6 @@ __global__ __launch_bounds__(256, 2) void cost_volume_bwd_kernel(
         // ---- forward recompute ----
         f32x16 z1;
         float inv, xlast;
-        uint32_t flags = 0, rare = 0;   // SPLIT: bit 2k = source k valid (dot != 0), bit 2k+1 = in front of it (z > 0); rare: bit 2k
         {
         float favg[HC];
 #pragma unroll
@@ -950,14 +926,7 @@ __global__ __launch_bounds__(256, 2) void cost_volume_bwd_kernel(
             for (int s = 0; s < HC; ++s) part += W.wv[s] * cur[s];
             float dotk = part + __shfl_xor(part, 32, 64);
             dotk = (W.zz > 0.0f) ? dotk : 0.0f;
-            if (SPLIT) {
-                flags |= (W.zz > 0.0f ? 2u : 0u) << (2 * k);
-                // in front, some tap inside the source image, and still an exactly zero score (all-zero features): the
-                // score's gradient reaches the current feature although the source is not averaged -- see below
-                if (W.zz > 0.0f && dotk == 0.0f && (W.ok[0] || W.ok[1] || W.ok[2] || W.ok[3])) rare |= 1u << (2 * k);
-            }
             if (dotk != 0.0f) {
-                if (SPLIT) flags |= 1u << (2 * k);
                 cnt += 1.0f;
                 dot_sum += dotk;
 #pragma unroll
@@ -1062,45 +1031,10 @@ __global__ __launch_bounds__(256, 2) void cost_volume_bwd_kernel(
         }
         ddot = __shfl(ddot, p, 64);  // both parities of the pixel need it
         FS_CV_T(tq2, ddot + dfavg[0]);
-        if (SPLIT) {
-            // Two-pass form (round 4): the source-feature gradient is NOT scattered from here.  What a source that counts
-            // receives from this point through each bilinear tap -- S = d favg / cnt + d dot / cnt * cur, this lane's
-            // channels -- goes to memory once, chunk-planar ([view, plane][float4 chunk][pixel]: neighbouring pixels are
-            // neighbours in memory for the writer and for the reader), with d dot / cnt and the sources' (valid, in-front)
-            // bits beside it; cv_src_grad_kernel, whose workgroups own TILES OF SOURCE TEXELS, walks the pixels that
-            // sample its tile plane by plane and accumulates in LDS: no global float atomics (259 M 192-byte atomic
-            // records per 10-view K = 8 call before: 38 of the backward's 41.5 ms).
-            if (live) {
-                const size_t pl = (size_t)b * D + d;
-                float4* rp = recS + (pl * (C / 4) + (size_t)hf * (HC / 4)) * hw + pix;
-                const float di = ddot * inv;
-#pragma unroll
-                for (int s = 0; s < HC / 4; ++s)
-                    rp[(size_t)s * hw] = make_float4(fmaf(di, cur[4 * s], dfavg[4 * s] * inv), fmaf(di, cur[4 * s + 1], dfavg[4 * s + 1] * inv),
-                                                     fmaf(di, cur[4 * s + 2], dfavg[4 * s + 2] * inv), fmaf(di, cur[4 * s + 3], dfavg[4 * s + 3] * inv));
-                if (hf == 0) recM[pl * hw + pix] = make_float2(di, __uint_as_float(flags));
-            }
-            // d cur = d dot / cnt * sum_k [z_k > 0] warped_k.  For every source that counts, [z_k > 0] = valid_k, so the
-            // sum is favg = cnt * x, and x is still in this lane's entries of the feature tile.
-#pragma unroll
-            for (int s = 0; s < HC; ++s) dcur[s] = fmaf(ddot, tx[p * XS + 2 * s + hf], dcur[s]);
-            // (a source in front whose score is EXACTLY zero with taps inside its image -- all-zero features -- is not
-            //  averaged but still passes d dot / cnt on: re-gather those, wave-uniformly; never taken on real data)
-            if (__builtin_amdgcn_ballot_w64(rare != 0u) != 0ull) {
-                for (int k = 0; k < K; ++k) {
-                    if (__builtin_amdgcn_ballot_w64(((rare >> (2 * k)) & 1u) != 0u) == 0ull) continue;
-                    warp_source<HC>(W, srcT + (((size_t)b * K + k) * hw) * C, w, h, hf, live, depth, rx, ry, rz,
-                                     Pmat + ((size_t)b * K + k) * 12, inv_w, inv_h);
-                    const float cd = ((rare >> (2 * k)) & 1u) ? inv * ddot : 0.0f;
-#pragma unroll
-                    for (int s = 0; s < HC; ++s) dcur[s] = fmaf(cd, W.wv[s], dcur[s]);
-                }
-            }
-        }
         wave_lds_sync();   // (the scatter staging below overwrites the tiles)
         FS_CV_T(tq3, gW2[0] + gW1[0][0]);
         // ---- back to the features ----
-        for (int k = 0; !SPLIT && k < K; ++k) {
+        for (int k = 0; k < K; ++k) {
             // (K = 1: W still holds this source from the forward recompute above -- no second gather)
             if (K > 1) warp_source<HC>(W, srcT + (((size_t)b * K + k) * hw) * C, w, h, hf, live, depth, rx, ry, rz,
                                         Pmat + ((size_t)b * K + k) * 12, inv_w, inv_h);
@@ -1240,7 +1174,7 @@ __global__ __launch_bounds__(256, 2) void cost_volume_bwd_kernel(
 
 
 // ==========================================================================================
-// Backward pass 1 on 16-pixel wavefronts (round 6; replaces cost_volume_bwd_kernel<., true, false> for the two-pass form).
+// Backward pass 1 on 16-pixel wavefronts (round 6; replaced round 4's 32-pixel pass 1, a record-writing cost_volume_bwd_kernel).
 // Same lane orders as the K >= 2 forward sweep above: the gather runs with lane = (pixel j, channel quarter c), the matrix
 // cores with lane = (pixel n, quarter g), and v_mfma_f32_16x16x4_f32 throughout.  What that buys over the 32-pixel kernel:
 //   * FOUR of the six products need no transposition at all: an accumulator of layer l (lane (n, g), register r = unit
@@ -1264,18 +1198,14 @@ __global__ __launch_bounds__(256, 2) void cost_volume_bwd_kernel(
 //     next plane's first tap wait also waited for them.
 // Measured against the 32-pixel kernel (profiles/r6_cv_bwd16.txt): config-3 scale 7.0 - 7.3 -> 6.7 ms, 10 views K = 8 7.5 -> 6.1 ms.
 // A workgroup covers one 32-pixel group (the same XCD-aware order as before) as two 16-pixel halves in turn; its four wavefronts
-// share the planes.  Records leave in NATURAL channel order ([view, plane][chunk of 4 channels][pixel]); cv_src_grad_kernel<C, true>
-// reads them.  d cur is summed over the workgroup's wavefronts in LDS and leaves as plain stores when the planes are not split
+// share the planes.  Records leave pixel-major in NATURAL channel order ([view, plane][pixel][chunk of 4 channels]);
+// cv_src_grad_kernel reads them.  d cur is summed over the workgroup's wavefronts in LDS and leaves as plain stores when the planes are not split
 // over workgroups.
 // ==========================================================================================
 // SAVED: the training forward kept the MLP's inputs (cost_volume16_kernel<C, true>: x, the averaged score, the validity bits) --
 // no gather here at all: three float4 loads per lane and plane instead of 4 K taps.
 template <int C, bool SAVED>
-#ifdef FS_BWD16_ONE_WAVE     // (A/B build: one wavefront per SIMD with the whole 512-register file)
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void cost_volume16_bwd_kernel(
-#else
 __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void cost_volume16_bwd_kernel(
-#endif
     int B, int K, int h, int w, int D, int slices, const float* __restrict__ curN, const float* __restrict__ srcN,
     const float* __restrict__ Pmat, const float* __restrict__ cur_invK, const float* __restrict__ planes, long long ps_b,
     long long ps_d, const float* __restrict__ w1, const float* __restrict__ b1, const float* __restrict__ w2,
@@ -1417,9 +1347,6 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
             FS_CV_T(tq0, depth);
             const float go = go_next;
             go_next = live_m ? gp[(size_t)min(d + 1, d1 - 1) * hw] : 0.0f;
-#if !FS_BWD16_SAVED_PREFETCH
-            if (SAVED && d > d0) load_saved(d);
-#endif
             // ---------------- forward recompute: gather (the forward sweep's code, plus the backward's bits) ----------------
             float favg[NR];
 #pragma unroll
@@ -1459,11 +1386,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
                 // with weight 0 --, then the blends.  (Tap by tap, each behind its own branch and wait, the two wavefronts of a SIMD
                 // spent most of a plane's time in 4 K serial memory round trips.)
                 const bool any_ok = live && (xin0 || xin1) && (yin0 || yin1);
-#ifdef FS_BWD16_NO_TAPS   // (timing-only build, WRONG results: the sweep without its tap loads)
-                if (false) {
-#else
                 if (__builtin_amdgcn_ballot_w64(any_ok) != 0ull) {
-#endif
 #ifndef FS_BWD16_TAPS_IN_FLIGHT
 #define FS_BWD16_TAPS_IN_FLIGHT 2      // taps of a source loaded together (4: measured the same, 5 more spilled registers)
 #endif
@@ -1566,9 +1489,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
                     const float4 v4 = xs_next[rb];
                     xop[4 * rb] = v4.x; xop[4 * rb + 1] = v4.y; xop[4 * rb + 2] = v4.z; xop[4 * rb + 3] = v4.w;
                 }
-#if FS_BWD16_SAVED_PREFETCH
                 if (d + 1 < d1) load_saved(d + 1);
-#endif
 #pragma unroll
                 for (int t = 0; t < NR; ++t) tX[256 * (t >> 2) + wr_at[t & 3]] = xop[t];
                 xop[NR] = g == 0 ? dot_m : (g == 1 ? 1.0f : 0.0f);
@@ -1655,11 +1576,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
                     for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
                         for (int cb = 0; cb < 2; ++cb)
-#ifdef FS_BWD16_NO_DW     // (timing-only build, WRONG weight gradients: the sweep without its two outer-product phases)
-                            acc2[rb][cb][s] += av[rb][s] + hv[cb][s];
-#else
                             acc2[rb][cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[rb][s], hv[cb][s], acc2[rb][cb], 0, 0, 0);
-#endif
             }
             FS_PHASE();
             // ---- phase 5: dz1 (to its tile) and the sums over it; its tile rows and x's (dW1 operands) on their way; dx ----
@@ -1704,18 +1621,14 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
             const float di = ddot * inv;
             if (live_m) {
                 const size_t pl = (size_t)b * D + d;
-#if FS_REC_PIXEL_MAJOR
                 // pixel-major records ([view, plane][pixel][C/4 chunks]: 4 C contiguous bytes per point): pass 2 reads the pixels of
                 // a ~10-pixel-wide box row by row, and with chunk-planar records a row was 160 useful bytes of every 256 fetched
                 float4* rp = recS + (pl * hw + pix_m) * (C / 4) + g;
-#else
-                float4* rp = recS + (pl * (C / 4) + g) * hw + pix_m;
-#endif
 #pragma unroll
                 for (int rb = 0; rb < RB; ++rb) {
                     const float4 cv = cv4[rb];
-                    rp[FS_REC_PIXEL_MAJOR ? (size_t)(4 * rb) : (size_t)(4 * rb) * hw] = make_float4(fmaf(di, cv.x, dx[rb][0] * inv), fmaf(di, cv.y, dx[rb][1] * inv),
-                                                            fmaf(di, cv.z, dx[rb][2] * inv), fmaf(di, cv.w, dx[rb][3] * inv));
+                    rp[(size_t)(4 * rb)] = make_float4(fmaf(di, cv.x, dx[rb][0] * inv), fmaf(di, cv.y, dx[rb][1] * inv),
+                                                       fmaf(di, cv.z, dx[rb][2] * inv), fmaf(di, cv.w, dx[rb][3] * inv));
                 }
                 if (g == 0) recM[pl * hw + pix_m] = make_float2(di, __uint_as_float(flags_m));
             }
@@ -1729,11 +1642,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 #pragma unroll
                         for (int cb = 0; cb < RB; ++cb) {
                             const float xv = s == 0 ? X4[cb].x : (s == 1 ? X4[cb].y : (s == 2 ? X4[cb].z : X4[cb].w));
-#ifdef FS_BWD16_NO_DW
-                            acc1[rb][cb][s] += av[rb][s] + xv;
-#else
                             acc1[rb][cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[rb][s], xv, acc1[rb][cb], 0, 0, 0);
-#endif
                         }
             }
             FS_PHASE();
@@ -1919,12 +1828,9 @@ __global__ __launch_bounds__(256) void cv_bwd_prep_kernel(
     }
 }
 
-#ifndef FS_SG_TH
-#define FS_SG_TH 8            // (A/B builds: -DFS_SG_TH=4 halves the tile and its LDS: twice the wavefronts per CU, more halo)
-#endif
-constexpr int kSgTW = 8, kSgTH = FS_SG_TH, kSgG = 4;
+constexpr int kSgTW = 8, kSgTH = 8, kSgG = 4;
 #ifdef FS_CV_SG_STATS   // debug build: [0] wave iterations, [1] pixels with a tap in the tile, [2] (tile, plane) cells walked,
-__device__ unsigned long long g_sg_stats[8];   // [3] whole-image fallbacks, [4] cells skipped (behind), [5] box pixels, [6] claim rounds
+__device__ unsigned long long g_sg_stats[8];   // [3] whole-image fallbacks, [4] cells skipped (behind), [5] box pixels
 #define FS_SG_COUNT(i, n) do { atomicAdd(&g_sg_stats[i], (unsigned long long)(n)); } while (0)
 #else
 #define FS_SG_COUNT(i, n) do {} while (0)
@@ -1933,47 +1839,37 @@ __device__ unsigned long long g_sg_stats[8];   // [3] whole-image fallbacks, [4]
 // How the taps are ADDED.  LDS float atomics are not an option on this chip: ds_add_f32 costs 193 cycles per wave
 // instruction per CU -- ds_add_u32 4.3, a ds_read_b32 + ds_write_b32 pair 11.7 (profiles/tools/lds_atomic_rate.hip,
 // profiles/r4_lds_atomic_rate.txt); the first build of this kernel, (pixel, quarter) lanes adding with ds_add_f32, ran
-// 116 ms on the 10-view K = 8 shape, 3x slower than the global atomics it was meant to replace.  So the adds are plain
-// read-modify-writes, made safe by construction: a workgroup is ONE wavefront with a tile of 8 x 8 texels (no other
-// wavefront ever touches its accumulators, no barriers), lane = pixel with all C channels (texel-major accumulator rows
-// of C + 4 floats: a tap is C/4 ds_read_b128 + C/4 ds_write_b128, and the 208-byte row stride keeps neighbouring
-// texels conflict-free); inside the wavefront two pixels collide iff they have the same tap base (x0, y0) (the taps
-// of one pixel are distinct texels, and the four taps are four instruction groups, executed in order): each pending
-// lane writes its id to claim[base], reads it back, the survivors add their four taps, the others go round again -- one
-// round at >= 1 texel per pixel, n rounds where n pixels share a base.  (The second build split the CHANNELS over the
-// four wavefronts of a 16 x 16 tile: every wavefront repeated the projection, and a serial chain of record loads, claim
-// and four dependent read-modify-writes per 64 pixels left it latency-bound -- 9.9 ms on the 10-view K = 8 shape, of which
-// the adds were hidden entirely: profiles/r4_cv_sg_v2_variants.txt.)
+// 116 ms on the 10-view K = 8 shape, 3x slower than the global atomics it was meant to replace.  So a workgroup is ONE
+// wavefront with a tile of 8 x 8 texels (no other wavefront ever touches its accumulators, no barriers), and the tile's
+// gradient lives in REGISTERS -- lane = texel of the tile, C accumulators each.  A batch of 64 pixels (lane = pixel) reaches
+// it through LDS: every pixel lane writes its record to a staging row (C/4 ds_write_b128; rows of C + 4 floats, the 208-byte
+// stride keeps neighbouring rows conflict-free) and appends (pixel lane, weight) to the list of each texel its taps cover (a
+// ds_add_rtn_u32 slot counter per texel, kSgCap entries; a tap that finds its texel's list full goes round again), then every
+// texel lane walks its list and blends the staged records it names (C/4 ds_read_b128 per entry).  Per 64 visited pixels that
+// is 12 b128 writes + ~4.5 x 12 b128 reads -- the round-4 form, read-modify-writes of LDS accumulators behind claim rounds,
+// took 48 + 48 (a ds_write_b128 costs 13 LDS cycles, a read 4).
 //   A tile's box is ~10 x 10 pixels, so kSgG = 4 planes (a quarter of the sweep apart) are walked together as one list of
 // pixels (plane by lane);
 // the four boxes are computed by 16 lanes at once (lane 4 g + q: corner q of plane g, quad reductions).  The loads of the
-// next 64 pixels are issued before the taps of the current 64 are added.
-// NAT: the records (and the current map of the rare path) are in natural channel order -- cost_volume16_bwd_kernel's -- instead of
-// the 32-pixel kernel's [parity][C/2] order.
-// FORM 1 (round 6): the tile's gradient lives in REGISTERS -- lane = texel of the 8 x 8 tile, C accumulators each -- and a batch's taps
-// reach it through LDS once instead of four read-modify-writes: every pixel lane writes its record to a staging row (C/4
-// ds_write_b128) and appends (pixel lane, weight) to the list of each texel its taps cover (a ds_add_rtn_u32 slot counter per
-// texel, kSgCap entries; a tap that finds its texel's list full goes round again), then every texel lane walks its list and blends
-// the staged records it names (C/4 ds_read_b128 per entry).  No claim rounds, no accumulator writes: per 64 visited pixels
-// 12 b128 writes + ~4.5 x 12 b128 reads instead of 48 + 48 (a ds_write_b128 costs 13 LDS cycles, a read 4).
+// next 64 pixels are issued before the taps of the current 64 are blended.  The records are cost_volume16_bwd_kernel's
+// (pixel-major, natural channel order).
 #ifndef FS_SG_CAP
 #define FS_SG_CAP 8
 #endif
 constexpr int kSgCap = FS_SG_CAP;
-template <int C, bool NAT, int FORM>
+template <int C>
 __global__ __launch_bounds__(64) void cv_src_grad_kernel(
     int B, int K, int h, int w, int D, int chunks, int tiles_x, int tiles_y, const float* __restrict__ curT,
     const float4* __restrict__ recS, const float2* __restrict__ recM, const float* __restrict__ Pmat,
     const float* __restrict__ Ginv, const float* __restrict__ cur_invK, const float* __restrict__ planes, long long ps_b,
     long long ps_d, float* __restrict__ d_src)
 {
-    constexpr int TW = kSgTW, TH = kSgTH, NT = TW * TH, NV = C / 4, ST = C + 4, HC = C / 2, G = kSgG;
-    constexpr int kClaim = (TW + 1) * (TH + 1) + 3;   // bases (lx, ly) in [-1, TW - 1] x [-1, TH - 1]
-    static_assert(FORM == 0 || NT == 64, "the register form keeps one texel per lane");
-    __shared__ __attribute__((aligned(16))) float acc[NT * ST];          // FORM 0: the accumulators; FORM 1: the batch's staged records
-    __shared__ uint32_t claim_[FORM == 0 ? kClaim : 64];                 // FORM 1: entries in each texel's list
-    __shared__ uint2 lst_[FORM == 0 ? 1 : 64 * kSgCap];                  // FORM 1: (pixel lane, weight bits)
-    float4 accr[NV];                                                     // FORM 1: this lane's texel
+    constexpr int TW = kSgTW, TH = kSgTH, NT = TW * TH, NV = C / 4, ST = C + 4, G = kSgG;
+    static_assert(NT == 64, "one texel per lane");
+    __shared__ __attribute__((aligned(16))) float acc[NT * ST];          // the batch's staged records
+    __shared__ uint32_t claim_[64];                                      // entries in each texel's list
+    __shared__ uint2 lst_[64 * kSgCap];                                  // (pixel lane, weight bits)
+    float4 accr[NV];                                                     // this lane's texel
     const int hw = h * w, T = tiles_x * tiles_y;
     // XCD x (= workgroup id % 8) owns the x-th contiguous range of tiles of every view: the workgroups in flight on an XCD
     // -- the same tiles of all K sources, which read the same records -- share one L2
@@ -1987,13 +1883,9 @@ __global__ __launch_bounds__(64) void cv_src_grad_kernel(
     const int tx0 = (tile % tiles_x) * TW, ty0 = (tile / tiles_x) * TH;
     const int tw_ = min(TW, w - tx0), th_ = min(TH, h - ty0);
     const int lane = threadIdx.x;
-    if (FORM == 0) {
-        for (int e = lane; e < NT * ST / 4; e += 64) ((float4*)acc)[e] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    } else {
-        claim_[lane] = 0u;
+    claim_[lane] = 0u;
 #pragma unroll
-        for (int s = 0; s < NV; ++s) accr[s] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    }
+    for (int s = 0; s < NV; ++s) accr[s] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     wave_lds_sync();
     volatile uint32_t* const claim = claim_;
     const float* P = Pmat + ((size_t)b * K + k) * 12;
@@ -2005,11 +1897,11 @@ __global__ __launch_bounds__(64) void cv_src_grad_kernel(
     const float Y0 = (float)ty0 - 0.55f, Y1 = (float)(ty0 + th_) + 0.55f;
     const uint32_t kbit = 2u * (uint32_t)k;
 
-    struct Geo { int t00, cid; float tx, ty; uint32_t okm; bool pend; };
+    struct Geo { int t00; float tx, ty; uint32_t okm; bool pend; };
 
     // The four planes of a group lie a quarter of the sweep apart (dg + g * gstride): walked together, the same pixel in
     // two of them samples texels many disparity steps apart -- with neighbouring planes (~0.56 texel apart at the native
-    // size) every batch that straddles two planes had lanes with the same tap base, i.e. a second claim round.
+    // size) every batch that straddles two planes had lanes with the same tap base, i.e. a second claim round of the round-4 form.
     const int gstride = (d1 - d0 + G - 1) / G;
     for (int dg = d0; dg < d0 + gstride; ++dg) {
         // ---- the tile's preimage boxes in the current view, four planes at once: lane 4 g + q = corner q of its plane ----
@@ -2104,21 +1996,14 @@ __global__ __launch_bounds__(64) void cv_src_grad_kernel(
             ge.okm = (okx0 && oky0 ? 1u : 0u) | (okx1 && oky0 ? 2u : 0u) | (okx0 && oky1 ? 4u : 0u) | (okx1 && oky1 ? 8u : 0u);
             bool pend = act && zz > 0.0f && ge.okm != 0u;
             ge.t00 = pend ? (int)ly * TW + (int)lx : 0;       // tile-local index of tap (0, 0), >= -(TW + 1)
-            ge.cid = pend ? ((int)ly + 1) * (TW + 1) + (int)lx + 1 : 0;   // the base's own slot (t00 wraps: (7, y) = (-1, y + 1))
             if (pend) {
-#ifdef FS_SG_FLOOR   // timing-only build (WRONG results): every plane group reads the records of the FIRST one -- 4 planes per view stay
-                     // cache-resident, i.e. the sweep with its record bytes taken out: what the projection + claim + LDS adds cost alone
-                const size_t pl = (size_t)b * D + (size_t)(d0 + gs * gstride);
-#else
                 const size_t pl = (size_t)b * D + (size_t)(dg + gs * gstride);
-#endif
                 const float2 mt = recM[pl * hw + pix];
                 const uint32_t fl = __float_as_uint(mt.y) >> kbit;
                 pend = (fl & 2u) != 0u;                       // (the first pass's own z_k > 0)
-                const bool pm = NAT && FS_REC_PIXEL_MAJOR;     // (the 16-pixel pass 1's records are pixel-major)
-                const float4* sp = pm ? recS + (pl * hw + pix) * NV : recS + pl * NV * hw + pix;
+                const float4* sp = recS + (pl * hw + pix) * NV;
 #pragma unroll
-                for (int s = 0; s < NV; ++s) S[s] = sp[pm ? (size_t)s : (size_t)s * hw];
+                for (int s = 0; s < NV; ++s) S[s] = sp[s];
                 if (pend && !(fl & 1u)) {
                     // in front, not averaged (an exactly zero score): only d dot / cnt * cur reaches this source
                     const float4* c4 = (const float4*)(curT + ((size_t)b * hw + pix) * C);
@@ -2137,7 +2022,7 @@ __global__ __launch_bounds__(64) void cv_src_grad_kernel(
             }
 #endif
         };
-        // ---- FORM 1: records to the staging rows, taps to their texels' lists; then every texel lane blends its list ----
+        // ---- records to the staging rows, taps to their texels' lists; then every texel lane blends its list ----
         struct Taps { int t00; float tx, ty; uint32_t todo; };
         auto place_taps = [&](Taps& tp) __attribute__((always_inline)) {
 #pragma unroll
@@ -2188,67 +2073,19 @@ __global__ __launch_bounds__(64) void cv_src_grad_kernel(
                 place_taps(tp);          // (taps that found their texel's list full: the staged records are still there)
             }
         };
-        // ---- FORM 0: the adds: claim rounds, then four taps of C/4 float4 read-modify-writes ----
-        auto process = [&](const Geo& ge, const float4 (&S)[NV]) __attribute__((always_inline)) {
-            bool pend = ge.pend;
-            while (__builtin_amdgcn_ballot_w64(pend) != 0ull) {
-#ifdef FS_CV_SG_STATS
-                if (lane == 0) FS_SG_COUNT(6, 1);
-#endif
-                if (pend) claim[ge.cid] = (uint32_t)lane;
-                wave_lds_sync();
-                const bool win = pend && claim[ge.cid] == (uint32_t)lane;
-                // Two winners never share a tap BASE, but tap 1 of base (0, 0) is tap 0 of base (1, 0): the four tap groups
-                // must reach the LDS in program order (all lanes' tap t before any lane's tap t + 1).  wave_lds_sync() -- a
-                // compiler-only fence, no instruction -- keeps the scheduler from hoisting a later group's ds_reads above an
-                // earlier group's ds_writes, which are provably distinct addresses within ONE lane.
-#pragma unroll
-                for (int tap = 0; tap < 4; ++tap) {
-                    const int ox = tap & 1, oy = tap >> 1;
-                    if (win && (ge.okm & (1u << tap))) {
-                        const float wt = (ox ? ge.tx : 1.0f - ge.tx) * (oy ? ge.ty : 1.0f - ge.ty);
-                        float4* a = (float4*)(acc + (ge.t00 + oy * TW + ox) * ST);
-#pragma unroll
-                        for (int s = 0; s < NV; ++s) {
-                            float4 v = a[s];
-                            v.x = fmaf(wt, S[s].x, v.x); v.y = fmaf(wt, S[s].y, v.y);
-                            v.z = fmaf(wt, S[s].z, v.z); v.w = fmaf(wt, S[s].w, v.w);
-                            a[s] = v;
-                        }
-                    }
-                    wave_lds_sync();
-                }
-                pend = pend && !win;
-            }
-        };
-        if constexpr (FORM == 1) {
-            // one record buffer: the next batch's loads are issued as soon as this batch's records sit in their staging rows, and
-            // are in flight while the lists are blended (a second register buffer costs the third wavefront per SIMD: 3.0 vs 2.8 ms)
-            Geo gA;
-            float4 SA[NV];
-            stage(0, gA, SA);
-            for (int i0 = 0; i0 < N; i0 += 64) {
-                const Taps tp = put_records(gA, SA);
-                if (i0 + 64 < N) stage(i0 + 64, gA, SA);
-                blend_lists(tp);
-            }
-            continue;
-        } else {
-        Geo gA, gB;
-        float4 SA[NV], SB[NV];
+        // one record buffer: the next batch's loads are issued as soon as this batch's records sit in their staging rows, and
+        // are in flight while the lists are blended (a second register buffer costs the third wavefront per SIMD: 3.0 vs 2.8 ms)
+        Geo gA;
+        float4 SA[NV];
         stage(0, gA, SA);
-        for (int i0 = 0; i0 < N; i0 += 128) {
-            const bool moreB = i0 + 64 < N;
-            if (moreB) stage(i0 + 64, gB, SB);
-            process(gA, SA);
-            if (!moreB) break;
-            if (i0 + 128 < N) stage(i0 + 128, gA, SA);
-            process(gB, SB);
-        }
+        for (int i0 = 0; i0 < N; i0 += 64) {
+            const Taps tp = put_records(gA, SA);
+            if (i0 + 64 < N) stage(i0 + 64, gA, SA);
+            blend_lists(tp);
         }
     }
     wave_lds_sync();
-    // ---- the tile leaves once, in the caller's [C, h, w] layout (slot q = parity * C/2 + s  ->  channel 2 s + parity; NAT: q) ----
+    // ---- the tile leaves once, in the caller's [C, h, w] layout ----
     {
         float* const dmap = d_src + (((size_t)b * K + k) * C) * hw;
         const int ty = lane / TW, tx = lane % TW;
@@ -2256,11 +2093,11 @@ __global__ __launch_bounds__(64) void cv_src_grad_kernel(
         float* const dpx = dmap + (size_t)(ty0 + ty) * w + (tx0 + tx);
 #pragma unroll
         for (int s = 0; s < NV; ++s) {
-            const float4 v = FORM == 1 ? accr[s] : ((const float4*)(acc + (lane < NT ? lane : 0) * ST))[s];
+            const float4 v = accr[s];
             const float vv[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const int q = 4 * s + e, ch = NAT ? q : 2 * (q % HC) + q / HC;
+                const int ch = 4 * s + e;
                 if (inside) { if (chunks > 1) atomicAdd(dpx + (size_t)ch * hw, vv[e]); else dpx[(size_t)ch * hw] = vv[e]; }
             }
         }
@@ -2307,8 +2144,6 @@ static bool cv_use_projected(int K)
 
 static int cv_plane_split(int B, int groups, int D)
 {
-    static const int forced = getenv("FS_CV_SPLIT") ? atoi(getenv("FS_CV_SPLIT")) : 0;   // (tuning knob)
-    if (forced > 0) return forced;
     int split = 1;
     while (split * 4 * 4 < D && (long long)B * groups * 4 * split < 12288) split *= 2;
     return split;
@@ -2407,9 +2242,8 @@ static int cv_forward_impl(int32_t B, int32_t K, int32_t C, int32_t h, int32_t w
                                    cur_invK, planes, (long long)plane_stride_b, (long long)plane_stride_d,
                                    (long long)plane_stride_pix, w1, b1, w2, b2, w3, b3, out, xs, xm, xhdr);
             };
-            // (K <= 2: tap by tap at four wavefronts per SIMD; K >= 3: a source's four taps in flight at three -- FS_CV_FWD_SHAPE=1 / 4 forces one)
-            static const int force_shape = [] { const char* e = getenv("FS_CV_FWD_SHAPE"); return e ? atoi(e) : 0; }();
-            const bool deep = force_shape == 4 || (force_shape != 1 && K >= 3);
+            // (K <= 2: tap by tap at four wavefronts per SIMD; K >= 3: a source's four taps in flight at three)
+            const bool deep = K >= 3;
             if (C == 48) {
                 if (deep) { if (saved) sweep16(cost_volume16_kernel<48, true, 4, 3>); else sweep16(cost_volume16_kernel<48, false, 4, 3>); }
                 else { if (saved) sweep16(cost_volume16_kernel<48, true, 1, 4>); else sweep16(cost_volume16_kernel<48, false, 1, 4>); }
@@ -2548,26 +2382,20 @@ static int cv_backward_impl(int32_t B, int32_t K, int32_t C, int32_t h, int32_t 
         set_last_error("cost volume backward memset", hipGetLastError());
         return FS_ERR_LAUNCH;
     }
-    // pass 1 of the two-pass form: the 16-pixel kernel on natural-order maps (round 6), FS_CV_BWD16=0 or a saved-activation
-    // call: the 32-pixel kernel on [parity][C/2] records
-    bool bwd16 = two_pass;
-    if (const char* e = getenv("FS_CV_BWD16")) bwd16 = bwd16 && atoi(e) != 0;
-    if (!bwd16) saved = nullptr;   // (the saved activations are in the 16-pixel kernel's chunk order: the other forms recompute)
+    // the two-pass form runs the 16-pixel kernels on natural-order maps, the one-kernel scatter form works on [parity][C/2] records
     const uint32_t* xhdr = (const uint32_t*)saved;
     const float4* xs = saved ? (const float4*)((const char*)saved + 256) : nullptr;
     const float2* xm = saved ? (const float2*)((const char*)saved + 256 + cv_saved_xs_bytes(B, C, h, w, D)) : nullptr;
-    cv_relayout(!bwd16, false, cur_feats, curT, C, hw, B, st);
-    cv_relayout(!bwd16, false, src_feats, srcT, C, hw, B * K, st);
+    cv_relayout(!two_pass, false, cur_feats, curT, C, hw, B, st);
+    cv_relayout(!two_pass, false, src_feats, srcT, C, hw, B * K, st);
     const int groups = (hw + 31) / 32;
     const int bslices = cv_bwd_plane_split(B, groups, D);
     auto sweep = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, dim3(cv_grid(B, groups, bslices)), dim3(256), 0, st, B, K, h, w, D, bslices, curT, srcT,
                            Pmat, cur_invK, planes, (long long)plane_stride_b,
                            (long long)plane_stride_d, (long long)plane_stride_pix, w1, b1, w2, b2, w3, grad_out,
-                           d_curT, d_srcT, d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, recS, recM);
+                           d_curT, d_srcT, d_w1, d_b1, d_w2, d_b2, d_w3, d_b3);
     };
-    // pass 2's form: 1 = register accumulators fed through per-texel lists (round 6), 0 = LDS read-modify-writes behind claim rounds
-    static const int sg_form = [] { const char* e = getenv("FS_CV_SG_FORM"); return e ? atoi(e) : 1; }() && kSgTW * kSgTH == 64 ? 1 : 0;
     auto tile_sweep = [&](auto kernel) {
         const unsigned grid = 8u * (unsigned)B * (unsigned)((tiles + 7) >> 3) * (unsigned)K * (unsigned)chunks;
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), 0, st, B, K, h, w, D, chunks, tiles_x, tiles_y, curT,
@@ -2579,29 +2407,19 @@ static int cv_backward_impl(int32_t B, int32_t K, int32_t C, int32_t h, int32_t 
                            Pmat, cur_invK, planes, (long long)plane_stride_b, (long long)plane_stride_d, w1, b1, w2, b2, w3,
                            grad_out, d_curT, d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, recS, recM, xs, xm, xhdr);
     };
-    if (bwd16) {
+    if (two_pass) {
         if (C == 48) {
             if (saved) sweep16(cost_volume16_bwd_kernel<48, true>); else sweep16(cost_volume16_bwd_kernel<48, false>);
-            if constexpr (kSgTW * kSgTH == 64) { if (sg_form) tile_sweep(cv_src_grad_kernel<48, true, 1>); else tile_sweep(cv_src_grad_kernel<48, true, 0>); }
-            else tile_sweep(cv_src_grad_kernel<48, true, 0>);
+            tile_sweep(cv_src_grad_kernel<48>);
         } else {
             if (saved) sweep16(cost_volume16_bwd_kernel<16, true>); else sweep16(cost_volume16_bwd_kernel<16, false>);
-            if constexpr (kSgTW * kSgTH == 64) { if (sg_form) tile_sweep(cv_src_grad_kernel<16, true, 1>); else tile_sweep(cv_src_grad_kernel<16, true, 0>); }
-            else tile_sweep(cv_src_grad_kernel<16, true, 0>);
-        }
-    } else if (two_pass) {
-        if (C == 48) {
-            sweep(cost_volume_bwd_kernel<24, true>);
-            tile_sweep(cv_src_grad_kernel<48, false, 0>);
-        } else {
-            sweep(cost_volume_bwd_kernel<8, true>);
-            tile_sweep(cv_src_grad_kernel<16, false, 0>);
+            tile_sweep(cv_src_grad_kernel<16>);
         }
     } else {
-        if (C == 48) sweep(cost_volume_bwd_kernel<24, false>); else sweep(cost_volume_bwd_kernel<8, false>);
+        if (C == 48) sweep(cost_volume_bwd_kernel<24>); else sweep(cost_volume_bwd_kernel<8>);
         cv_relayout(true, true, d_srcT, d_src_feats, C, hw, B * K, st);
     }
-    cv_relayout(!bwd16, true, d_curT, d_cur_feats, C, hw, B, st);
+    cv_relayout(!two_pass, true, d_curT, d_cur_feats, C, hw, B, st);
     FS_CHECK_LAUNCH("cost_volume_backward");
     return FS_OK;
 }

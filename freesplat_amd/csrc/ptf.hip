@@ -308,6 +308,7 @@ struct PtfState { float *G, *X, *R, *O, *E, *D; };
 
 // SPLIT: the fused rows whose latent row the GRU wrote itself (`fused` == NULL: the fold) are handled by ptf_write_state_fused_kernel,
 // four lanes per row -- they move ~300 bytes, not a 256-byte latent row; this launch then walks the kept and the appended rows only.
+// !SPLIT: every row, 16 lanes per row (fs_ptf_write_state, whose fused latent rows come from `fused`).
 template <bool SPLIT>
 __global__ __launch_bounds__(256) void ptf_write_state_kernel(
     int n_keep, int n_fuse, int n_app, const int32_t* __restrict__ counts, const long long* __restrict__ keep_idx,
@@ -437,9 +438,8 @@ __global__ __launch_bounds__(256) void ptf_write_state_fused_kernel(
 // ------------------------------------------------------------------------------------------
 struct PtfGrad { float *G, *X, *R, *O, *E, *D; };   // any member may be NULL (no gradient for that field)
 
-// SPLIT: the fused rows are handled by ptf_write_state_bwd_fused_kernel (4 lanes per row instead of 16: a fused row moves ~300 bytes,
-// not a 256-byte latent row, and 10 of its 16 lanes had nothing to do) -- this launch then walks the kept and the appended rows only.
-template <bool SPLIT>
+// The kept and the appended rows; the fused rows are handled by ptf_write_state_bwd_fused_kernel (4 lanes per row instead of 16: a
+// fused row moves ~300 bytes, not a 256-byte latent row).
 __global__ __launch_bounds__(256) void ptf_write_state_bwd_kernel(
     int n_keep, int n_fuse, int n_app, const long long* __restrict__ keep_idx, const long long* __restrict__ fuse_idx,
     const long long* __restrict__ fuse_pix, const long long* __restrict__ app_pix, PtfState s,
@@ -448,141 +448,58 @@ __global__ __launch_bounds__(256) void ptf_write_state_bwd_kernel(
     float* __restrict__ g_rho_i, float* __restrict__ g_om_i, float* __restrict__ g_d_i)
 {
     const int c = threadIdx.x & 15;
-    const int n_out = n_keep + n_fuse + n_app;
     const float4 z4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if constexpr (SPLIT) {
-        // kept + appended rows only (the grid covers a quarter of them): FOUR rows per 16-lane group in flight -- indices, then every
-        // load (the out row's gradient; an appended pixel's accumulated values), then the stores.  Lane c: float4 c of the latent row;
-        // lanes 0 - 3 the extrinsics, 4 - 6 the position, 7 - 9 the scalars R, O, D.
-        constexpr int U = 4;
-        const long long n_ka = (long long)n_keep + n_app, G = (long long)gridDim.x * 16;
-        const long long r0 = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);
-        long long dst[U];
-        bool kept[U], live[U];
+    // kept + appended rows only (the grid covers a quarter of them): FOUR rows per 16-lane group in flight -- indices, then every
+    // load (the out row's gradient; an appended pixel's accumulated values), then the stores.  Lane c: float4 c of the latent row;
+    // lanes 0 - 3 the extrinsics, 4 - 6 the position, 7 - 9 the scalars R, O, D.
+    constexpr int U = 4;
+    const long long n_ka = (long long)n_keep + n_app, G = (long long)gridDim.x * 16;
+    const long long r0 = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);
+    long long dst[U];
+    bool kept[U], live[U];
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const long long r = r0 + u * G;
-            live[u] = r < n_ka; kept[u] = r < n_keep;
-            dst[u] = 0;
-            if (live[u]) dst[u] = kept[u] ? keep_idx[r] : app_pix[r - n_keep];
-        }
-        float4 g[U], e[U], acc[U];
-        float x[U], q[U], ax[U], aq[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            g[u] = e[u] = acc[u] = z4; x[u] = q[u] = ax[u] = aq[u] = 0.0f;
-            if (!live[u]) continue;            // (no loads for rows that do not exist)
-            const long long r = r0 + u * G;
-            const size_t row = (size_t)(kept[u] ? r : r + n_fuse);
-            const long long m = dst[u];
-            if (go.G) g[u] = ((const float4*)(go.G + row * 64))[c];
-            if (c < 4 && go.E && kept[u]) e[u] = ((const float4*)(go.E + row * 16))[c];
-            if (c >= 4 && c < 7 && go.X) x[u] = go.X[3 * row + (c - 4)];
-            if (c >= 7 && c < 10) { const float* gp = c == 7 ? go.R : (c == 8 ? go.O : go.D); if (gp) q[u] = gp[row]; }
-            if (!kept[u]) {                    // an appended pixel is appended once and never fused: plain read-modify-write
-                acc[u] = ((const float4*)(g_lat_i + m * 64))[c];
-                if (c >= 4 && c < 7) ax[u] = g_x_i[3 * m + (c - 4)];
-                if (c >= 7 && c < 10) aq[u] = (c == 7 ? g_rho_i : (c == 8 ? g_om_i : g_d_i))[m];
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (!live[u]) continue;
-            const long long m = dst[u];
-            if (kept[u]) {
-                ((float4*)(gs.G + m * 64))[c] = g[u];
-                if (c < 4) ((float4*)(gs.E + m * 16))[c] = e[u];
-                if (c >= 4 && c < 7) gs.X[3 * m + (c - 4)] = x[u];
-                if (c == 7) gs.R[m] = q[u];
-                if (c == 8) gs.O[m] = q[u];
-                if (c == 9) gs.D[m] = q[u];
-            } else {
-                ((float4*)(g_lat_i + m * 64))[c] = make_float4(acc[u].x + g[u].x, acc[u].y + g[u].y, acc[u].z + g[u].z, acc[u].w + g[u].w);
-                if (c >= 4 && c < 7 && go.X) g_x_i[3 * m + (c - 4)] = ax[u] + x[u];
-                if (c == 7 && go.R) g_rho_i[m] = aq[u] + q[u];
-                if (c == 8 && go.O) g_om_i[m] = aq[u] + q[u];
-                if (c == 9 && go.D) g_d_i[m] = aq[u] + q[u];
-            }
-        }
-        return;
+    for (int u = 0; u < U; ++u) {
+        const long long r = r0 + u * G;
+        live[u] = r < n_ka; kept[u] = r < n_keep;
+        dst[u] = 0;
+        if (live[u]) dst[u] = kept[u] ? keep_idx[r] : app_pix[r - n_keep];
     }
-    const int row = blockIdx.x * 16 + (threadIdx.x >> 4);
-    if (row >= n_out) return;
-    const float4 dG = go.G ? ((const float4*)(go.G + (size_t)row * 64))[c] : z4;
-    if (row < n_keep) {
-        const long long m = keep_idx[row];
-        ((float4*)(gs.G + m * 64))[c] = dG;
-        if (c < 4) ((float4*)(gs.E + m * 16))[c] = go.E ? ((const float4*)(go.E + (size_t)row * 16))[c] : z4;
-        if (c == 4) {
+    float4 g[U], e[U], acc[U];
+    float x[U], q[U], ax[U], aq[U];
 #pragma unroll
-            for (int k = 0; k < 3; ++k) gs.X[3 * m + k] = go.X ? go.X[3 * (size_t)row + k] : 0.0f;
+    for (int u = 0; u < U; ++u) {
+        g[u] = e[u] = acc[u] = z4; x[u] = q[u] = ax[u] = aq[u] = 0.0f;
+        if (!live[u]) continue;            // (no loads for rows that do not exist)
+        const long long r = r0 + u * G;
+        const size_t row = (size_t)(kept[u] ? r : r + n_fuse);
+        const long long m = dst[u];
+        if (go.G) g[u] = ((const float4*)(go.G + row * 64))[c];
+        if (c < 4 && go.E && kept[u]) e[u] = ((const float4*)(go.E + row * 16))[c];
+        if (c >= 4 && c < 7 && go.X) x[u] = go.X[3 * row + (c - 4)];
+        if (c >= 7 && c < 10) { const float* gp = c == 7 ? go.R : (c == 8 ? go.O : go.D); if (gp) q[u] = gp[row]; }
+        if (!kept[u]) {                    // an appended pixel is appended once and never fused: plain read-modify-write
+            acc[u] = ((const float4*)(g_lat_i + m * 64))[c];
+            if (c >= 4 && c < 7) ax[u] = g_x_i[3 * m + (c - 4)];
+            if (c >= 7 && c < 10) aq[u] = (c == 7 ? g_rho_i : (c == 8 ? g_om_i : g_d_i))[m];
         }
-        if (c == 5) {
-            gs.R[m] = go.R ? go.R[row] : 0.0f;
-            gs.O[m] = go.O ? go.O[row] : 0.0f;
-            gs.D[m] = go.D ? go.D[row] : 0.0f;
-        }
-    } else if (row < n_keep + n_fuse) {
-        const int t = row - n_keep;
-        const long long m = fuse_idx[t], p = fuse_pix[t];
-        const float w0 = s.R[m], w1 = rho_i[p], ws = w0 + w1, inv = 1.0f / ws;
-        // (the latent row's gradient goes through the GRU: ptf_gru_inputs_bwd writes gs.G[m])
-        float dw0 = 0.0f, dw1 = 0.0f;  // partial sums of this lane; reduced over the 16-lane group below
-        if (c < 4) {
-            const float4 a = ((const float4*)(s.E + m * 16))[c], b = ((const float4*)E_i)[c];
-            const float4 g = go.E ? ((const float4*)(go.E + (size_t)row * 16))[c] : z4;
-            const float ox = (a.x * w0 + b.x * w1) * inv, oy = (a.y * w0 + b.y * w1) * inv;
-            const float oz = (a.z * w0 + b.z * w1) * inv, ow = (a.w * w0 + b.w * w1) * inv;
-            ((float4*)(gs.E + m * 16))[c] = make_float4(g.x * w0 * inv, g.y * w0 * inv, g.z * w0 * inv, g.w * w0 * inv);
-            dw0 += (g.x * (a.x - ox) + g.y * (a.y - oy) + g.z * (a.z - oz) + g.w * (a.w - ow)) * inv;
-            dw1 += (g.x * (b.x - ox) + g.y * (b.y - oy) + g.z * (b.z - oz) + g.w * (b.w - ow)) * inv;
-        }
-        if (c == 4) {
+    }
 #pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const float a = s.X[3 * m + k], b = x_i[3 * p + k], g = go.X ? go.X[3 * (size_t)row + k] : 0.0f;
-                const float o = (a * w0 + b * w1) * inv;
-                gs.X[3 * m + k] = g * w0 * inv;
-                atomicAdd(&g_x_i[3 * p + k], g * w1 * inv);
-                dw0 += g * (a - o) * inv;
-                dw1 += g * (b - o) * inv;
-            }
-        }
-        if (c == 5) {
-            const float a = s.D[m], b = d_i[p], g = go.D ? go.D[row] : 0.0f;
-            const float o = (a * w0 + b * w1) * inv;
-            gs.D[m] = g * w0 * inv;
-            atomicAdd(&g_d_i[p], g * w1 * inv);
-            dw0 += g * (a - o) * inv;
-            dw1 += g * (b - o) * inv;
-            const float gR = go.R ? go.R[row] : 0.0f, gO = go.O ? go.O[row] : 0.0f;
-            dw0 += gR; dw1 += gR;          // R_out = w0 + w1
-            gs.O[m] = gO;                  // O_out = O[m] + om_i[p]
-            atomicAdd(&g_om_i[p], gO);
-        }
-        // sum dw0 / dw1 over lanes 0..5 of the 16-lane group (xor shuffles stay inside the group)
-#pragma unroll
-        for (int d = 8; d >= 1; d >>= 1) {
-            dw0 += __shfl_xor(dw0, d, 64);
-            dw1 += __shfl_xor(dw1, d, 64);
-        }
-        if (c == 0) {
-            gs.R[m] = dw0;                 // (+ the positional-encoding term: ptf_gru_inputs_bwd adds it)
-            atomicAdd(&g_rho_i[p], dw1);
-        }
-    } else {
-        const long long p = app_pix[row - n_keep - n_fuse];
-        float4* q = (float4*)(g_lat_i + p * 64) + c;   // an appended pixel is appended once and never fused
-        const float4 v = *q;
-        *q = make_float4(v.x + dG.x, v.y + dG.y, v.z + dG.z, v.w + dG.w);
-        if (c == 4 && go.X) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) g_x_i[3 * p + k] += go.X[3 * (size_t)row + k];
-        }
-        if (c == 5) {
-            if (go.R) g_rho_i[p] += go.R[row];
-            if (go.O) g_om_i[p] += go.O[row];
-            if (go.D) g_d_i[p] += go.D[row];
+    for (int u = 0; u < U; ++u) {
+        if (!live[u]) continue;
+        const long long m = dst[u];
+        if (kept[u]) {
+            ((float4*)(gs.G + m * 64))[c] = g[u];
+            if (c < 4) ((float4*)(gs.E + m * 16))[c] = e[u];
+            if (c >= 4 && c < 7) gs.X[3 * m + (c - 4)] = x[u];
+            if (c == 7) gs.R[m] = q[u];
+            if (c == 8) gs.O[m] = q[u];
+            if (c == 9) gs.D[m] = q[u];
+        } else {
+            ((float4*)(g_lat_i + m * 64))[c] = make_float4(acc[u].x + g[u].x, acc[u].y + g[u].y, acc[u].z + g[u].z, acc[u].w + g[u].w);
+            if (c >= 4 && c < 7 && go.X) g_x_i[3 * m + (c - 4)] = ax[u] + x[u];
+            if (c == 7 && go.R) g_rho_i[m] = aq[u] + q[u];
+            if (c == 8 && go.O) g_om_i[m] = aq[u] + q[u];
+            if (c == 9 && go.D) g_d_i[m] = aq[u] + q[u];
         }
     }
 }
@@ -873,19 +790,12 @@ static int fold_step_impl(int32_t M_max, const int32_t* M_dev, int32_t h, int32_
     PtfState so{oG, oX, oR, oO, oE, oD};
     const long long n_out_max = (long long)M_max + P;
     // (the counts are on the device: both grids cover their worst case, workgroups past the rows that exist leave at once)
-    static const bool split = [] { const char* e = getenv("FS_PTF_WS_SPLIT"); return !(e && atoi(e) == 0); }();
-    if (split) {
-        const unsigned cap = 256 * 8 * 4;        // 8 workgroups per CU resident, four rounds of them: enough to balance, few enough to be cheap when empty
-        hipLaunchKernelGGL(ptf_write_state_kernel<true>, dim3(std::min<unsigned>((unsigned)((n_out_max + 15) / 16), cap)), dim3(256), 0, st, 0, 0, 0,
-                           (const int32_t*)counts, (const long long*)keep, (const long long*)fuse, (const long long*)fpix,
-                           (const long long*)app, si, g_i, x_i, rho_i, om_i, d_i, E_i, (const float*)nullptr, so);
-        hipLaunchKernelGGL(ptf_write_state_fused_kernel, dim3(std::min<unsigned>((unsigned)((nf_max + 63) / 64), cap)), dim3(256), 0, st, 0, 0,
-                           (const int32_t*)counts, (const long long*)fuse, (const long long*)fpix, si, x_i, rho_i, om_i, d_i, E_i, so);
-    } else {
-        hipLaunchKernelGGL(ptf_write_state_kernel<false>, dim3((unsigned)((n_out_max + 15) / 16)), dim3(256), 0, st, 0, 0, 0,
-                           (const int32_t*)counts, (const long long*)keep, (const long long*)fuse, (const long long*)fpix,
-                           (const long long*)app, si, g_i, x_i, rho_i, om_i, d_i, E_i, (const float*)nullptr, so);
-    }
+    const unsigned cap = 256 * 8 * 4;        // 8 workgroups per CU resident, four rounds of them: enough to balance, few enough to be cheap when empty
+    hipLaunchKernelGGL(ptf_write_state_kernel<true>, dim3(std::min<unsigned>((unsigned)((n_out_max + 15) / 16), cap)), dim3(256), 0, st, 0, 0, 0,
+                       (const int32_t*)counts, (const long long*)keep, (const long long*)fuse, (const long long*)fpix,
+                       (const long long*)app, si, g_i, x_i, rho_i, om_i, d_i, E_i, (const float*)nullptr, so);
+    hipLaunchKernelGGL(ptf_write_state_fused_kernel, dim3(std::min<unsigned>((unsigned)((nf_max + 63) / 64), cap)), dim3(256), 0, st, 0, 0,
+                       (const int32_t*)counts, (const long long*)fuse, (const long long*)fpix, si, x_i, rho_i, om_i, d_i, E_i, so);
     FS_CHECK_LAUNCH("ptf_write_state");
     return FS_OK;
 }
@@ -1047,23 +957,15 @@ FS_API int fs_ptf_write_state_backward(int32_t n_keep, int32_t n_fuse, int32_t n
     PtfState s{nullptr, const_cast<float*>(X), const_cast<float*>(R), nullptr, const_cast<float*>(E), const_cast<float*>(D)};
     PtfGrad go{g_out[0], g_out[1], g_out[2], g_out[3], g_out[4], g_out[5]};
     PtfGrad gs{g_in[0], g_in[1], g_in[2], g_in[3], g_in[4], g_in[5]};
-    // FS_PTF_WS_BWD_SPLIT=0: one launch, 16 lanes per row for every row (rounds 2 - 5; A/B)
-    static const bool split = [] { const char* e = getenv("FS_PTF_WS_BWD_SPLIT"); return !(e && atoi(e) == 0); }();
-    if (split) {
-        const long long n_ka = (long long)n_keep + n_app;
-        if (n_ka > 0)
-            hipLaunchKernelGGL(ptf_write_state_bwd_kernel<true>, dim3((unsigned)((n_ka + 63) / 64)), dim3(256), 0, st, n_keep, n_fuse,
-                               n_app, (const long long*)keep_idx, (const long long*)fuse_idx, (const long long*)fuse_pix,
-                               (const long long*)append_pix, s, x_i, rho_i, d_i, E_i, go, gs, g_lat_i, g_x_i, g_rho_i, g_om_i, g_d_i);
-        if (n_fuse > 0)
-            hipLaunchKernelGGL(ptf_write_state_bwd_fused_kernel, dim3((unsigned)((n_fuse + 63) / 64)), dim3(256), 0, st, n_keep, n_fuse,
-                               (const long long*)fuse_idx, (const long long*)fuse_pix, s, x_i, rho_i, d_i, E_i, go, gs, g_x_i, g_rho_i,
-                               g_om_i, g_d_i);
-    } else {
-        hipLaunchKernelGGL(ptf_write_state_bwd_kernel<false>, dim3((unsigned)((n_out + 15) / 16)), dim3(256), 0, st, n_keep, n_fuse,
+    const long long n_ka = (long long)n_keep + n_app;
+    if (n_ka > 0)
+        hipLaunchKernelGGL(ptf_write_state_bwd_kernel, dim3((unsigned)((n_ka + 63) / 64)), dim3(256), 0, st, n_keep, n_fuse,
                            n_app, (const long long*)keep_idx, (const long long*)fuse_idx, (const long long*)fuse_pix,
                            (const long long*)append_pix, s, x_i, rho_i, d_i, E_i, go, gs, g_lat_i, g_x_i, g_rho_i, g_om_i, g_d_i);
-    }
+    if (n_fuse > 0)
+        hipLaunchKernelGGL(ptf_write_state_bwd_fused_kernel, dim3((unsigned)((n_fuse + 63) / 64)), dim3(256), 0, st, n_keep, n_fuse,
+                           (const long long*)fuse_idx, (const long long*)fuse_pix, s, x_i, rho_i, d_i, E_i, go, gs, g_x_i, g_rho_i,
+                           g_om_i, g_d_i);
     FS_CHECK_LAUNCH("ptf_write_state_bwd");
     return FS_OK;
 }

@@ -11,8 +11,6 @@
 //   preprocess_bwd  1 thread / Gaussian: conic -> cov2D -> Sigma & view position, mean2D ->
 //                   mean through the perspective divide, RGB -> SH & view direction.
 //                   SH gradients leave through LDS so the [N, M, 3] rows are written coalesced.
-#include <cstdlib>
-
 #include "fs_common.h"
 
 namespace fs {
@@ -105,11 +103,7 @@ constexpr int kBwdQuads = 7;  // float4 per slot of two survivors
 // the (blue, depth) pair runs as scalar operations (packed fp32 has no throughput advantage on this chip, fs_common.h), and
 // the wavefront reduction carries 9 instead of 10 values per survivor.
 template <bool FAST_EXP, bool DEPTH>
-#ifdef FS_BWD_WAVES         // (A/B builds: make VARIANT=b8 EXTRA=-DFS_BWD_WAVES=8 forces <= 64 registers)
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FS_BWD_WAVES, FS_BWD_WAVES))) void render_bwd_kernel(
-#else
 __global__ __launch_bounds__(64) void render_bwd_kernel(
-#endif
     int H, int W, int T, const uint32_t* __restrict__ offsets,
     const uint32_t* __restrict__ point_list, const float4* __restrict__ rec,
     const float* __restrict__ bg, const uint32_t* __restrict__ counters, const float* __restrict__ final_T,
@@ -616,9 +610,7 @@ int launch_render_bwd(const fs_raster_dims& d, const float* bg, const void* geom
             hipLaunchKernelGGL(kernel, dim3(4 * nblk), dim3(64), 0, st, d.H, d.W, T, offsets, point_list, g.rec, bg, counters,
                                final_T, n_contrib, dL_dcolor, dL_ddepth, grad);
         };
-        // FS_RASTER_BWD_DEPTH=1 forces the depth-channel instantiation without a depth gradient (A/B runs)
-        static const bool force_depth = getenv("FS_RASTER_BWD_DEPTH") && atoi(getenv("FS_RASTER_BWD_DEPTH")) != 0;
-        const bool depth = dL_ddepth != nullptr || force_depth;
+        const bool depth = dL_ddepth != nullptr;
         if (d.flags & FS_RASTER_FAST_EXP) { if (depth) go(render_bwd_kernel<true, true>); else go(render_bwd_kernel<true, false>); }
         else { if (depth) go(render_bwd_kernel<false, true>); else go(render_bwd_kernel<false, false>); }
     }

@@ -10,8 +10,8 @@
 //                                       (depth_bits<<32 | id<<4 | quadrant mask) written there
 //   tile_scan    1 workgroup            exclusive scan of the T tile counts -> compact ranges of the saved lists,
 //                                       instance total, overflow flag
-//   sort_blend   1 workgroup / tile     LDS bucket sort of the tile's keys by depth (O(n); bitonic network for lists
-//                                       > 2048 keys and degenerate tiles) -> list words (id<<4 | mask) in (depth, id)
+//   sort_blend   1 workgroup / tile     LDS bucket sort of the tile's keys by depth (O(n); longer lists by depth groups,
+//                                       degenerate tiles by a bitonic network) -> list words (id<<4 | mask) in (depth, id)
 //                                       order, kept IN LDS (written to the saved list only when a backward follows);
 //                                       then each of the 4 wavefronts blends its own 8x8 QUADRANT front to back with no
 //                                       further barrier: survivors of 64 list entries compacted pairwise into
@@ -30,7 +30,6 @@
 //     super-tiles (neighbours share most of their Gaussians -> one L2) and super-tile s goes to XCD s % 8
 //     (fs_common.h:tile_for_block).
 #include <stdlib.h>
-#include <string.h>
 
 #include <type_traits>
 
@@ -107,7 +106,6 @@ __device__ __forceinline__ void stage_rows(float* lds, const float* __restrict__
 // ------------------------------------------------------------------------------------------
 // Tile binning helpers of the projection kernel's count and key-writing passes.
 // ------------------------------------------------------------------------------------------
-constexpr int kBinLds = 4096;  // tiles of a workgroup's bounding box whose counters live in LDS
 
 // Which 8x8-pixel quadrants of tile (tx,ty) can receive alpha >= 1/255 from this Gaussian?
 // bit q = (qy<<1)|qx.  Conservative (never drops a contributing quadrant): the maximum over the
@@ -246,47 +244,7 @@ __device__ __forceinline__ unsigned long long pack_quad_masks4(const QuadForm& f
     return m;
 }
 
-// Workgroup-private tile counters: the 256 Gaussians of a workgroup are neighbours on screen
-// (the encoder emits them in pixel order), so their tile rectangles span a small bounding box.
-// Counting happens with LDS atomics inside that box and only one global atomic per touched
-// tile and workgroup leaves the CU.  Falls back to direct global atomics when the box is larger
-// than kBinLds tiles.  Returns the box in bx0,by0,bw,bh (bw*bh == 0: nothing to bin).
-struct BinBox { int x0, y0, w, h; bool lds; };
-
-__device__ __forceinline__ BinBox block_bin_box(int* s_box, bool valid, ushort4 rc)
-{
-    // Bounds first inside each wavefront (shuffles; two 16-bit fields per exchange), then across the four
-    // wavefronts through 8 LDS words.  (256 threads doing atomicMin/atomicMax on the same four LDS words
-    // serialise completely: that version spent 9 of the workgroup's 25 us here.)
-    int x0 = valid ? (int)rc.x : 0x7fff, y0 = valid ? (int)rc.y : 0x7fff;
-    int x1 = valid ? (int)rc.z : 0, y1 = valid ? (int)rc.w : 0;
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const int lo = __shfl_xor((x0 << 16) | y0, m, 64), hi = __shfl_xor((x1 << 16) | y1, m, 64);
-        x0 = min(x0, lo >> 16); y0 = min(y0, lo & 0xffff);
-        x1 = max(x1, hi >> 16); y1 = max(y1, hi & 0xffff);
-    }
-    __syncthreads();  // (s_box may alias memory other threads are still reading)
-    if ((threadIdx.x & 63) == 0) {
-        s_box[2 * (threadIdx.x >> 6)] = (x0 << 16) | y0;
-        s_box[2 * (threadIdx.x >> 6) + 1] = (x1 << 16) | y1;
-    }
-    __syncthreads();
-    BinBox b;
-    b.x0 = 0x7fff; b.y0 = 0x7fff;
-    int bx1 = 0, by1 = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        const int lo = s_box[2 * w], hi = s_box[2 * w + 1];
-        b.x0 = min(b.x0, lo >> 16); b.y0 = min(b.y0, lo & 0xffff);
-        bx1 = max(bx1, hi >> 16); by1 = max(by1, hi & 0xffff);
-    }
-    b.w = max(0, bx1 - b.x0); b.h = max(0, by1 - b.y0);
-    b.lds = (b.w * b.h) <= kBinLds;
-    return b;
-}
-
-// same for fp16-stored rows (FS_RASTER_SH_FP16: storage-only half precision, fp32 math)
+// stage_rows for fp16-stored rows (FS_RASTER_SH_FP16: storage-only half precision, fp32 math)
 __device__ __forceinline__ void stage_rows_half(float* lds, const _Float16* __restrict__ src, size_t base, int cnt,
                                                 int per)
 {
@@ -667,135 +625,6 @@ __global__ __launch_bounds__(256) FS_PRE_OCC void preprocess_views_kernel(
     }
 }
 
-// The per-view projection + binning kernel of rounds 3 - 5 (one workgroup = 256 Gaussians, workgroup-wide binning with
-// four barriers): kept for same-session A/Bs against preprocess_views_kernel (FREESPLAT_PREPROCESS=legacy).
-__global__ __launch_bounds__(256) void preprocess_kernel(
-    fs_raster_dims d, const float* __restrict__ means3D, const float* __restrict__ cov3D,
-    const float* __restrict__ shs, const float* __restrict__ colors,
-    const float* __restrict__ opacities, const float* __restrict__ view,
-    const float* __restrict__ proj, const float* __restrict__ campos,
-    const float* __restrict__ tanfov_dev, const float* __restrict__ scale_dev, GeomView g,
-    int32_t* __restrict__ radii, uint32_t* __restrict__ tile_counts, unsigned long long* __restrict__ keys,
-    uint32_t tile_cap)
-{
-    const float tanfovx = tanfov_dev ? tanfov_dev[0] : d.tanfovx;
-    const float tanfovy = tanfov_dev ? tanfov_dev[1] : d.tanfovy;
-    const float wscale = scale_dev ? scale_dev[0] : 1.0f;  // scale-invariant rescale (1/near)
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    FS_PT(0, 0);
-    const int base = blockIdx.x * 256;
-    const int cnt = min(256, d.N - base);
-    const int per_sh = d.M * 3;
-    const bool sh_cm = (d.flags & FS_RASTER_SH_CHANNEL_MAJOR) != 0;
-    const int sh_cs = sh_cm ? d.M : 1, sh_ks = sh_cm ? 1 : 3;
-    float* l_sh = lds;                                   // [256 * per_sh]: the only rows wide enough to need staging
-    if (shs) {
-        if (d.flags & FS_RASTER_SH_FP16) stage_rows_half(l_sh, (const _Float16*)shs, base, cnt, per_sh);
-        else stage_rows(l_sh, shs, base, cnt, per_sh);
-    }
-    const int t = threadIdx.x;
-    const bool live = t < cnt;
-    const int i = base + t;
-    float3 p_in = make_float3(0.0f, 0.0f, 0.0f);
-    float c_in[6] = {0, 0, 0, 0, 0, 0};
-    float op = 0.0f;
-    if (live) {
-        load_mean_cov(d, means3D, cov3D, (size_t)i, p_in, c_in);
-        op = opacities[i];
-    }
-    __syncthreads();
-    FS_PT(0, 1);  // inputs staged
-    const Projected pr = project_gaussian(d, live, p_in, c_in, op, (size_t)i, colors, l_sh + (size_t)t * per_sh, sh_cs, sh_ks,
-                                          view, proj, campos, tanfovx, tanfovy, scale_dev != nullptr, wscale);
-    const float4 r0 = pr.r0, r1 = pr.r1, r2 = pr.r2;
-    const ushort4 rect = pr.rect;
-    const uint8_t cb = pr.cb;
-    const int rad = pr.rad;
-    FS_PT(0, 2);  // projected
-    if (live) {
-        g.rec[3 * (size_t)i + 0] = r0;
-        g.rec[3 * (size_t)i + 1] = r1;
-        g.rec[3 * (size_t)i + 2] = r2;
-        g.rect[i] = rect;
-        g.clamp[i] = cb;
-        radii[i] = rad;
-    }
-
-    // ---- binning (the staging LDS is dead from here on): count per tile in LDS, reserve, write the keys ----
-    __syncthreads();
-    FS_PT(0, 3);  // records written
-    int* s_box = (int*)lds;
-    uint32_t* s_cnt = (uint32_t*)lds + 16;   // per tile of the workgroup's box: instance count, then the next free slot
-    const bool valid = rad > 0;
-    const bool cull = (d.flags & FS_RASTER_TILE_CULL) != 0;
-    const int gx = (d.W + kTile - 1) / kTile;
-    const QuadForm qf = quad_form(r0, r1);
-    const int area = (rect.z - rect.x) * (rect.w - rect.y);
-    const bool small = area <= 16;
-    unsigned long long qm = 0;
-    if (valid && small) qm = pack_quad_masks(qf, r0, rect);
-    // key = depth bits : (gaussian id << 4 | quadrant mask); the mask is a function of (id, tile), so
-    // ordering by the key is ordering by (depth, id)
-    const unsigned long long key_hi = ((unsigned long long)__float_as_uint(r1.w) << 32) | ((uint32_t)i << 4);
-    FS_PT(0, 4);  // quadrant masks
-    const BinBox bb = block_bin_box(s_box, valid, rect);
-    FS_PT(0, 5);  // workgroup box
-    if (bb.w * bb.h == 0) return;
-    if (bb.lds) {
-        for (int k = t; k < bb.w * bb.h; k += 256) s_cnt[k] = 0;
-        __syncthreads();
-        if (valid) {
-            int k = 0;
-            for (int y = rect.y; y < rect.w; ++y) {
-                RowBands rb = {};
-                if (!small) rb = row_bands(qf, r0, y);
-                for (int x = rect.x; x < rect.z; ++x, ++k) {
-                    const uint32_t m = small ? (uint32_t)(qm >> (4 * k)) & 15u : quad_mask_row(rb, r0, x);
-                    if (!cull || m) atomicAdd(&s_cnt[(y - bb.y0) * bb.w + (x - bb.x0)], 1u);
-                }
-            }
-        }
-        __syncthreads();
-        FS_PT(0, 6);  // counted
-        for (int k = t; k < bb.w * bb.h; k += 256) {
-            const uint32_t c = s_cnt[k];
-            // first slot of this workgroup in the tile's key area (one returning global atomic per touched tile)
-            s_cnt[k] = c ? atomicAdd(&tile_counts[(bb.y0 + k / bb.w) * gx + bb.x0 + k % bb.w], c) : 0u;
-        }
-        __syncthreads();
-        FS_PT(0, 7);  // slots reserved
-        if (valid) {
-            int k = 0;
-            for (int y = rect.y; y < rect.w; ++y) {
-                RowBands rb = {};
-                if (!small) rb = row_bands(qf, r0, y);
-                for (int x = rect.x; x < rect.z; ++x, ++k) {
-                    const uint32_t m = small ? (uint32_t)(qm >> (4 * k)) & 15u : quad_mask_row(rb, r0, x);
-                    if (!cull || m) {
-                        const uint32_t slot = atomicAdd(&s_cnt[(y - bb.y0) * bb.w + (x - bb.x0)], 1u);
-                        // (tile * tile_cap + slot < 2^32: tile_capacity() bounds the product)
-                        if (slot < tile_cap) keys[(uint32_t)(y * gx + x) * tile_cap + slot] = key_hi | m;
-                    }
-                }
-            }
-        }
-        FS_PT(0, 8);  // keys written
-    } else if (valid) {
-        int k = 0;
-        for (int y = rect.y; y < rect.w; ++y) {
-            RowBands rb = {};
-            if (!small) rb = row_bands(qf, r0, y);
-            for (int x = rect.x; x < rect.z; ++x, ++k) {
-                const uint32_t m = small ? (uint32_t)(qm >> (4 * k)) & 15u : quad_mask_row(rb, r0, x);
-                if (!cull || m) {
-                    const uint32_t slot = atomicAdd(&tile_counts[y * gx + x], 1u);
-                    if (slot < tile_cap) keys[(uint32_t)(y * gx + x) * tile_cap + slot] = key_hi | m;
-                }
-            }
-        }
-    }
-}
-
 // ------------------------------------------------------------------------------------------
 // tile_scan: exclusive scan over T tile counts (T ~ 5e3; one workgroup of 1024 per view: workgroup b scans view b's
 // counters at counts0 + b * counts_stride bytes into offsets0 + b * offsets_stride bytes and counters0 + 2 b)
@@ -899,7 +728,7 @@ __device__ __forceinline__ void bitonic_sort_any(Ptr a, uint32_t n)
 }
 
 // ------------------------------------------------------------------------------------------
-// Register-resident bitonic sort for tile lists of <= 4096 keys: thread t of the 256 holds the EPT
+// Register-resident bitonic network (the bucket sort's fallback for degenerate tiles): thread t of the 256 holds the EPT
 // consecutive keys [t*EPT, (t+1)*EPT).  Strides below EPT are compare-exchanges between a thread's
 // own registers; strides that stay inside a wavefront (partner thread = t ^ m, m < 64) move through
 // DPP / ds_swizzle / ds_bpermute, i.e. without LDS round trips or barriers; only the last stages'
@@ -974,82 +803,6 @@ struct Stages {
         if constexpr (K >= 4) Clean<EPT, K / 4>::run(k, t, lds);
     }
 };
-
-template <int EPT>
-__device__ __forceinline__ void sort_tile_in_registers(const unsigned long long* __restrict__ keys,
-                                                       uint32_t* __restrict__ out, uint32_t n,
-                                                       unsigned long long* lds)
-{
-    const int t = threadIdx.x;
-    unsigned long long k[EPT];
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) {
-        const uint32_t i = (uint32_t)t * EPT + e;
-        k[e] = i < n ? keys[i] : ~0ull;
-    }
-    Stages<EPT, 256 * EPT>::run(k, t, lds);
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) {
-        const uint32_t i = (uint32_t)t * EPT + e;
-        if (i < n) out[i] = (uint32_t)k[e];
-    }
-}
-
-// Lists a little longer than a power of two (the common case: C3 averages 1156 keys per tile) would pay the
-// whole next network for mostly padding.  Two-run form: the first 256*EA keys and the remaining <= 256*EB keys
-// (EB < EA) are sorted by their own, smaller networks, laid out back to back through LDS, and merged by the last
-// stage of the 512*EA network alone (one flip + its half-cleaners).  In steps x keys-per-thread this is
-// 55*4 + 36*1 + 11*8 = 344 instead of 66*8 = 528 for 1024 < n <= 1280.
-template <int EA, int EB>
-__device__ __forceinline__ void sort_tile_two_runs(const unsigned long long* __restrict__ keys,
-                                                   uint32_t* __restrict__ out, uint32_t n, unsigned long long* lds)
-{
-    static_assert(EB < EA, "second run must be the shorter one");
-    constexpr int E = 2 * EA, NA = 256 * EA, NB = 256 * EB;
-    const int t = threadIdx.x;
-    unsigned long long ka[EA], kb[EB];
-#pragma unroll
-    for (int e = 0; e < EA; ++e) ka[e] = keys[t * EA + e];  // n > NA
-#pragma unroll
-    for (int e = 0; e < EB; ++e) {
-        const uint32_t i = (uint32_t)(NA + t * EB + e);
-        kb[e] = i < n ? keys[i] : ~0ull;
-    }
-    Stages<EA, NA>::run(ka, t, lds);
-    Stages<EB, NB>::run(kb, t, lds);
-    unsigned long long k[E];
-#pragma unroll
-    for (int c0 = 0; c0 < NA + NB; c0 += kSortLds) {  // through the exchange buffer, kSortLds keys at a time
-        __syncthreads();
-#pragma unroll
-        for (int e = 0; e < EA; ++e) {
-            const int i = t * EA + e - c0;
-            if (i >= 0 && i < kSortLds) lds[i] = ka[e];
-        }
-#pragma unroll
-        for (int e = 0; e < EB; ++e) {
-            const int i = NA + t * EB + e - c0;
-            if (i >= 0 && i < kSortLds) lds[i] = kb[e];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            const int i = t * E + e - c0;
-            if (i >= 0 && i < kSortLds && i + c0 < NA + NB) k[e] = lds[i];
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < E; ++e)
-        if (t * E + e >= NA + NB) k[e] = ~0ull;
-    thread_exchange<E, 255, true>(k, t, lds);  // flip step of the last stage: i <-> i ^ (512*EA - 1)
-    Clean<E, 256 * E / 4>::run(k, t, lds);
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        const uint32_t i = (uint32_t)t * E + e;
-        if (i < n) out[i] = (uint32_t)k[e];
-    }
-}
-
 
 // ------------------------------------------------------------------------------------------
 // Bucket sort of one tile's keys in LDS (lists of <= 2048 keys: every tile of the BASELINE configs).
@@ -1543,15 +1296,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FS_BLEND_WA
     } else if (n <= (uint32_t)kSortLds) {
         sort_tile_buckets<kSortLds / 256>(kt, TRACK ? gl : nullptr, n, sk, s_cnt, s_red);
     }
-#ifdef FS_LONG_SORT_NETWORKS   // (rounds 1 - 4: register bitonic networks up to 4096 keys, the global-memory network beyond; A/B builds)
-    else if (n <= 2560u) {
-        sort_tile_two_runs<8, 2>(kt, gl, n, sk);
-    } else if (n <= 3072u) {
-        sort_tile_two_runs<8, 4>(kt, gl, n, sk);
-    } else if (n <= 4096u) {
-        sort_tile_in_registers<16>(kt, gl, n, sk);
-    }
-#endif
     else if (!sort_tile_partitioned(kt, gl, n, sk, s_cnt, s_red, s_grp)) {
         // degenerate (thousands of identical depths in one tile): in place in global memory, the plain network
         __syncthreads();
@@ -1608,12 +1352,6 @@ FS_API const int32_t* fs_raster_n_contrib(const void* image, int32_t H, int32_t 
 }
 
 namespace fs {
-// FREESPLAT_PREPROCESS=legacy: the per-view projection kernel of rounds 3 - 5 (same-session A/Bs)
-static bool legacy_preprocess()
-{
-    static const bool on = [] { const char* e = getenv("FREESPLAT_PREPROCESS"); return e && strcmp(e, "legacy") == 0; }();
-    return on;
-}
 constexpr int kMaxViewsInFlight = 16;   // key areas (scratch slots) a multi-view call may use at once
 // FREESPLAT_RASTER_BATCH: views per projection launch of a multi-view call (default 16 = all views of a call in flight).  The blends of one batch run on the
 // side streams while the projection of the next batch runs on the main stream.
@@ -1684,7 +1422,7 @@ static int launch_binning(const fs_raster_dims& d, int nv, const float* means3D,
     return FS_OK;
 }
 
-// Sort + blend of ONE view whose keys are binned (launch_binning, or the legacy projection kernel).
+// Sort + blend of ONE view whose keys are binned (launch_binning).
 static int launch_blend(const fs_raster_dims& d, const float* bg, void* geom, void* binning, void* image, void* scratch,
                         int64_t cap, float* out_color, float* out_depth, float* out_alpha, const uint32_t* counters,
                         hipStream_t st)
@@ -1715,42 +1453,6 @@ static int launch_blend(const fs_raster_dims& d, const float* bg, void* geom, vo
     return FS_OK;
 }
 
-// rounds 3 - 5: projection + binning of one view by the per-view kernel, its own memset and single-workgroup scan
-static int launch_binning_legacy(const fs_raster_dims& d, const float* means3D, const float* cov3D, const float* shs,
-                                 const float* colors_precomp, const float* opacities, const float* viewmatrix,
-                                 const float* projmatrix, const float* campos, const float* tanfov_dev, const float* scale_dev,
-                                 void* geom, void* binning, void* scratch, int64_t cap, int32_t* radii, uint32_t* counters,
-                                 hipStream_t st)
-{
-    const int T = num_tiles(d.H, d.W);
-    GeomView g = geom_view(geom, d.N > 0 ? d.N : 1);
-    uint32_t* counts = (uint32_t*)scratch;
-    unsigned long long* keys = (unsigned long long*)((char*)scratch + align_up((size_t)T * 4, 256));
-    const uint32_t tile_cap = tile_capacity(cap, T);
-    if (hipMemsetAsync(counts, 0, (size_t)T * 4, st) != hipSuccess) {
-        set_last_error("memset tile counts", hipGetLastError());
-        return FS_ERR_LAUNCH;
-    }
-    const int M = shs ? d.M : 0;
-    if (d.N > 0) {
-        size_t lds = (size_t)(256 * M * 3) * sizeof(float);
-        if (lds < (size_t)(16 + kBinLds) * 4) lds = (size_t)(16 + kBinLds) * 4;
-        {
-            ScopedStage prof_(kStPreprocess, st);
-            hipLaunchKernelGGL(preprocess_kernel, dim3((d.N + 255) / 256), dim3(256), lds, st, d, means3D,
-                               cov3D, shs, colors_precomp, opacities, viewmatrix, projmatrix, campos,
-                               tanfov_dev, scale_dev, g, radii, counts, keys, tile_cap);
-        }
-        FS_CHECK_LAUNCH("preprocess");
-    }
-    {
-        ScopedStage prof_(kStTileScan, st);
-        hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, st, (const char*)counts, (size_t)0, (char*)binning,
-                           (size_t)0, T, counters, (unsigned long long)cap, tile_cap);
-    }
-    FS_CHECK_LAUNCH("tile_scan");
-    return FS_OK;
-}
 }  // namespace fs
 
 FS_API int fs_raster_forward(const fs_raster_dims* dims, const float* means3D, const float* cov3D,
@@ -1767,12 +1469,8 @@ FS_API int fs_raster_forward(const fs_raster_dims* dims, const float* means3D, c
     int rc = check_forward_args(d, means3D, cov3D, shs, colors_precomp, opacities, radii, cap);
     if (rc != FS_OK) return rc;
     hipStream_t st = (hipStream_t)stream_;
-    if (legacy_preprocess())
-        rc = launch_binning_legacy(d, means3D, cov3D, shs, colors_precomp, opacities, viewmatrix, projmatrix, campos,
-                                   tanfov_dev, scale_dev, geom, binning, scratch, cap, radii, counters, st);
-    else
-        rc = launch_binning(d, 1, means3D, cov3D, shs, colors_precomp, opacities, viewmatrix, projmatrix, campos, tanfov_dev,
-                            scale_dev, geom, 0, binning, 0, scratch, 0, cap, radii, counters, st);
+    rc = launch_binning(d, 1, means3D, cov3D, shs, colors_precomp, opacities, viewmatrix, projmatrix, campos, tanfov_dev,
+                        scale_dev, geom, 0, binning, 0, scratch, 0, cap, radii, counters, st);
     if (rc != FS_OK) return rc;
     return launch_blend(d, bg, geom, binning, image, scratch, cap, out_color, out_depth, out_alpha, counters, st);
 }
@@ -1795,7 +1493,6 @@ struct ForkJoin {  // cached events: fork `main` into the side streams, join the
 FS_API int fs_raster_scratch_slots(int32_t v, int32_t n_streams)
 {
     if (v < 0 || n_streams < 0) return FS_ERR_INVALID_ARG;
-    if (fs::legacy_preprocess()) return n_streams > 1 ? (n_streams < v ? n_streams : (v > 0 ? v : 1)) : 1;
     return v < 1 ? 1 : (v < fs::kMaxViewsInFlight ? v : fs::kMaxViewsInFlight);
 }
 
@@ -1826,7 +1523,6 @@ FS_API int fs_raster_forward_views(const fs_raster_dims* dims, int32_t v, const 
     hipStream_t main = (hipStream_t)main_stream;
     if (ns > 0 && !fj.ok) { set_last_error("event create", hipGetLastError()); return FS_ERR_LAUNCH; }
     const size_t P = (size_t)d.H * d.W;
-    const bool legacy = fs::legacy_preprocess();
     auto join = [&]() -> int {   // main waits for everything queued on the side streams
         for (int s = 0; s < ns; ++s)
             if (hipEventRecord(fj.done[s], (hipStream_t)streams[s]) != hipSuccess ||
@@ -1841,29 +1537,6 @@ FS_API int fs_raster_forward_views(const fs_raster_dims* dims, int32_t v, const 
                                 (char*)image + strides[2] * i, scratch_i, cap, out_color + 3 * P * i, out_depth + P * i,
                                 out_alpha + P * i, counters + 2 * (size_t)i, st);
     };
-    if (legacy) {   // rounds 3 - 5: whole views alternate over the streams, one key area per stream
-        if (ns > 0) {
-            if (hipEventRecord(fj.ready, main) != hipSuccess) { set_last_error("event record", hipGetLastError()); return FS_ERR_LAUNCH; }
-            for (int s = 0; s < ns; ++s)
-                if (hipStreamWaitEvent((hipStream_t)streams[s], fj.ready, 0) != hipSuccess) {
-                    set_last_error("stream wait", hipGetLastError());
-                    return FS_ERR_LAUNCH;
-                }
-        }
-        for (int i = 0; i < v && rc == FS_OK; ++i) {
-            const int s = ns > 0 ? i % ns : 0;
-            hipStream_t st = ns > 0 ? (hipStream_t)streams[s] : main;
-            void* scratch_i = (char*)scratch + strides[3] * s;
-            rc = fs::launch_binning_legacy(d, means3D, cov3D, shs, colors_precomp, opacities, viewmatrix + 16 * (size_t)i,
-                                           projmatrix + 16 * (size_t)i, campos + 3 * (size_t)i,
-                                           tanfov ? tanfov + 2 * (size_t)i : nullptr, scale ? scale + i : nullptr,
-                                           (char*)geom + strides[0] * i, (char*)binning + strides[1] * i, scratch_i, cap,
-                                           radii ? radii + (size_t)d.N * i : nullptr, counters + 2 * (size_t)i, st);
-            if (rc == FS_OK) rc = blend(i, scratch_i, st);
-        }
-        const int jr = join();   // join even after a failed launch: never leave `main` unordered
-        return rc != FS_OK ? rc : jr;
-    }
     // One projection launch set per BATCH of views on `main`, the blends of the batch fan out over the side streams; `main`
     // goes straight on to the next batch's projection, which overlaps those blends.  View i's key area is scratch slot
     // i % kMaxViewsInFlight: after kMaxViewsInFlight views the streams are joined before the slots are reused.

@@ -128,106 +128,21 @@ LAST_FOLD_COUNTS = None   # device tensor [V,4] (kept, fused, appended, state ro
 
 
 def gru_tables(gru: "GRU") -> Tensor:
-    """The GRU's weights and biases as MFMA operands of csrc/ptf_gru.hip: rows of 64 lanes, lane l = (p = l & 31,
-    hf = l >> 5), one row per MFMA in the order the kernel consumes them, then the bias rows.  Cached per parameter
-    version."""
+    """The GRU's weights and biases as MFMA operands of csrc/ptf_gru.hip:ptf_gru16_kernel (fs_ptf_gru_table_layout() = 1): the
+    forward's operand rows of _gru_stream16_index, then the six bias vectors.  Cached per parameter version."""
     params = _gru_params(gru)
     key = tuple((q.data_ptr(), q._version) for q in params)
     hit = _table_cache.get(gru)
     if hit is not None and hit[0] == key:
         return hit[1]
-    dev = params[0].device
-    if _lib.lib().fs_ptf_gru_table_layout() == 1:          # the 16-pair forward kernel's tables
-        tab = _gru_operand_stream16(gru, forward_only=True)
-        assert tab.shape[0] == _lib.lib().fs_ptf_gru_table_rows()
-        _table_cache[gru] = (key, tab)
-        return tab
-    with torch.no_grad():
-        Wr1, br1, Wr2, br2, Wz1, bz1, Wz2, bz2, Wn1, bn1, Wn2, bn2 = [q.detach().float() for q in params]
-        lane = torch.arange(64, device=dev)
-        pp, hf = lane & 31, lane >> 5
-        acc_row = lambda q, h: (q & 3) + 8 * (q >> 2) + 4 * h
-        unit = lambda s: acc_row(s[:, None] & 15, hf[None, :]) + 32 * (s[:, None] >> 4)      # [steps, 64]
-
-        def l1(W):   # [64,176]: step s <-> input s + 88*hf
-            s = torch.arange(88, device=dev)
-            col = s[:, None] + 88 * hf[None, :]
-            return torch.stack([W[32 * b + pp[None, :].expand_as(col), col] for b in range(2)])
-
-        def l2(W):   # [64,64]: step s <-> hidden unit of accumulator register s & 15, block s >> 4
-            col = unit(torch.arange(32, device=dev))
-            return torch.stack([W[32 * b + pp[None, :].expand_as(col), col] for b in range(2)])
-
-        def n1(W):   # [64,152]: steps 0..31 <-> r*hid units, 32..75 <-> x|xe input 64 + (s-32) + 44*hf
-            s = torch.arange(44, device=dev)
-            col = torch.cat([unit(torch.arange(32, device=dev)), 64 + s[:, None] + 44 * hf[None, :]])
-            return torch.stack([W[32 * b + pp[None, :].expand_as(col), col] for b in range(2)])
-
-        def bias(bv):  # [64] -> [2,16,64]
-            q = torch.arange(16, device=dev)
-            return torch.stack([bv[acc_row(q[:, None], hf[None, :]) + 32 * b] for b in range(2)])
-
-        # one row per MFMA, in the order ptf_gru_kernel consumes them (the workgroup streams them through LDS once for
-        # its four wavefronts): per k-step the row blocks of the matrices that share the step's B operand
-        r1, z1, r2, z2, nn1, nn2 = l1(Wr1), l1(Wz1), l2(Wr2), l2(Wz2), n1(Wn1), l2(Wn2)       # [2 blocks, steps, 64]
-        il = lambda *ms: torch.stack([m[b] for m in ms for b in range(2)], dim=1).reshape(-1, 64)   # [steps * 2 * len(ms), 64]
-        ops = torch.cat([il(r1, z1), il(r2, z2), il(nn1), il(nn2)])
-        rows_b = _lib.lib().fs_ptf_gru_table_rows() - 6 * 32
-        assert ops.shape[0] == 696 <= rows_b
-        tab = torch.cat([ops, ops.new_zeros(rows_b - ops.shape[0], 64)] +
-                        [bias(bv).reshape(-1, 64) for bv in (br1, bz1, br2, bz2, bn1, bn2)]).contiguous()
+    assert _lib.lib().fs_ptf_gru_table_layout() == 1
+    tab = _gru_operand_stream16(gru, forward_only=True)
     assert tab.shape[0] == _lib.lib().fs_ptf_gru_table_rows()
     _table_cache[gru] = (key, tab)
     return tab
 
 
-_table_t_cache: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
-
-
-def gru_tables_t(gru: "GRU") -> Tensor:
-    """The GRU's six weight matrices TRANSPOSED, in the MFMA operand order of csrc/ptf_gru.hip:ptf_gru_bwd_kernel:
-    row (rb, s) of a matrix, lane l = (p = l & 31, hf = l >> 5), holds W[u(s, hf)][32 rb + p] -- u = the forward's
-    accumulator unit map -- and 0 where 32 rb + p is not an input of that matrix.  mlp_n's first layer appears twice:
-    its r*hid columns as two row blocks of their own, its x | xe columns placed at their positions among the 176
-    features of the concatenated row (blocks 2..5), so that they accumulate straight into dcat.  Cached per parameter
-    version."""
-    params = _gru_params(gru)
-    key = tuple((q.data_ptr(), q._version) for q in params)
-    hit = _table_t_cache.get(gru)
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    dev = params[0].device
-    with torch.no_grad():
-        Wr1, _, Wr2, _, Wz1, _, Wz2, _, Wn1, _, Wn2, _ = [q.detach().float() for q in params]
-        lane = torch.arange(64, device=dev)
-        pp, hf = lane & 31, lane >> 5
-        s = torch.arange(32, device=dev)
-        unit = ((s[:, None] & 15) & 3) + 8 * ((s[:, None] & 15) >> 2) + 4 * hf[None, :] + 32 * (s[:, None] >> 4)   # [32, 64]
-
-        def tr(W, blocks, col_of_feature=None):
-            """[blocks*32 rows, 64 lanes]: W[unit(s, hf), col(32 rb + p)], zero where the column does not exist."""
-            out = []
-            Wp = torch.cat([W, torch.zeros(W.shape[0], 1, device=dev)], dim=1)       # last column = 0 (the "no input" slot)
-            for rb in blocks:
-                f = 32 * rb + pp                                                     # feature of this lane's row
-                col = f if col_of_feature is None else col_of_feature(f)
-                col = torch.where((col >= 0) & (col < W.shape[1]), col, torch.full_like(col, W.shape[1]))
-                out.append(Wp[unit, col[None, :].expand_as(unit)])
-            return torch.cat(out)
-
-        n1_from_cat = lambda f: torch.where(f >= 88, f - 24, torch.full_like(f, -1))   # cat feature -> mlp_n input (x | xe)
-        tab = torch.cat([tr(Wn2, range(2)), tr(Wn1, range(2)), tr(Wn1, range(2, 6), n1_from_cat), tr(Wr2, range(2)),
-                         tr(Wz2, range(2)), tr(Wr1, range(6)), tr(Wz1, range(6))]).contiguous()
-    assert tab.shape == (_lib.lib().fs_ptf_gru_table_t_rows(), 64)
-    _table_t_cache[gru] = (key, tab)
-    return tab
-
-
-# first rows of the matrices in the transposed operand table (csrc/ptf_gru.hip)
-_KTN2, _KTN1H, _KTN1C, _KTR2, _KTZ2, _KTR1, _KTZ1 = 0, 64, 128, 256, 320, 384, 576
 _stream_cache: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
-
-
 _stream16_index_cache: dict = {}
 
 
@@ -318,43 +233,15 @@ def _gru_operand_stream16(gru: "GRU", forward_only: bool = False, transposed_onl
 
 
 def gru_operand_stream(gru: "GRU") -> Tensor:
-    """The operand rows of ptf_gru_bwd_kernel in the order in which it consumes them: the 696 rows of the forward
-    (gru_tables, already in consumption order), then the transposed layers' rows (gru_tables_t) -- mlp_n second layer,
-    mlp_n first layer, r/z second layers, r/z first layers --, padded to whole LDS chunks."""
-    if _lib.lib().fs_ptf_gru_stream_layout() == 2:          # the 16-pair backward kernel's stream (built from the parameters)
-        tab = gru_tables(gru)                               # (cached per parameter version: a new table = new parameters)
-        hit = _stream_cache.get(gru)
-        if hit is not None and hit[0] is tab:
-            return hit[2]
-        stream = _gru_operand_stream16(gru)
-        _stream_cache[gru] = (tab, None, stream)
-        return stream
-    tab, tab_t = gru_tables(gru), gru_tables_t(gru)
+    """The operand stream of csrc/ptf_gru.hip:ptf_gru_bwd16_kernel (fs_ptf_gru_stream_layout() = 2), built from the parameters:
+    the 696 rows of the forward (re-run), then the transposed layers' rows, then the six bias vectors."""
+    assert _lib.lib().fs_ptf_gru_stream_layout() == 2
+    tab = gru_tables(gru)                                   # (cached per parameter version: a new table = new parameters)
     hit = _stream_cache.get(gru)
-    if hit is not None and hit[0] is tab and hit[1] is tab_t:
-        return hit[2]
-    o = []
-    for s in range(32):
-        o += [_KTN2 + s, _KTN2 + 32 + s]
-    for s in range(32):
-        o += [_KTN1H + s, _KTN1H + 32 + s] + [_KTN1C + 32 * j + s for j in range(4)]
-    for s in range(32):
-        o += [_KTR2 + s, _KTR2 + 32 + s, _KTZ2 + s, _KTZ2 + 32 + s]
-    for s in range(32):
-        for rb in range(6):
-            o += [_KTR1 + 32 * rb + s, _KTZ1 + 32 * rb + s]
-    rows = _lib.lib().fs_ptf_gru_stream_rows()
-    assert 696 + len(o) == 1464 <= rows
-    stream = tab.new_zeros(rows, 64)
-    stream[:696] = tab[:696]
-    stream[696: 1464] = tab_t[torch.tensor(o, device=tab.device)]
-    if _lib.lib().fs_ptf_gru_stream_layout() == 1:
-        # interleaved by quads of rows (include/freesplat_amd.h): [chunk][owner wavefront][quad][lane][row of the quad] -- a lane's
-        # four consecutive operand rows are one float4 in memory and in the kernel's LDS ring
-        c = _lib.lib().fs_ptf_gru_stream_chunk_rows()
-        assert rows % c == 0 and c % 16 == 0
-        stream = stream.view(rows // c, 4, c // 16, 4, 64).permute(0, 1, 2, 4, 3).contiguous().view(rows, 64)
-    _stream_cache[gru] = (tab, tab_t, stream)
+    if hit is not None and hit[0] is tab:
+        return hit[1]
+    stream = _gru_operand_stream16(gru)
+    _stream_cache[gru] = (tab, stream)
     return stream
 
 
@@ -366,10 +253,7 @@ def save_gru_activations(V: int = 2, P: int = 0, device=None) -> bool:
     backward runs the transposed layers only (fs_ptf_gru_backward_saved: 704 instead of 1 400 MFMAs per 16 pairs) -- 4 KB per
     possible fused pair and step held until the backward: (V - 1) * P * 4 KB, 10 GB for config 3's three views at 968x1296.
     FREESPLAT_GRU_SAVE=1 / 0 forces it on / off (A/B); otherwise it is on when that fits a quarter of the memory currently free
-    on the device (a 288 GB MI355X: always; a small card falls back to the re-running backward instead of running out of memory).
-    Unavailable with the 32-pair kernels."""
-    if _lib.lib().fs_ptf_gru_stream_t_rows() <= 0:
-        return False
+    on the device (a 288 GB MI355X: always; a small card falls back to the re-running backward instead of running out of memory)."""
     e = os.environ.get("FREESPLAT_GRU_SAVE")
     if e is not None:
         return e != "0"

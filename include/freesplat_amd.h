@@ -156,8 +156,7 @@ int fs_raster_scratch_slots(int32_t v, int32_t n_streams);
  * n_streams > 1: the projection launch sets run on main_stream, the blend of view i on streams[i % n_streams], ordered after
  * its batch's projection by an event -- so the next batch's projection overlaps the blends of this one; main_stream is ordered
  * after all of them before the call returns (fork / join with events, no host sync), so to the caller the call is
- * stream-ordered on main_stream like every other entry point.  n_streams <= 1: everything on main_stream.
- * (FREESPLAT_PREPROCESS=legacy in the environment selects the per-view projection kernel of revisions <= 5 for A/B runs.) */
+ * stream-ordered on main_stream like every other entry point.  n_streams <= 1: everything on main_stream. */
 int fs_raster_forward_views(const fs_raster_dims* dims, int32_t v, const float* means3D, const float* cov3D,
                             const float* shs, const float* colors_precomp, const float* opacities,
                             const float* bg, const float* viewmatrix, const float* projmatrix,
@@ -372,18 +371,19 @@ int fs_ptf_fold(int32_t V, int32_t h, int32_t w, const float* lat, const float* 
  * operand order, fs_ptf_gru_table_rows() rows of 64 floats (layout: csrc/ptf_gru.hip; builder:
  * freesplat_amd/ptf.py:gru_tables). */
 int32_t fs_ptf_gru_table_rows(void);
-/* Layout of `tables` (ABI 6): 0 = the 32-pair kernels' (operand rows of the forward in consumption order, then 192 bias rows); 1 = the
- * 16-pair forward kernel's (the default; FS_GRU_FWD16=0 or FS_GRU_BWD16=0 selects 0): its 696 operand rows of v_mfma_f32_16x16x4_f32
- * padded to whole chunks and interleaved by quads as operand-stream layout 2, then six rows = the bias vectors. */
+/* Layout of `tables` (ABI 6): always 1 = the 16-pair forward kernel's: its 696 operand rows of v_mfma_f32_16x16x4_f32 padded to
+ * whole chunks and interleaved by quads as operand-stream layout 2, then six rows = the bias vectors.  (0 = the 32-pair kernels'
+ * tables of revisions <= 5.) */
 int32_t fs_ptf_gru_table_layout(void);
 int fs_ptf_gru_forward(int32_t n, const float* cat, const float* tables, float* fused, void* stream);
 
 /* Backward of the GRU on the fp32 matrix cores (autograd of networks.py:201-214 w.r.t. its input rows): the forward
  * is re-run from cat[n,176], then every linear layer runs transposed (dX^T = W^T dY^T).  `operand_stream` =
- * fs_ptf_gru_stream_rows() rows of 64 floats: the forward's operand rows (`tables`) followed by the rows of the six
- * transposed matrices (fs_ptf_gru_table_t_rows() of them), re-ordered into the order in which the kernel consumes
- * them -- the workgroup streams them through LDS once for its four wavefronts (layout: csrc/ptf_gru.hip; builders:
- * freesplat_amd/ptf.py:gru_tables_t, gru_operand_stream).  `tables` supplies the biases.
+ * fs_ptf_gru_stream_rows() rows of 64 floats: the forward's operand rows followed by the rows of the six transposed
+ * matrices, in the order in which the kernel consumes them -- the workgroup streams them through LDS once for its four
+ * wavefronts -- then the biases (layout: fs_ptf_gru_stream_layout(); builder: freesplat_amd/ptf.py:gru_operand_stream).
+ * `tables` (non-NULL) is not read, it stays in the signature for ABI 6; fs_ptf_gru_table_t_rows() reports the 768 rows of the
+ * transposed table of revisions <= 5, which nothing reads.
  * g_fused[n,64] = gradient of the GRU output -> dcat[n,176] = gradient of the input rows (fed to
  * fs_ptf_gru_inputs_backward), and side[n, fs_ptf_gru_side_cols()] =
  *   [dr1 | dz1 | dR | dZ | dn1 | dN | relu(r1) | relu(z1) | relu(n1) | r*hid]   (64 floats each)
@@ -396,13 +396,12 @@ int fs_ptf_gru_forward(int32_t n, const float* cat, const float* tables, float* 
  * sums, reduced by a second launch). */
 int32_t fs_ptf_gru_table_t_rows(void);
 int32_t fs_ptf_gru_stream_rows(void);
-/* Memory layout of `operand_stream` (ABI 6): 0 = row r is 64 consecutive floats; 1 = interleaved by quads of rows -- with
+/* Memory layout of `operand_stream` (ABI 6): always 2 = the stream of the 16-pair backward kernel: 1 400 operand rows of
+ * v_mfma_f32_16x16x4_f32 in consumption order, padded to whole chunks and interleaved by quads of rows -- with
  * c = fs_ptf_gru_stream_chunk_rows() rows per LDS chunk, element [chunk][owner wavefront (4)][quad (c/16)][lane (64)][row of the
  * quad (4)] holds row chunk*c + wavefront*(c/4) + 4*quad + row, lane `lane`, so that a lane's four consecutive operand rows are one
- * float4 (one ds_read_b128 per four MFMAs); 2 = the stream of the 16-pair backward kernel (the default; FS_GRU_BWD16=0 in the
- * environment selects the 32-pair kernel and layout 1): 1 400 operand rows of v_mfma_f32_16x16x4_f32 in consumption order, padded to whole
- * chunks and interleaved as in layout 1, followed by six rows = the bias vectors br1, bz1, br2, bz2, bn1, bn2.
- * freesplat_amd/ptf.py:gru_operand_stream builds what the library reports. */
+ * float4 (one ds_read_b128 per four MFMAs) --, followed by six rows = the bias vectors br1, bz1, br2, bz2, bn1, bn2.
+ * (0 / 1 = the 32-pair kernel's streams of revisions <= 5.)  freesplat_amd/ptf.py:gru_operand_stream builds it. */
 int32_t fs_ptf_gru_stream_layout(void);
 int32_t fs_ptf_gru_stream_chunk_rows(void);
 int32_t fs_ptf_gru_side_cols(void);
@@ -411,7 +410,7 @@ int fs_ptf_gru_backward(int32_t n, const float* cat, const float* tables, const 
 /* Backward of the GRU over the n fused pairs of a step that fs_ptf_fold_step_save ran (replaces the re-run of the forward inside
  * fs_ptf_gru_backward: 704 instead of 1 400 matrix instructions per 16 pairs; reference: autograd through networks.py:188-214).
  * stream_t: the fs_ptf_gru_stream_t_rows() transposed operand rows of stream layout 2 alone (rows 696 .. 1399, interleaved by quads
- * inside chunks exactly like layout 2, no bias rows; freesplat_amd/ptf.py:gru_operand_stream_t); 0 rows = unavailable in this mode.
+ * inside chunks exactly like layout 2, no bias rows; freesplat_amd/ptf.py:gru_operand_stream_t).
  * side: the step's buffer (columns 6 .. 9 filled by the forward; columns 0 .. 5 are written here), act: the step's gates. */
 int32_t fs_ptf_gru_act_cols(void);
 int32_t fs_ptf_gru_stream_t_rows(void);

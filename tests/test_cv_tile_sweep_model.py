@@ -96,7 +96,7 @@ def test_tile_sweep_model_matches_oracle_autograd(V, K, h4, w4, D, behind):
 
 
 def test_register_form_lists_blend_every_tap_exactly_once():
-    """Model of round 6's pass 2 (cv_src_grad_kernel<C, NAT, 1>): a batch's taps are appended to per-texel lists of 8 entries
+    """Model of round 6's pass 2 (cv_src_grad_kernel<C>): a batch's taps are appended to per-texel lists of 8 entries
     (slot = the value a ds_add_rtn_u32 returns; a tap whose slot is >= 8 stays pending), every texel blends min(count, 8)
     entries, the counters are cleared and the pending taps go round again.  Whatever the collisions, the result is the plain
     scatter-add."""

@@ -421,9 +421,7 @@ def test_training_fold_with_kept_and_with_recomputed_gru_activations(hip_device,
     layers only (fs_ptf_gru_backward_saved); FREESPLAT_GRU_SAVE=0 re-runs the forward inside the backward kernel as before.  Same
     outputs (the same forward kernel arithmetic) and the same gradients -- the kept values ARE the values the re-run produces, up to
     the order in which the two kernels round sigmoid / tanh inputs (identical operand rows, identical MFMA order: in practice bits)."""
-    from freesplat_amd import _lib, ptf as P
-    if _lib.lib().fs_ptf_gru_stream_t_rows() == 0:
-        pytest.skip("32-pair GRU kernels selected (FS_GRU_FWD16=0 / FS_GRU_BWD16=0): no saved-activation backward")
+    from freesplat_amd import ptf as P
     V, h, w = 4, 48, 64
     E, Kn, depths, lat, dens, wts, coords = _scene(V, h, w, seed=78)
     torch.manual_seed(4)
