@@ -25,7 +25,7 @@ class RasterDims(C.Structure):
                 ("flags", C.c_int32)]
 
 
-ABI_VERSION = 6          # include/freesplat_amd.h FS_ABI_VERSION
+ABI_VERSION = 7          # include/freesplat_amd.h FS_ABI_VERSION
 
 RASTER_TILE_CULL = 1
 RASTER_SH_FP16 = 2
@@ -33,6 +33,7 @@ RASTER_SH_CHANNEL_MAJOR = 4
 RASTER_COV_FULL = 8
 RASTER_FAST_EXP = 16
 RASTER_NO_BACKWARD_STATE = 32
+RASTER_DETERMINISTIC = 64
 
 
 def build(force: bool = False) -> str:
@@ -58,6 +59,7 @@ SIGNATURES = {
     "fs_raster_buffer_sizes": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_size_t)]),
     "fs_raster_forward": (C.c_int, [C.POINTER(RasterDims)] + [_VP] * 15 + [C.c_int64] + [_VP] * 6),
     "fs_raster_backward": (C.c_int, [C.POINTER(RasterDims)] + [_VP] * 24 + [C.c_int, _VP]),
+    "fs_raster_backward_scratch_bytes": (C.c_size_t, [C.POINTER(RasterDims), C.c_int32, C.c_int32, C.c_int64]),
     "fs_cost_volume_workspace_bytes": (C.c_size_t, [C.c_int32] * 5),
     "fs_cost_volume_forward": (C.c_int, [C.c_int32] * 6 + [_VP] * 6 + [C.c_int64] * 3 + [_VP] * 9),
     "fs_cost_volume_forward_layout": (C.c_int, [C.c_int32] * 6 + [_VP] * 6 + [C.c_int64] * 3 + [_VP] * 8 + [C.c_int32, _VP]),

@@ -84,6 +84,7 @@ __device__ __forceinline__ float wave_sum_pair(const float (&va)[10], const floa
 }
 
 constexpr int kBwdQuads = 7;  // float4 per slot of two survivors
+constexpr int kSlabStride = 10;  // floats per (list position, quadrant) row of the deterministic mode's slab (components 0..9)
 // Backward blend loop, same organisation as the forward (raster_fwd.hip:blend_quadrant): one single-wavefront
 // workgroup per 8x8 quadrant, no barriers; the tile list is walked BACK TO FRONT 64 entries at a time with the
 // records of the next batch in flight; the survivors of a batch are compacted (highest list position first) two per
@@ -102,13 +103,17 @@ constexpr int kBwdQuads = 7;  // float4 per slot of two survivors
 // fourth channel of the behind-colour recurrence, of the score s and of the colour partials does not exist; what is left of
 // the (blue, depth) pair runs as scalar operations (packed fp32 has no throughput advantage on this chip, fs_common.h), and
 // the wavefront reduction carries 9 instead of 10 values per survivor.
-template <bool FAST_EXP, bool DEPTH>
+// STORE = true (FS_RASTER_DETERMINISTIC): the same loop, but a pair's wavefront sums leave with plain stores into the slab
+// row of (list position, quadrant) -- slab [cap][4][kSlabStride] -- instead of atomics into grad (unused then); every slab
+// row whose entry carries this quadrant's bit is written, with zeros where the pair left early or the entry lies past the
+// quadrant's last contributor, so det_rank_sum never reads an unwritten row.  Positions >= cap_lim are not stored.
+template <bool FAST_EXP, bool DEPTH, bool STORE>
 __global__ __launch_bounds__(64) void render_bwd_kernel(
     int H, int W, int T, const uint32_t* __restrict__ offsets,
     const uint32_t* __restrict__ point_list, const float4* __restrict__ rec,
     const float* __restrict__ bg, const uint32_t* __restrict__ counters, const float* __restrict__ final_T,
     const int32_t* __restrict__ n_contrib, const float* __restrict__ dL_dcolor,
-    const float* __restrict__ dL_ddepth, float* __restrict__ grad)
+    const float* __restrict__ dL_ddepth, float* __restrict__ grad, float* __restrict__ slab, uint32_t cap_lim)
 {
     __shared__ float4 s_pair[33 * kBwdQuads];   // up to 1 carried + 64 new survivors, two per slot
     if (counters && counters[1]) return;  // the forward overflowed its capacity: no image, no lists -> zero gradients
@@ -138,6 +143,17 @@ __global__ __launch_bounds__(64) void render_bwd_kernel(
     int maxlast = last;
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) maxlast = max(maxlast, __shfl_xor(maxlast, m, 64));
+    if constexpr (STORE) {
+        // zero rows for this quadrant's entries in [m_end, n): no pair of the loop below reaches them
+        for (int j = min(n, maxlast) + lane; j < n; j += 64) {
+            const uint32_t pos = a + (uint32_t)j;
+            if ((pl[j] & qbit) && pos < cap_lim) {
+                float2* z = (float2*)(slab + ((size_t)pos * 4 + wave) * kSlabStride);
+#pragma unroll
+                for (int k = 0; k < kSlabStride / 2; ++k) z[k] = make_float2(0.0f, 0.0f);
+            }
+        }
+    }
     if (maxlast == 0) return;
     const int m_end = min(n, maxlast);  // entries at or beyond this position contributed to no pixel of the quadrant
 
@@ -146,6 +162,19 @@ __global__ __launch_bounds__(64) void render_bwd_kernel(
     const int row = lane >> 4, col = lane & 15;
     float4* const cp = s_pair;
 
+    // row r of the wavefront: components 5*(r&1) .. +4 of survivor (r >> 1); lane (r, c < 5) flushes component c
+    auto flush = [&](const float4* q, float v) __attribute__((always_inline)) {
+        const float4 ids = q[6];
+        if (col < 5) {
+            if constexpr (STORE) {
+                const uint32_t pos = __float_as_uint(row < 2 ? ids.z : ids.w);   // (0xffffffff: the unused half of a pair)
+                if (pos < cap_lim) slab[((size_t)pos * 4 + wave) * kSlabStride + 5 * (row & 1) + col] = v;
+            } else {
+                const uint32_t id = __float_as_uint(row < 2 ? ids.x : ids.y);
+                if (v != 0.0f) atomicAdd(&grad[(size_t)id * kGradStride + 5 * (row & 1) + col], v);
+            }
+        }
+    };
     // One pair of survivors (a further back, b in front of it): recompute, recurrences, partials, wavefront sums, flush.
     auto do_pair = [&](const float4* q) __attribute__((always_inline)) {
         const float4 c0 = q[0], c1 = q[1], c2 = q[2], c3 = q[3];
@@ -155,7 +184,10 @@ __global__ __launch_bounds__(64) void render_bwd_kernel(
         bool on_a = __float_as_int(c3.z) <= last, on_b = __float_as_int(c3.w) <= last;
         on_a = on_a & (__float_as_uint(pw.x) <= __float_as_uint(c2.z));
         on_b = on_b & (__float_as_uint(pw.y) <= __float_as_uint(c2.w));
-        if (__builtin_amdgcn_ballot_w64(on_a | on_b) == 0) return;  // wave-uniform
+        if (__builtin_amdgcn_ballot_w64(on_a | on_b) == 0) {  // wave-uniform
+            if constexpr (STORE) flush(q, 0.0f);
+            return;
+        }
         f32x2 Gr = blend_exp_of_neg<FAST_EXP>(pw);
         f32x2 oe = (f32x2){c3.x, c3.y} * Gr;
         f32x2 al_raw = {fminf(0.99f, oe.x), fminf(0.99f, oe.y)};
@@ -172,7 +204,10 @@ __global__ __launch_bounds__(64) void render_bwd_kernel(
         }
         on_a = on_a & (al_raw.x >= 1.0f / 255.0f);
         on_b = on_b & (al_raw.y >= 1.0f / 255.0f);
-        if (__builtin_amdgcn_ballot_w64(on_a | on_b) == 0) return;
+        if (__builtin_amdgcn_ballot_w64(on_a | on_b) == 0) {
+            if constexpr (STORE) flush(q, 0.0f);
+            return;
+        }
         const float4 ka = q[4], kb = q[5];
         const f32x2 al = {on_a ? al_raw.x : 0.0f, on_b ? al_raw.y : 0.0f};
         const f32x2 G = {on_a ? Gr.x : 0.0f, on_b ? Gr.y : 0.0f};
@@ -220,13 +255,7 @@ __global__ __launch_bounds__(64) void render_bwd_kernel(
         const f32x2 sxx = wdx * dx, sxy = wdx * dy, syy = wdy * dy;
         va[0] = wdx.x; va[1] = wdy.x; va[2] = sxx.x; va[3] = sxy.x; va[4] = syy.x; va[5] = v_op.x;
         vb[0] = wdx.y; vb[1] = wdy.y; vb[2] = sxx.y; vb[3] = sxy.y; vb[4] = syy.y; vb[5] = v_op.y;
-        const float v = wave_sum_pair<DEPTH ? 10 : 9>(va, vb);
-        // row r of the wavefront: components 5*(r&1) .. +4 of survivor (r >> 1); lane (r, c < 5) flushes component c
-        const float4 ids = q[6];
-        if (col < 5) {
-            const uint32_t id = __float_as_uint(row < 2 ? ids.x : ids.y);
-            if (v != 0.0f) atomicAdd(&grad[(size_t)id * kGradStride + 5 * (row & 1) + col], v);
-        }
+        flush(q, wave_sum_pair<DEPTH ? 10 : 9>(va, vb));
     };
 
     // software pipeline over batches of 64 entries, highest batch first: list words two batches ahead, records one
@@ -264,7 +293,8 @@ __global__ __launch_bounds__(64) void render_bwd_kernel(
             d[8] = -a1.x; d[10] = skip_bits(a1.z);       // [B_a B_b thr_a thr_b] (B = b; thr = bits of -threshold)
             d[12] = a1.y; d[14] = __int_as_float((bi << 6) + lane + 1);  // [op_a op_b pos_a pos_b]
             cp[(k >> 1) * kBwdQuads + 4 + (k & 1)] = make_float4(a2.x, a2.y, a2.z, a1.w);  // [r g b depth]
-            d[24] = __uint_as_float(w_this >> 4);        // [id_a id_b . .]
+            d[24] = __uint_as_float(w_this >> 4);        // [id_a id_b pos_a pos_b] (positions: STORE only)
+            if constexpr (STORE) d[26] = __uint_as_float(a + (uint32_t)((bi << 6) + lane));
         }
         wave_lds_sync();
         // An odd survivor is CARRIED into the next batch (it stays in the front slot as the `a` half; the next batch's
@@ -287,6 +317,7 @@ __global__ __launch_bounds__(64) void render_bwd_kernel(
             d[15] = __int_as_float(0x7fffffff);
             cp[5] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             d[25] = 0.0f;
+            if constexpr (STORE) d[27] = __uint_as_float(0xffffffffu);
         }
         wave_lds_sync();
         do_pair(cp);
@@ -579,15 +610,293 @@ __global__ __launch_bounds__(256) void zero_float4_kernel(float4* __restrict__ p
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) p[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 }
 
+// ------------------------------------------------------------------------------------------
+// Deterministic mode (FS_RASTER_DETERMINISTIC): render_bwd_kernel<.., STORE = true> stores every pair's sums into the slab row
+// of (list position, quadrant); these kernels sum the rows of each Gaussian in a fixed order into the view's [N, 12] gradient
+// rows, with plain stores (the float atomics of the default mode add in arrival order, which changes from launch to launch).
+// Inverted index of one view (integer atomics only, whose results do not depend on their order):
+//   det_count     cnt[g] = instances of Gaussian g in the view's point list
+//   det_scan_*    exclusive scan: seg[g] = first index slot of g
+//   det_fill      idx[seg[g] + k] = the positions of g, in any order; seg[g] ends as the END of g's slots (start = seg[g-1])
+//   det_rank_sum  one thread per slot: the rank of its position in its segment, and the position's sum over its quadrants
+//                 (0..3 in order) -> rows[] in ascending position order per Gaussian
+// Reduction, split so that no thread walks a long segment alone (a Gaussian that covers thousands of tiles):
+//   det_reduce_chunks  one thread per kDetChunk consecutive slots of rows[]: the runs of its Gaussians in ascending position;
+//                      a Gaussian whose slots all lie in the chunk gets its row written here, the runs cut by a chunk edge
+//                      leave partial sums
+//   det_finish         one thread per Gaussian: the partial sums of a cut segment added in chunk order; zero rows for
+//                      Gaussians with no instance and for every Gaussian of a view whose forward overflowed
+// The order of every fp32 sum is thus a function of the forward's lists alone -- not of the stream count, the instance
+// capacity or the scheduling.
+constexpr int kDetChunk = 32;
+
+struct DetRegion {   // one per stream in flight: [seg N][bsum][slab cap*4 rows][idx cap][gid cap][rows cap][partials (cap/kDetChunk + 1) x 2 rows]
+    uint32_t* seg;
+    uint32_t* bsum;
+    float* slab;
+    __host__ __device__ static size_t head_bytes(int N)
+    {
+        return align_up((size_t)(N + 1) * 4, 256) + align_up((size_t)((N + 2047) / 2048 + 2) * 4, 256);
+    }
+    __host__ __device__ static size_t slab_bytes(size_t cap) { return align_up(cap * 4 * kSlabStride * 4, 256); }
+    __host__ __device__ static size_t bytes(int N, size_t cap)
+    {
+        return head_bytes(N) + slab_bytes(cap) + 2 * align_up(cap * 4, 256) + align_up(cap * kSlabStride * 4, 256) +
+               align_up((cap / kDetChunk + 1) * 2 * kSlabStride * 4, 256);
+    }
+    __host__ __device__ DetRegion(void* base, int N)
+    {
+        char* p = (char*)base;
+        seg = (uint32_t*)p;
+        bsum = (uint32_t*)(p + align_up((size_t)(N + 1) * 4, 256));
+        slab = (float*)(p + head_bytes(N));
+    }
+    // the index and the partial sums follow the slab rows of the view's I instances (I <= cap: device-side layout)
+    __device__ uint32_t* idx(uint32_t I) const { return (uint32_t*)((char*)slab + slab_bytes(I)); }
+    __device__ uint32_t* gid(uint32_t I) const { return (uint32_t*)((char*)idx(I) + align_up((size_t)I * 4, 256)); }
+    __device__ float* rows(uint32_t I) const { return (float*)((char*)gid(I) + align_up((size_t)I * 4, 256)); }
+    __device__ float* partials(uint32_t I) const { return (float*)((char*)rows(I) + align_up((size_t)I * kSlabStride * 4, 256)); }
+};
+
+// instances the index covers: the forward's count, bounded by the buffers' capacity; 0 when the forward overflowed
+__device__ __forceinline__ uint32_t det_instances(const uint32_t* offsets, int T, const uint32_t* counters, uint32_t cap_lim)
+{
+    if (counters && counters[1]) return 0;
+    return min(offsets[T], cap_lim);
+}
+
+__global__ __launch_bounds__(256) void det_count_kernel(int N, int T, const uint32_t* __restrict__ offsets,
+                                                        const uint32_t* __restrict__ point_list, const uint32_t* __restrict__ counters,
+                                                        uint32_t cap_lim, uint32_t* __restrict__ cnt)
+{
+    const uint32_t I = det_instances(offsets, T, counters, cap_lim);
+    for (uint32_t j = blockIdx.x * 256 + threadIdx.x; j < I; j += gridDim.x * 256) {
+        const uint32_t g = point_list[j] >> 4;
+        if (g < (uint32_t)N) atomicAdd(&cnt[g], 1u);
+    }
+}
+
+// exclusive scan of cnt[0..N) in place: blocks of 2048 (256 threads x 8), block totals scanned by one workgroup
+__device__ __forceinline__ uint32_t det_block_excl_scan(uint32_t x, uint32_t* lds, uint32_t& total)
+{
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    uint32_t v = x;
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {
+        const uint32_t o = __shfl_up(v, m, 64);
+        if (lane >= m) v += o;
+    }
+    if (lane == 63) lds[w] = v;
+    __syncthreads();
+    uint32_t off = 0;
+    for (int k = 0; k < w; ++k) off += lds[k];
+    total = lds[0] + lds[1] + lds[2] + lds[3];
+    __syncthreads();
+    return off + v - x;
+}
+__global__ __launch_bounds__(256) void det_scan_blocks_kernel(int N, const uint32_t* __restrict__ cnt, uint32_t* __restrict__ bsum)
+{
+    __shared__ uint32_t lds[4];
+    const size_t b0 = (size_t)blockIdx.x * 2048 + threadIdx.x * 8;
+    uint32_t s = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) s += (b0 + k < (size_t)N) ? cnt[b0 + k] : 0u;
+    uint32_t total;
+    det_block_excl_scan(s, lds, total);
+    if (threadIdx.x == 0) bsum[blockIdx.x] = total;
+}
+__global__ __launch_bounds__(256) void det_scan_totals_kernel(int nb, uint32_t* __restrict__ bsum)
+{
+    __shared__ uint32_t lds[4];
+    uint32_t carry = 0;
+    for (int c = 0; c < nb; c += 256) {
+        const int i = c + threadIdx.x;
+        const uint32_t x = i < nb ? bsum[i] : 0u;
+        uint32_t total;
+        const uint32_t e = det_block_excl_scan(x, lds, total);
+        if (i < nb) bsum[i] = carry + e;
+        carry += total;
+    }
+}
+__global__ __launch_bounds__(256) void det_scan_apply_kernel(int N, uint32_t* __restrict__ cnt, const uint32_t* __restrict__ bsum)
+{
+    __shared__ uint32_t lds[4];
+    const size_t b0 = (size_t)blockIdx.x * 2048 + threadIdx.x * 8;
+    uint32_t x[8], s = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { x[k] = (b0 + k < (size_t)N) ? cnt[b0 + k] : 0u; s += x[k]; }
+    uint32_t total;
+    uint32_t e = bsum[blockIdx.x] + det_block_excl_scan(s, lds, total);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        if (b0 + k < (size_t)N) cnt[b0 + k] = e;
+        e += x[k];
+    }
+}
+
+__global__ __launch_bounds__(256) void det_fill_kernel(int N, int T, const uint32_t* __restrict__ offsets,
+                                                       const uint32_t* __restrict__ point_list, const uint32_t* __restrict__ counters,
+                                                       uint32_t cap_lim, DetRegion r)
+{
+    const uint32_t I = det_instances(offsets, T, counters, cap_lim);
+    uint32_t* const idx = r.idx(I);
+    for (uint32_t j = blockIdx.x * 256 + threadIdx.x; j < I; j += gridDim.x * 256) {
+        const uint32_t g = point_list[j] >> 4;
+        if (g < (uint32_t)N) idx[atomicAdd(&r.seg[g], 1u)] = j;
+    }
+}
+
+// adds the slab rows of list position pos (the quadrants named by its entry's mask, in order 0..3) to acc
+__device__ __forceinline__ void det_add_position(float (&acc)[kSlabStride], const float* __restrict__ slab, uint32_t pos, uint32_t mask)
+{
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        if (!((mask >> q) & 1u)) continue;
+        const float2* r = (const float2*)(slab + ((size_t)pos * 4 + q) * kSlabStride);
+#pragma unroll
+        for (int k = 0; k < kSlabStride / 2; ++k) {
+            const float2 x = r[k];
+            acc[2 * k] += x.x;
+            acc[2 * k + 1] += x.y;
+        }
+    }
+}
+// one thread per index slot k: the rank r of its position among its Gaussian's (the positions are distinct: a Gaussian appears at
+// most once per tile), and the position's sum over its quadrants -> rows[seg start + r], gid[seg start + r] = the Gaussian.  The
+// slots of a segment thus end up in ascending position order whatever order det_fill claimed them in.
+__global__ __launch_bounds__(256) void det_rank_sum_kernel(int N, int T, const uint32_t* __restrict__ offsets,
+                                                           const uint32_t* __restrict__ point_list,
+                                                           const uint32_t* __restrict__ counters, uint32_t cap_lim, DetRegion r)
+{
+    const uint32_t I = det_instances(offsets, T, counters, cap_lim);
+    const uint32_t* __restrict__ idx = r.idx(I);
+    uint32_t* __restrict__ gid = r.gid(I);
+    float* __restrict__ rows = r.rows(I);
+    for (uint32_t k = blockIdx.x * 256 + threadIdx.x; k < I; k += gridDim.x * 256) {
+        const uint32_t pos = idx[k], w = point_list[pos], g = w >> 4;
+        const uint32_t s = g ? r.seg[g - 1] : 0u, e = r.seg[g];
+        uint32_t rank = 0;
+        for (uint32_t m = s; m < e; ++m) rank += idx[m] < pos ? 1u : 0u;
+        float acc[kSlabStride];
+#pragma unroll
+        for (int i = 0; i < kSlabStride; ++i) acc[i] = 0.0f;
+        det_add_position(acc, r.slab, pos, w & 15u);
+        const uint32_t o = s + rank;
+        gid[o] = g;
+        float2* dst = (float2*)(rows + (size_t)o * kSlabStride);
+#pragma unroll
+        for (int i = 0; i < kSlabStride / 2; ++i) dst[i] = make_float2(acc[2 * i], acc[2 * i + 1]);
+    }
+}
+
+__device__ __forceinline__ void det_write_row(float* __restrict__ grad, uint32_t g, const float (&acc)[kSlabStride])
+{
+    float4* o = (float4*)(grad + (size_t)g * kGradStride);
+    o[0] = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    o[1] = make_float4(acc[4], acc[5], acc[6], acc[7]);
+    o[2] = make_float4(acc[8], acc[9], 0.0f, 0.0f);
+}
+
+__global__ __launch_bounds__(256) void det_reduce_chunks_kernel(int N, int T, const uint32_t* __restrict__ offsets,
+                                                                const uint32_t* __restrict__ point_list,
+                                                                const uint32_t* __restrict__ counters, uint32_t cap_lim,
+                                                                DetRegion r, float* __restrict__ grad)
+{
+    const uint32_t I = det_instances(offsets, T, counters, cap_lim);
+    const uint32_t* __restrict__ gid = r.gid(I);
+    const float* __restrict__ rows = r.rows(I);
+    const uint32_t nchunks = (I + kDetChunk - 1) / kDetChunk;
+  for (uint32_t c = blockIdx.x * 256 + threadIdx.x; c < nchunks; c += gridDim.x * 256) {
+    const uint32_t k0 = c * kDetChunk, k1 = min(k0 + kDetChunk, I);
+    float* part = r.partials(I) + (size_t)c * 2 * kSlabStride;
+    uint32_t k = k0;
+    while (k < k1) {
+        const uint32_t g = gid[k];
+        const uint32_t s = g ? r.seg[g - 1] : 0u, e = r.seg[g];
+        float acc[kSlabStride];
+#pragma unroll
+        for (int i = 0; i < kSlabStride; ++i) acc[i] = 0.0f;
+        const uint32_t run_end = min(e, k1);
+        for (; k < run_end; ++k) {   // ascending positions
+            const float2* x = (const float2*)(rows + (size_t)k * kSlabStride);
+#pragma unroll
+            for (int i = 0; i < kSlabStride / 2; ++i) {
+                const float2 y = x[i];
+                acc[2 * i] += y.x;
+                acc[2 * i + 1] += y.y;
+            }
+        }
+        if (s >= k0 && e <= k1) {
+            det_write_row(grad, g, acc);       // the whole segment lies in this chunk
+        } else {
+            // a cut run: it starts this chunk (slot 0 of the pair) or ends it (slot 1)
+            float* o = part + (s <= k0 ? 0 : kSlabStride);
+#pragma unroll
+            for (int i = 0; i < kSlabStride; ++i) o[i] = acc[i];
+        }
+    }
+  }  // chunks
+}
+
+__global__ __launch_bounds__(256) void det_finish_kernel(int N, int T, const uint32_t* __restrict__ offsets,
+                                                         const uint32_t* __restrict__ counters, uint32_t cap_lim, DetRegion r,
+                                                         float* __restrict__ grad)
+{
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= N) return;
+    const uint32_t I = det_instances(offsets, T, counters, cap_lim);
+    float acc[kSlabStride];
+#pragma unroll
+    for (int i = 0; i < kSlabStride; ++i) acc[i] = 0.0f;
+    const uint32_t s = (I == 0 || g == 0) ? 0u : r.seg[g - 1], e = I == 0 ? 0u : r.seg[g];
+    if (e > s) {
+        const uint32_t c0 = s / kDetChunk, c1 = (e - 1) / kDetChunk;
+        if (c0 == c1) return;                  // written by det_reduce_chunks
+        const float* part = r.partials(I);
+        for (uint32_t c = c0; c <= c1; ++c) {
+            // the first chunk's run ends it (slot 1) unless the segment starts on the chunk's edge; later runs start theirs
+            const float* p = part + ((size_t)c * 2 + ((c == c0 && s != c0 * kDetChunk) ? 1 : 0)) * kSlabStride;
+#pragma unroll
+            for (int i = 0; i < kSlabStride; ++i) acc[i] += p[i];
+        }
+    }
+    det_write_row(grad, (uint32_t)g, acc);
+}
+
+__global__ __launch_bounds__(256) void zero_u32_kernel(uint32_t* __restrict__ p, size_t n)
+{
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) p[i] = 0u;
+}
+
 }  // namespace fs
 
 using namespace fs;
 
 namespace {
 
-// blend backward of ONE view into its screen-space gradient rows (grad [N, 12], zeroed here)
+// FS_RASTER_DETERMINISTIC: the slab and the index of one view (DetRegion) + the index build and the reduction into grad
+void launch_det_reduce(const fs_raster_dims& d, const uint32_t* offsets, const uint32_t* point_list, const uint32_t* counters,
+                       uint32_t cap_lim, const DetRegion& r, float* grad, hipStream_t st)
+{
+    const int T = num_tiles(d.H, d.W), N = d.N;
+    const unsigned gN = (unsigned)((N + 255) / 256), nb = (unsigned)((N + 2047) / 2048);
+    constexpr unsigned kGridInst = 2048;   // grid-stride over the instances (their count is on the device)
+    hipLaunchKernelGGL(det_count_kernel, dim3(kGridInst), dim3(256), 0, st, N, T, offsets, point_list, counters, cap_lim, r.seg);
+    hipLaunchKernelGGL(det_scan_blocks_kernel, dim3(nb), dim3(256), 0, st, N, (const uint32_t*)r.seg, r.bsum);
+    hipLaunchKernelGGL(det_scan_totals_kernel, dim3(1), dim3(256), 0, st, (int)nb, r.bsum);
+    hipLaunchKernelGGL(det_scan_apply_kernel, dim3(nb), dim3(256), 0, st, N, r.seg, (const uint32_t*)r.bsum);
+    hipLaunchKernelGGL(det_fill_kernel, dim3(kGridInst), dim3(256), 0, st, N, T, offsets, point_list, counters, cap_lim, r);
+    hipLaunchKernelGGL(det_rank_sum_kernel, dim3(kGridInst), dim3(256), 0, st, N, T, offsets, point_list, counters, cap_lim, r);
+    hipLaunchKernelGGL(det_reduce_chunks_kernel, dim3(kGridInst), dim3(256), 0, st, N, T, offsets, point_list, counters, cap_lim, r,
+                       grad);
+    hipLaunchKernelGGL(det_finish_kernel, dim3(gN), dim3(256), 0, st, N, T, offsets, counters, cap_lim, r, grad);
+}
+
+// blend backward of ONE view into its screen-space gradient rows (grad [N, 12], zeroed here; with det != NULL written by the
+// deterministic reduction instead, from the slab rows of det's region)
 int launch_render_bwd(const fs_raster_dims& d, const float* bg, const void* geom, const void* binning, const void* image,
-                      const uint32_t* counters, const float* dL_dcolor, const float* dL_ddepth, float* grad, hipStream_t st)
+                      const uint32_t* counters, const float* dL_dcolor, const float* dL_ddepth, float* grad, hipStream_t st,
+                      const DetRegion* det = nullptr, uint32_t cap_lim = 0xffffffffu)
 {
     const int T = num_tiles(d.H, d.W);
     const size_t P = (size_t)d.H * d.W;
@@ -598,7 +907,11 @@ int launch_render_bwd(const fs_raster_dims& d, const float* bg, const void* geom
     const int32_t* n_contrib = (const int32_t*)((const char*)image + align_up(P * 4, 256));
     // zero the view's 48 N bytes of screen-space gradient rows with a kernel of our own: hipMemsetAsync's fill kernel ran this at
     // 0.18 TB/s (264 us per view at 1.0 M Gaussians, 19 % of the training step's GPU time: profiles/r6_bwd_fill_ab.txt)
-    {
+    // (deterministic mode: the counts of the index instead -- det_finish writes every gradient row)
+    if (det) {
+        const unsigned blocks = (unsigned)std::min<size_t>(((size_t)d.N + 255) / 256, 4096);
+        if (blocks) hipLaunchKernelGGL(zero_u32_kernel, dim3(blocks), dim3(256), 0, st, det->seg, (size_t)d.N);
+    } else {
         const size_t n4 = (size_t)d.N * kGradStride / 4;      // (kGradStride = 12 floats: three float4 per Gaussian)
         const unsigned blocks = (unsigned)std::min<size_t>((n4 + 255) / 256, 4096);
         if (blocks) hipLaunchKernelGGL(zero_float4_kernel, dim3(blocks), dim3(256), 0, st, (float4*)grad, n4);
@@ -608,11 +921,17 @@ int launch_render_bwd(const fs_raster_dims& d, const float* bg, const void* geom
         ScopedStage prof_(kStRenderBwd, st);
         auto go = [&](auto kernel) {
             hipLaunchKernelGGL(kernel, dim3(4 * nblk), dim3(64), 0, st, d.H, d.W, T, offsets, point_list, g.rec, bg, counters,
-                               final_T, n_contrib, dL_dcolor, dL_ddepth, grad);
+                               final_T, n_contrib, dL_dcolor, dL_ddepth, grad, det ? det->slab : nullptr, cap_lim);
         };
-        const bool depth = dL_ddepth != nullptr;
-        if (d.flags & FS_RASTER_FAST_EXP) { if (depth) go(render_bwd_kernel<true, true>); else go(render_bwd_kernel<true, false>); }
-        else { if (depth) go(render_bwd_kernel<false, true>); else go(render_bwd_kernel<false, false>); }
+        const bool depth = dL_ddepth != nullptr, fast = (d.flags & FS_RASTER_FAST_EXP) != 0;
+        if (det) {
+            if (fast) { if (depth) go(render_bwd_kernel<true, true, true>); else go(render_bwd_kernel<true, false, true>); }
+            else { if (depth) go(render_bwd_kernel<false, true, true>); else go(render_bwd_kernel<false, false, true>); }
+        } else {
+            if (fast) { if (depth) go(render_bwd_kernel<true, true, false>); else go(render_bwd_kernel<true, false, false>); }
+            else { if (depth) go(render_bwd_kernel<false, true, false>); else go(render_bwd_kernel<false, false, false>); }
+        }
+        if (det) launch_det_reduce(d, offsets, point_list, counters, cap_lim, *det, grad, st);
     }
     FS_CHECK_LAUNCH("render_bwd");
     return FS_OK;
@@ -663,7 +982,10 @@ FS_API int fs_raster_backward(const fs_raster_dims* dims, const float* means3D, 
     if (shs ? !dL_dshs : !dL_dcolors) return FS_ERR_INVALID_ARG;
     if (shs && d.M * 3 > 48) return FS_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream_;
-    int rc = launch_render_bwd(d, bg, geom, binning, image, counters, dL_dcolor, dL_ddepth, (float*)grad_scratch, st);
+    // deterministic mode: the view's slab and index follow its gradient rows (fs_raster_backward_scratch_bytes with v = 0)
+    const DetRegion det((char*)grad_scratch + align_up((size_t)d.N * 48, 256), d.N);
+    int rc = launch_render_bwd(d, bg, geom, binning, image, counters, dL_dcolor, dL_ddepth, (float*)grad_scratch, st,
+                               (d.flags & FS_RASTER_DETERMINISTIC) ? &det : nullptr);
     if (rc != FS_OK) return rc;
     return launch_preprocess_bwd(d, 1, means3D, cov3D, shs, opacities, viewmatrix, projmatrix, campos, tanfov_dev, scale_dev, geom, 0,
                                  grad_scratch, 0, dL_dmeans3D, dL_dmeans2D, dL_dcov3D, dL_dshs, dL_dcolors,
@@ -672,6 +994,26 @@ FS_API int fs_raster_backward(const fs_raster_dims* dims, const float* means3D, 
 
 namespace {
 constexpr int kMaxStreamsBwd = 8;
+// instance capacity of a views call's deterministic regions: what its binning stride holds past the tile ranges (0: too small)
+size_t det_capacity(const fs_raster_dims& d, size_t binning_stride)
+{
+    const size_t ranges = binning_offsets_bytes(d.H, d.W);
+    return binning_stride > ranges ? (binning_stride - ranges) / 4 : 0;
+}
+}  // namespace
+
+FS_API size_t fs_raster_backward_scratch_bytes(const fs_raster_dims* dims, int32_t v, int32_t n_streams, int64_t inst_capacity)
+{
+    if (!dims || dims->N < 0 || dims->H <= 0 || dims->W <= 0 || v < 0 || inst_capacity < 0) return 0;
+    const size_t N = (size_t)dims->N, rows = align_up(N * 48, 256);
+    if (!(dims->flags & FS_RASTER_DETERMINISTIC)) return v == 0 ? N * 12 * 4 : (size_t)v * rows;
+    // the capacity as fs_raster_buffer_sizes stores it in the binning buffer (a views call reads it back from strides[1])
+    const size_t cap = align_up((size_t)(inst_capacity > 0 ? inst_capacity : 1) * 4, 256) / 4;
+    const int regions = (v == 0 || n_streams <= 1) ? 1 : std::min(std::min(n_streams, v), kMaxStreamsBwd);
+    return (v == 0 ? rows : (size_t)v * rows) + (size_t)regions * DetRegion::bytes(dims->N, cap);
+}
+
+namespace {
 struct ForkJoinBwd {
     hipEvent_t ready = nullptr, done[kMaxStreamsBwd] = {};
     bool ok = false;
@@ -731,13 +1073,21 @@ static int raster_backward_views_impl(const fs_raster_dims* dims, int32_t v, con
                 return FS_ERR_LAUNCH;
             }
     }
+    // deterministic mode: one slab + index region per stream in flight, after the v gradient buffers, sized by the instance
+    // capacity that the binning stride holds (fs_raster_backward_scratch_bytes)
+    const bool det = (d.flags & FS_RASTER_DETERMINISTIC) != 0;
+    const size_t cap_det = det ? det_capacity(d, strides[1]) : 0;
+    if (det && cap_det == 0) return FS_ERR_INVALID_ARG;
+    const size_t region_bytes = det ? DetRegion::bytes(d.N, cap_det) : 0;
     int rc = FS_OK;
     for (int i = 0; i < v && rc == FS_OK; ++i) {  // the blend backward of every view, alternating over the streams
         hipStream_t st = ns > 0 ? (hipStream_t)streams[i % ns] : main;
+        const DetRegion region((char*)grad_scratch + grad_stride * v + region_bytes * (ns > 0 ? i % ns : 0), d.N);
         rc = launch_render_bwd(d, bg + 3 * (size_t)i, (const char*)geom + strides[0] * i,
                                (const char*)binning + strides[1] * i, (const char*)image + strides[2] * i,
                                counters ? counters + 2 * (size_t)i : nullptr, dL_dcolor + 3 * P * i, dL_ddepth ? dL_ddepth + P * i : nullptr,
-                               (float*)((char*)grad_scratch + grad_stride * i), st);
+                               (float*)((char*)grad_scratch + grad_stride * i), st, det ? &region : nullptr,
+                               (uint32_t)std::min<size_t>(cap_det, 0xffffffffu));
     }
     for (int s = 0; s < ns; ++s)
         if (hipEventRecord(fj.done[s], (hipStream_t)streams[s]) != hipSuccess ||

@@ -231,7 +231,7 @@ class _RenderViews(torch.autograd.Function):
             rs.num_rendered = -1
             states.append(rs)
         # everything the one-call backward needs while the views still live in the strided buffers of this call
-        batch = dict(dims=dims, sz=sz, geom=geom, binning=binning, image=image, counters=counters, bgs=bgs, views=views, fulls=fulls,
+        batch = dict(dims=dims, sz=sz, cap=cap, geom=geom, binning=binning, image=image, counters=counters, bgs=bgs, views=views, fulls=fulls,
                      campos=campos, tanfov=tanfov, scale=scale)
         if deferred:
             # without a backward to come only the 8-byte counter pairs stay alive until the check, not the buffers
@@ -290,11 +290,13 @@ class _RenderViews(torch.autograd.Function):
                 g_color = torch.zeros(v, 3, b["dims"].H, b["dims"].W, dtype=torch.float32, device=dev)
             f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
             out = dict(means3D=f32(N, 3), means2D=f32(N, 3), cov3D=f32(*cov6.shape), shs=f32(*shs.shape), opacities=f32(N))
-            scratch = torch.empty(v * ((N * 48 + 255) // 256 * 256), dtype=torch.uint8, device=dev)
+            dims = R.backward_dims(b["dims"])       # (+ FS_RASTER_DETERMINISTIC: slabs sized by the forward's capacity)
+            scratch = torch.empty(R.backward_scratch_bytes(dims, v, n_streams if n_streams > 1 else 0, b["cap"]),
+                                  dtype=torch.uint8, device=dev)
             strides = (C.c_size_t * 3)(*b["sz"][:3])
             handles = (C.c_void_p * max(n_streams, 1))(*[s.cuda_stream for s in st.side_streams[:n_streams]])
             p = R._lib.ptr
-            common = (C.byref(b["dims"]), v, p(means), p(cov6), p(shs), None, p(opac), p(b["bgs"]), p(b["views"]), p(b["fulls"]),
+            common = (C.byref(dims), v, p(means), p(cov6), p(shs), None, p(opac), p(b["bgs"]), p(b["views"]), p(b["fulls"]),
                       p(b["campos"]), p(b["tanfov"]), p(b["scale"]), p(b["geom"]), p(b["binning"]), p(b["image"]), p(b["counters"]),
                       strides, p(g_color), p(g_depth), p(scratch), p(out["means3D"]), p(out["means2D"]), p(out["cov3D"]),
                       p(out["shs"]), None, p(out["opacities"]), 0, n_streams if n_streams > 1 else 0, handles)

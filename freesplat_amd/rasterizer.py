@@ -38,6 +38,11 @@ TILE_CULL = os.environ.get("FREESPLAT_TILE_CULL", "1") != "0"
 # T >= 1e-4 termination: a flipped one changes a pixel by less than its remaining transmittance, 1e-4 x colour (about one
 # pixel per 2 M; counted in tests and in bench.py's `fast_exp` block).  Opt-in because it is not BIT-exact.
 FAST_EXP = os.environ.get("FREESPLAT_FAST_EXP", "0") == "1"
+# Deterministic backward (include/freesplat_amd.h FS_RASTER_DETERMINISTIC): the blend backward stores every quadrant's sums and
+# adds them per Gaussian in a fixed order instead of with float atomics, so the gradients are the same bits on every run.  On
+# when this is true (FREESPLAT_DETERMINISTIC=1) or torch.use_deterministic_algorithms(True) is in force; read when the
+# backward is launched (the forward and its saved state are the same in both modes).  Costs scratch and time.
+DETERMINISTIC = os.environ.get("FREESPLAT_DETERMINISTIC", "0") == "1"
 # Views of one render_views call are spread round-robin over this many HIP streams so that the short
 # latency-bound launches of one view (tile scan, kernel tails) overlap the VALU-bound blend of another.
 NUM_STREAMS = max(1, int(os.environ.get("FREESPLAT_RASTER_STREAMS", "2")))  # views of one call round-robin over this many streams
@@ -204,6 +209,28 @@ def make_dims(N, M, settings: GaussianRasterizationSettings, sh_fp16: bool = Fal
     return d
 
 
+def deterministic() -> bool:
+    """Whether a backward launched now runs in the deterministic mode (FS_RASTER_DETERMINISTIC)."""
+    return DETERMINISTIC or torch.are_deterministic_algorithms_enabled()
+
+
+def backward_dims(dims: _lib.RasterDims) -> _lib.RasterDims:
+    """The dims a backward is launched with: the forward's, plus FS_RASTER_DETERMINISTIC when deterministic() holds."""
+    if not deterministic():
+        return dims
+    d = _lib.RasterDims.from_buffer_copy(dims)
+    d.flags |= _lib.RASTER_DETERMINISTIC
+    return d
+
+
+def backward_scratch_bytes(dims: _lib.RasterDims, v: int, n_streams: int, cap: int) -> int:
+    """fs_raster_backward_scratch_bytes: v = 0 for the single-view backward."""
+    n = int(_lib.lib().fs_raster_backward_scratch_bytes(C.byref(dims), v, n_streams, cap))
+    if n == 0 and dims.N > 0:
+        raise _lib.FreeSplatHipError("fs_raster_backward_scratch_bytes: invalid arguments")
+    return n
+
+
 def rasterize_forward_checked(dims, means3D, cov3D, shs, colors, opacities, bg, view, proj, campos):
     """Forward + capacity check (one host sync on the 8-byte counter pair), retrying once with the
     exact capacity when the instance list overflowed."""
@@ -231,7 +258,7 @@ def rasterize_backward(rs: RasterState, means3D, cov3D, shs, colors, opacities, 
     """Launch the backward of one view.  `out` = dict of preallocated gradient tensors (for the
     multi-view accumulate path) or None to allocate."""
     dev = means3D.device
-    d = rs.dims
+    d = backward_dims(rs.dims)
     N = d.N
     if out is None:
         out = dict(
@@ -242,7 +269,10 @@ def rasterize_backward(rs: RasterState, means3D, cov3D, shs, colors, opacities, 
             colors=None if colors is None else torch.empty(N, 3, dtype=torch.float32, device=dev),
             opacities=torch.empty(N, dtype=torch.float32, device=dev),
         )
-    scratch = torch.empty(max(N, 1) * 12, dtype=torch.float32, device=dev)
+    if d.flags & _lib.RASTER_DETERMINISTIC:
+        scratch = torch.empty(max(backward_scratch_bytes(d, 0, 0, rs.cap), 1), dtype=torch.uint8, device=dev)
+    else:
+        scratch = torch.empty(max(N, 1) * 12, dtype=torch.float32, device=dev)
     if g_color is None:
         g_color = torch.zeros(3, d.H, d.W, dtype=torch.float32, device=dev)
     g_color = g_color.contiguous()

@@ -44,7 +44,7 @@ const char* fs_version(void);
  * it right after loading the library (freesplat_amd/_lib.py does): a stale build would otherwise accept calls with
  * shifted pointers.  3 = round 3 (single-pass binning: scratch = per-tile key areas, counters[1] = largest tile list on
  * overflow, geom without the mask / depth arrays; fused sort + blend). */
-#define FS_ABI_VERSION 6
+#define FS_ABI_VERSION 7
 int fs_abi_version(void);
 /* Last HIP error string observed by a failing call on this thread (never NULL). */
 const char* fs_last_error(void);
@@ -103,6 +103,21 @@ typedef struct fs_raster_dims {
  * lists of tiles with more than 2048 entries, which are sorted through global memory -- `binning` must still be a buffer
  * of the size fs_raster_buffer_sizes reports); fs_raster_backward(_views) refuses dims that carry the flag. */
 #define FS_RASTER_NO_BACKWARD_STATE 32
+/* Deterministic backward (ABI revision 7): fs_raster_backward, fs_raster_backward_views and fs_raster_backward_views_rows
+ * produce the same gradient bits on every run.  The default backward adds each 8x8 quadrant's per-Gaussian sums into the
+ * view's gradient rows with float atomics, whose arrival order -- and so the last bits of the sum -- changes from launch
+ * to launch.  With this flag every quadrant's sums are stored once into a slab row of (list position, quadrant) and each
+ * Gaussian's rows are summed in a fixed order, with plain stores:
+ *   per view: ascending position in the view's depth-sorted lists (ascending tile index; a Gaussian appears at most once
+ *   per tile) of the per-position sums, each of which adds the 8x8 quadrants 0, 1, 2, 3 in that order.  The positions of a Gaussian are summed in consecutive runs
+ *   that break where the view's inverted index (slots ordered by Gaussian, then position) crosses a multiple of 32 slots;
+ *   the run sums are added in run order.
+ *   over views: in view order, inside the per-Gaussian pass (as without the flag).
+ * For fixed inputs and fixed flags the gradients are therefore the same bits whatever the stream count, the batch size, the
+ * instance capacity, the workgroup scheduling or the _rows chunking.  They differ from the default mode's only by the
+ * order of the fp32 sums.  Costs scratch (fs_raster_backward_scratch_bytes) and time.  The forward entry points
+ * accept the flag and ignore it. */
+#define FS_RASTER_DETERMINISTIC 64
 
 /* Byte sizes of the four caller-owned device buffers for (N, H, W, instance capacity):
  *   out[0] geom    : per-Gaussian screen-space state            (saved for backward)
@@ -170,7 +185,8 @@ int fs_raster_forward_views(const fs_raster_dims* dims, int32_t v, const float* 
  * are the buffers filled by the matching forward, `counters` the forward's counter pair (may be NULL): when its
  * overflow flag is set the forward produced no image and no valid lists, and the backward of that view yields
  * ZERO gradients instead of walking unbacked tile ranges (a caller that defers the capacity check -- decoder
- * check="deferred" -- may reach backward before it has seen the flag).  `grad_scratch` >= N*12*4 bytes.
+ * check="deferred" -- may reach backward before it has seen the flag).  `grad_scratch` >= N*12*4 bytes, or with
+ * FS_RASTER_DETERMINISTIC fs_raster_backward_scratch_bytes(dims, 0, 0, the forward's inst_capacity) bytes.
  * Outputs (device; overwritten when accumulate == 0, added to when accumulate != 0 -- the
  * multi-view decoder sums the per-view gradients of one shared Gaussian set this way):
  * dL_dmeans3D[N,3], dL_dmeans2D[N,3] (screen-space grad
@@ -509,7 +525,9 @@ int fs_depth_tail_backward(int32_t B, int32_t D, int32_t h2, int32_t w2, const f
 /* Backward of v views of ONE Gaussian set in one host call (counterpart of fs_raster_forward_views; same packed
  * per-view arrays and buffer strides[0..2] = geom / binning / image; counters [v,2] | NULL as in fs_raster_backward).
  * dL_dcolor [v,3,H,W], dL_ddepth [v,H,W] | NULL.
- * grad_scratch: v buffers of align_up(N*48, 256) bytes.  The blend backward of the views alternates over the
+ * grad_scratch: v buffers of align_up(N*48, 256) bytes (FS_RASTER_DETERMINISTIC: fs_raster_backward_scratch_bytes(dims, v,
+ * n_streams, cap) bytes, where cap is the forward's inst_capacity: the call reads it back from strides[1], so strides[1] must
+ * be the binning size fs_raster_buffer_sizes reported for cap).  The blend backward of the views alternates over the
  * streams; after the join ONE pass over the Gaussians turns the screen-space gradients of all views into the
  * parameter gradients (inputs read once, sums in registers, outputs written once; `accumulate` adds to their
  * current contents).  Stream-ordered on main_stream like fs_raster_forward_views. */
@@ -536,6 +554,14 @@ int fs_raster_backward_views_rows(const fs_raster_dims* dims, int32_t v, const f
                                   float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcov3D, float* dL_dshs,
                                   float* dL_dcolors, float* dL_dopacities, int32_t accumulate, int32_t n_streams,
                                   void* const* streams, void* main_stream, int32_t row0, int32_t nrows, int32_t with_blend);
+
+/* Bytes of `grad_scratch` the backward needs.  v = 0: fs_raster_backward (one view); v >= 1: fs_raster_backward_views(_rows)
+ * with v views on n_streams streams.  Without FS_RASTER_DETERMINISTIC in dims->flags: N*12*4 (v = 0) or v*align_up(N*48, 256),
+ * as before; n_streams and inst_capacity are not used.  With it, those gradient rows plus one region per stream in flight
+ * (one for v = 0 or n_streams <= 1), each sized by inst_capacity (the forward's): the slab, cap x 4 quadrants x 40 B, the
+ * view's inverted index, the per-position sums and the run sums of the reduction -- about 210 B per instance.  0 for invalid
+ * arguments. */
+size_t fs_raster_backward_scratch_bytes(const fs_raster_dims* dims, int32_t v, int32_t n_streams, int64_t inst_capacity);
 
 /* ---- PTF training path: backward of one fold step's data movement (encoder_freesplat.py:485-519) ----
  * fs_ptf_fold_step_lists: device pointers (into the step's scratch) of the four ordered index lists the step left
