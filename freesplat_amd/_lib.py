@@ -25,7 +25,7 @@ class RasterDims(C.Structure):
                 ("flags", C.c_int32)]
 
 
-ABI_VERSION = 7          # include/freesplat_amd.h FS_ABI_VERSION
+ABI_VERSION = 8          # include/freesplat_amd.h FS_ABI_VERSION
 
 RASTER_TILE_CULL = 1
 RASTER_SH_FP16 = 2
@@ -114,6 +114,10 @@ SIGNATURES = {
     "fs_invert_4x4": (C.c_int, [C.c_int32, _VP, _VP, _VP]),
     "fs_depth_tail_forward": (C.c_int, [C.c_int32] * 4 + [_VP] * 2 + [C.c_int32] + [_VP] * 7),
     "fs_depth_tail_backward": (C.c_int, [C.c_int32] * 4 + [_VP] * 2 + [C.c_int32] + [_VP] * 13),
+    "fs_image_metrics_scratch_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "fs_image_metrics": (C.c_int, [C.c_int32] * 4 + [_VP] * 7),
+    "fs_depth_metrics_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
+    "fs_depth_metrics": (C.c_int, [C.c_int32, C.c_int64, _VP, _VP, C.c_float, _VP, _VP, _VP]),
     "fs_raster_scratch_slots": (C.c_int, [C.c_int32, C.c_int32]),
     "fs_raster_tile_ranges": (_VP, [_VP, C.c_int32, C.c_int32]),
     "fs_raster_point_list": (_VP, [_VP, C.c_int32, C.c_int32]),

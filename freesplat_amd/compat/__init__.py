@@ -19,7 +19,29 @@ def install() -> None:
     sys.modules.setdefault("diff_gaussian_rasterization_depth", m)
 
 
-def patch_reference(decoder: bool = True) -> dict:
+METRIC_MODULES = ("src.evaluation.metrics", "src.model.model_wrapper", "src.evaluation.metric_computer")
+
+
+def patch_metrics() -> dict:
+    """Rebind the evaluation metrics inside the importable reference package `src` to the device ones
+    (freesplat_amd/metrics.py): compute_psnr and compute_ssim in each module that imported them by name
+    (src.evaluation.metrics, src.model.model_wrapper, src.evaluation.metric_computer), and
+    src.model.model_wrapper.depth_render_metrics.  compute_lpips stays the reference's.
+    Returns {dotted name: replacement} like patch_reference()."""
+    from .. import metrics
+    done = {}
+    for modname in METRIC_MODULES:
+        mod = importlib.import_module(modname)
+        for n in ("compute_psnr", "compute_ssim"):
+            setattr(mod, n, getattr(metrics, n))
+            done[f"{modname}.{n}"] = getattr(metrics, n)
+    mw = importlib.import_module("src.model.model_wrapper")
+    mw.depth_render_metrics = metrics.depth_render_metrics
+    done["src.model.model_wrapper.depth_render_metrics"] = metrics.depth_render_metrics
+    return done
+
+
+def patch_reference(decoder: bool = True, metrics: bool = False) -> dict:
     """Rebind, inside the already importable reference package `src`, every name on the hot path to its
     MI355X implementation (same constructor / call signatures and state-dict keys, so configs and
     checkpoints are untouched):
@@ -32,7 +54,8 @@ def patch_reference(decoder: bool = True) -> dict:
                                                                                  replaced by direct indexing)
       src.model.encoder.modules.networks.DepthDecoder.forward                   (networks.py:108-154)
       src.model.decoder.DECODERS["splatting_cuda"]                              (decoder/__init__.py:5-13)
-    Returns {dotted name: replacement} for logging."""
+    and with metrics=True also the evaluation metrics (patch_metrics()); without it the evaluation modules are not
+    imported.  Returns {dotted name: replacement} for logging."""
     from .. import cost_volume, depth_tail, encoder_forward, gaussian_adapter, ptf
     from ..decoder import DecoderSplattingCUDA
     done = {}
@@ -59,4 +82,6 @@ def patch_reference(decoder: bool = True) -> dict:
         dec.DECODERS["splatting_cuda"] = DecoderSplattingCUDA
         dec.DecoderSplattingCUDA = DecoderSplattingCUDA
         done['src.model.decoder.DECODERS["splatting_cuda"]'] = DecoderSplattingCUDA
+    if metrics:
+        done.update(patch_metrics())
     return done

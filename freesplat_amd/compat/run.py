@@ -12,6 +12,8 @@ does, in this order,
   3. runpy.run_module(<module>, run_name="__main__") with sys.argv = [<module>, args...]
 
 `--dry-run` after the module name stops after step 2 and prints what was rebound (used to check the wiring against the reference tree).
+`--gpu-metrics` after the module name also rebinds the evaluation metrics (compat.patch_metrics(): compute_psnr, compute_ssim,
+depth_render_metrics on the device).  Both flags are removed from the target's argv.
 """
 import os
 import runpy
@@ -25,13 +27,14 @@ def main(argv=None) -> dict:
         raise SystemExit(0 if argv else 2)
     module, rest = argv[0], argv[1:]
     dry = "--dry-run" in rest
-    rest = [a for a in rest if a != "--dry-run"]
+    gpu_metrics = "--gpu-metrics" in rest
+    rest = [a for a in rest if a not in ("--dry-run", "--gpu-metrics")]
     if os.getcwd() not in sys.path:
         sys.path.insert(0, os.getcwd())
     from freesplat_amd import _lib, compat
     _lib.lib()                      # fail now, loudly, if libfreesplat_hip.so is missing: there is no fallback path
     compat.install()
-    done = compat.patch_reference()
+    done = compat.patch_reference(metrics=gpu_metrics)
     for name, obj in done.items():
         print(f"[freesplat_amd] {name} -> {getattr(obj, '__module__', '?')}.{getattr(obj, '__qualname__', obj)}", file=sys.stderr)
     if dry:

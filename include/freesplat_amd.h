@@ -20,6 +20,10 @@
  *   fs_ptf_*
  *       the device steps of EncoderFreeSplat.fuse_gaussians,
  *       src/model/encoder/encoder_freesplat.py:431-522.
+ *   fs_image_metrics / fs_depth_metrics
+ *       compute_ssim and compute_psnr, src/evaluation/metrics.py:11-19, 37-52 (as called from
+ *       src/model/model_wrapper.py:74-86 and src/evaluation/metric_computer.py:54-55), and the masked
+ *       per-view sums of depth_render_metrics, src/model/model_wrapper.py:90-110.
  */
 #ifndef FREESPLAT_AMD_H
 #define FREESPLAT_AMD_H
@@ -43,8 +47,9 @@ const char* fs_version(void);
 /* Integer ABI revision: bumped whenever a signature, a flag or the layout of an opaque buffer changes.  A binding checks
  * it right after loading the library (freesplat_amd/_lib.py does): a stale build would otherwise accept calls with
  * shifted pointers.  3 = round 3 (single-pass binning: scratch = per-tile key areas, counters[1] = largest tile list on
- * overflow, geom without the mask / depth arrays; fused sort + blend). */
-#define FS_ABI_VERSION 7
+ * overflow, geom without the mask / depth arrays; fused sort + blend).  8 = the evaluation metrics (fs_image_metrics,
+ * fs_depth_metrics). */
+#define FS_ABI_VERSION 8
 int fs_abi_version(void);
 /* Last HIP error string observed by a failing call on this thread (never NULL). */
 const char* fs_last_error(void);
@@ -587,6 +592,34 @@ int fs_ptf_write_state_backward(int32_t n_keep, int32_t n_fuse, int32_t n_app, c
 int fs_ptf_gru_inputs_backward(int32_t n_fuse, const int64_t* fuse_idx, const int64_t* fuse_pix, const float* R,
                                const float* O, const float* rho_i, const float* om_i, const float* dcat, float* g_G,
                                float* g_R, float* g_O, float* g_lat_i, float* g_rho_i, float* g_om_i, void* stream);
+
+/* ------------------------------------------------------------------------------------ *
+ * Evaluation metrics (metrics.py:11-52, model_wrapper.py:74-110)                        *
+ * ------------------------------------------------------------------------------------ */
+
+/* gt, pred [B,C,H,W] (B, C >= 1, H, W >= 11) -> per view
+ *   ssim[B] (double): skimage.metrics.structural_similarity(gt_b, pred_b, win_size=11, gaussian_weights=True,
+ *     channel_axis=0, data_range=1.0): 11-tap Gaussian (sigma 1.5, weights normalised in double, used in fp32), sample
+ *     covariance (121/120), C1 = 1e-4, C2 = 9e-4, S averaged over the interior [5,H-5) x [5,W-5) of every channel (the
+ *     5-pixel crop skimage applies: every kept window lies inside the image), then over channels.  Inputs are not clipped;
+ *     NaN / Inf propagate.  Identical inputs give exactly 1.0.
+ *   mse[B] (double): mean over c, h, w of (clip(gt,0,1) - clip(pred,0,1))^2 (compute_psnr's; PSNR = -10 log10(mse)).
+ *   ssim_map [B,C,H-10,W-10] fp32 = S per interior pixel, or NULL (not written).
+ * Per-pixel arithmetic fp32, sums fp64 in a fixed order: a view's values are the same bits whatever the batch, the stream
+ * or the run.  scratch: fs_image_metrics_scratch_bytes(B, C, H, W) bytes (0 = invalid arguments).  H or W < 11 (where
+ * skimage raises "win_size exceeds image extent"), B, C <= 0 or a NULL required pointer: FS_ERR_INVALID_ARG. */
+size_t fs_image_metrics_scratch_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
+int fs_image_metrics(int32_t B, int32_t C, int32_t H, int32_t W, const float* gt, const float* pred, double* ssim,
+                     double* mse, float* ssim_map, void* scratch, void* stream);
+/* gt, pred [B,HW] (B = b*v views) -> out [6,B] (double): per view
+ *   out[0] n_valid = #(gt > threshold)        out[1] n_nonnan = valid pixels whose |gt - pred| is not NaN
+ *   out[2] sum |gt - pred|  and  out[3] sum |gt - pred| / gt  over those pixels
+ *   out[4] / out[5] = valid pixels with max(gt/pred, pred/gt) < 1.25 / < 1.1f (a NaN ratio counts as false).
+ * The caller forms abs_diff = out[2]/out[1], abs_rel = out[3]/out[1], delta = out[4|5]/out[0] (0/0 = NaN as nanmean gives).
+ * Deterministic as fs_image_metrics.  scratch: fs_depth_metrics_scratch_bytes(B, HW) bytes (0 = invalid arguments). */
+size_t fs_depth_metrics_scratch_bytes(int32_t B, int64_t HW);
+int fs_depth_metrics(int32_t B, int64_t HW, const float* gt, const float* pred, float threshold, double* out,
+                     void* scratch, void* stream);
 
 /* Debug/test accessors into the opaque buffers (device pointers, no copies). */
 const uint32_t* fs_raster_tile_ranges(const void* binning, int32_t H, int32_t W);  /* [T+1] offsets */
