@@ -25,7 +25,7 @@ class RasterDims(C.Structure):
                 ("flags", C.c_int32)]
 
 
-ABI_VERSION = 8          # include/freesplat_amd.h FS_ABI_VERSION
+ABI_VERSION = 9          # include/freesplat_amd.h FS_ABI_VERSION
 
 RASTER_TILE_CULL = 1
 RASTER_SH_FP16 = 2
@@ -70,6 +70,8 @@ SIGNATURES = {
     "fs_cost_volume_saved_bytes": (C.c_size_t, [C.c_int32] * 5),
     "fs_cost_volume_forward_train": (C.c_int, [C.c_int32] * 6 + [_VP] * 6 + [C.c_int64] * 3 + [_VP] * 10),
     "fs_cost_volume_backward_train": (C.c_int, [C.c_int32] * 6 + [_VP] * 6 + [C.c_int64] * 3 + [_VP] * 17),
+    "fs_cost_volume_backward_det_bytes": (C.c_size_t, [C.c_int32] * 6),
+    "fs_cost_volume_backward_det": (C.c_int, [C.c_int32] * 6 + [_VP] * 6 + [C.c_int64] * 3 + [_VP] * 18),
     "fs_unproject_forward": (C.c_int, [C.c_int32] * 3 + [_VP] * 5),
     "fs_unproject_backward": (C.c_int, [C.c_int32] * 3 + [_VP] * 5),
     "fs_gaussian_head_forward": (C.c_int, [C.c_int64] + [_VP] * 4 + [C.c_int64, _VP, C.c_float, C.c_float] + [_VP] * 5),
@@ -110,10 +112,15 @@ SIGNATURES = {
     "fs_ptf_fold_step_lists": (C.c_int, [C.c_int32] * 3 + [_VP, C.POINTER(C.c_void_p)]),
     "fs_ptf_write_state_backward": (C.c_int, [C.c_int32] * 3 + [_VP] * 12 + [C.POINTER(C.c_void_p)] * 2 + [_VP] * 6),
     "fs_ptf_gru_inputs_backward": (C.c_int, [C.c_int32] + [_VP] * 14),
+    "fs_ptf_backward_det_bytes": (C.c_size_t, [C.c_int32] * 2),
+    "fs_ptf_write_state_backward_det": (C.c_int, [C.c_int32] * 3 + [_VP] * 12 + [C.POINTER(C.c_void_p)] * 2 + [_VP] * 5
+                                        + [C.c_int32, _VP, _VP]),
+    "fs_ptf_gru_inputs_backward_det": (C.c_int, [C.c_int32] + [_VP] * 13 + [C.c_int32, _VP, _VP]),
     "fs_frame_views": (C.c_int, [C.c_int32] + [_VP] * 4 + [C.c_int32] + [_VP] * 6),
     "fs_invert_4x4": (C.c_int, [C.c_int32, _VP, _VP, _VP]),
     "fs_depth_tail_forward": (C.c_int, [C.c_int32] * 4 + [_VP] * 2 + [C.c_int32] + [_VP] * 7),
     "fs_depth_tail_backward": (C.c_int, [C.c_int32] * 4 + [_VP] * 2 + [C.c_int32] + [_VP] * 13),
+    "fs_depth_tail_backward_det": (C.c_int, [C.c_int32] * 4 + [_VP] * 2 + [C.c_int32] + [_VP] * 11),
     "fs_image_metrics_scratch_bytes": (C.c_size_t, [C.c_int32] * 4),
     "fs_image_metrics": (C.c_int, [C.c_int32] * 4 + [_VP] * 7),
     "fs_depth_metrics_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),

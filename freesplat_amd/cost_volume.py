@@ -19,6 +19,7 @@ import torch
 from torch import Tensor, nn
 
 from . import _lib
+from .rasterizer import deterministic
 
 
 def save_activations(K: int) -> bool:
@@ -120,13 +121,28 @@ class _CostVolumeFn(torch.autograd.Function):
         D, strides = ctx.D, ctx.strides
         dev = g.device
         L = _lib.lib()
-        ws = torch.empty(L.fs_cost_volume_backward_workspace_bytes_for(B, K, C, h, w, D, strides[2]), dtype=torch.uint8, device=dev)
+        det = _deterministic_backward(K, strides[2])
+        if det:
+            ws = torch.empty(L.fs_cost_volume_backward_workspace_bytes(B, K, C, h, w, D), dtype=torch.uint8, device=dev)
+        else:
+            ws = torch.empty(L.fs_cost_volume_backward_workspace_bytes_for(B, K, C, h, w, D, strides[2]), dtype=torch.uint8,
+                             device=dev)
         d_cur, d_src = torch.empty_like(cur_feats), torch.empty_like(src_feats)
         e = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
         d_w1, d_b1, d_w2, d_b2, d_w3, d_b3 = e(32, C + 1), e(32), e(32, 32), e(32), e(1, 32), e(1)
         p = _lib.ptr
         g_ = g.contiguous()
-        if ctx.saved is not None:
+        if det:
+            # no float atomics: per-view fixed-order sums of slab rows (include/freesplat_amd.h fs_cost_volume_backward_det)
+            ds = torch.empty(L.fs_cost_volume_backward_det_bytes(B, K, C, h, w, D), dtype=torch.uint8, device=dev)
+            _lib.check(L.fs_cost_volume_backward_det(B, K, C, h, w, D, p(cur_feats), p(src_feats), p(src_extrinsics),
+                                                     p(src_Ks), p(cur_invK), p(planes), strides[0], strides[1], strides[2],
+                                                     p(w1.detach()), p(b1.detach()), p(w2.detach()), p(b2.detach()),
+                                                     p(w3.detach()), p(g_), p(ws), p(ctx.saved), p(d_cur), p(d_src),
+                                                     p(d_w1), p(d_b1), p(d_w2), p(d_b2), p(d_w3), p(d_b3), p(ds),
+                                                     _lib.current_stream()), "fs_cost_volume_backward_det")
+            ctx.saved = None
+        elif ctx.saved is not None:
             _lib.check(L.fs_cost_volume_backward_train(B, K, C, h, w, D, p(cur_feats), p(src_feats), p(src_extrinsics),
                                                        p(src_Ks), p(cur_invK), p(planes), strides[0], strides[1], strides[2],
                                                        p(w1.detach()), p(b1.detach()), p(w2.detach()), p(b2.detach()),
@@ -143,6 +159,25 @@ class _CostVolumeFn(torch.autograd.Function):
                        "fs_cost_volume_backward")
         # (every gradient, the MLP's included, comes out of the one kernel: no per-point workspace, no GEMMs here)
         return d_cur, d_src, None, None, None, None, None, d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, None, None
+
+
+def _deterministic_backward(K: int, plane_stride_pix: int) -> bool:
+    """Whether this backward runs the deterministic form (rasterizer.deterministic()).  K > 16 and per-pixel planes have only
+    the atomic scatter form: in the deterministic mode they raise, as torch does for an op without a deterministic
+    implementation -- or, under torch.use_deterministic_algorithms(True, warn_only=True), warn and run the atomic form."""
+    if not deterministic():
+        return False
+    if K <= 16 and plane_stride_pix == 0:
+        return True
+    why = "K > 16 source views" if K > 16 else "per-pixel depth planes"
+    msg = (f"freesplat_amd cost volume backward with {why} does not have a deterministic implementation (only the atomic "
+           "scatter form handles it), but deterministic mode is on (torch.use_deterministic_algorithms(True) or "
+           "FREESPLAT_DETERMINISTIC=1)")
+    if torch.are_deterministic_algorithms_enabled() and torch.is_deterministic_algorithms_warn_only_enabled():
+        import warnings
+        warnings.warn(msg)
+        return False
+    raise RuntimeError(msg)
 
 
 def _dev32(t: Tensor, name: str) -> Tensor:

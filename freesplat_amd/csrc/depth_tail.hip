@@ -383,6 +383,111 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     }
 }
 
+// Deterministic variant (fs_depth_tail_backward_det): the same gradient without LDS float atomics.  The four wavefronts add their
+// fine pixels' terms into g_prob ONE WAVEFRONT AT A TIME (wavefront 0 first; a lane owns its pixel's column, so inside a
+// wavefront no two lanes share an address and a lane adds its nine candidates in order), and each wavefront's share of the
+// depth-map term goes to its own row of s_gEw, summed in wavefront order.  Every gather starts with a barrier: no wavefront clears
+// g_prob while another still reads the previous chunk (D > 128).  Any D, one code path (the planes in chunks of 128).
+__global__ __launch_bounds__(256) void depth_tail_bwd_det_kernel(int B, int D, int h2, int w2, const float* __restrict__ logits,
+                                                                 const float* __restrict__ cand, int log_planes,
+                                                                 const float* __restrict__ stats,
+                                                                 const float* __restrict__ coarse,
+                                                                 const float* __restrict__ depth,
+                                                                 const float* __restrict__ depth_map,
+                                                                 const int32_t* __restrict__ argmax,
+                                                                 const float* __restrict__ g_coarse,
+                                                                 const float* __restrict__ g_depth,
+                                                                 const float* __restrict__ g_map,
+                                                                 const float* __restrict__ g_w, float* __restrict__ g_logits)
+{
+    __shared__ __attribute__((aligned(16))) float s_gp[kBwdPlanes * 64];
+    __shared__ float s_gEw[4][64], s_dot[4][64];
+    const int hw = h2 * w2, H = 2 * h2, W = 2 * w2;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const long long e = (long long)blockIdx.x * 64 + lane;
+    const bool live = e < (long long)B * hw;
+    const long long ee = live ? e : 0;
+    const int b = (int)(ee / hw), p = (int)(ee % hw);
+    const int Y = p / w2, X = p % w2;
+    s_gEw[w][lane] = 0.0f;
+
+    auto gather = [&](int c0, bool with_map) {
+        __syncthreads();                                   // (every wavefront is done with the previous chunk's g_prob)
+        for (int k = threadIdx.x; k < kBwdPlanes * 16; k += 256) ((float4*)s_gp)[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        float wt[9], gw[9];
+        int dd[9];
+        float gEacc = 0.0f;
+        const size_t fb = (size_t)b * H * W;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) {
+            const int idx = 9 * w + i;
+            const int fy = 2 * Y + idx / 6 - 2, fx = 2 * X + idx % 6 - 2;
+            const bool inside = live && fy >= 0 && fy < H && fx >= 0 && fx < W;
+            const int cy = min(max(fy, 0), H - 1), cx = min(max(fx, 0), W - 1);
+            const Bilin q = bilin_x2(cy, cx, h2, w2);
+            wt[i] = inside ? (q.i00 == p ? q.w00 : 0.0f) + (q.i01 == p ? q.w01 : 0.0f) + (q.i10 == p ? q.w10 : 0.0f) +
+                                 (q.i11 == p ? q.w11 : 0.0f)
+                           : 0.0f;
+            const int f = cy * W + cx;
+            dd[i] = g_w ? argmax[fb + f] - c0 : -1;
+            gw[i] = g_w ? g_w[fb + f] : 0.0f;
+            if (with_map && g_map && wt[i] != 0.0f) {
+                const float dm = depth_map[fb + f], gm = g_map[fb + f];
+                gEacc += wt[i] * (log_planes ? gm * dm : -gm * dm * dm);
+            }
+        }
+        if (with_map) s_gEw[w][lane] = gEacc;
+        for (int turn = 0; turn < 4; ++turn) {
+            __syncthreads();                               // (the clear, then the previous wavefront's adds)
+            if (w == turn && g_w) {
+#pragma unroll
+                for (int i = 0; i < 9; ++i)
+                    if (wt[i] != 0.0f && dd[i] >= 0 && dd[i] < kBwdPlanes) s_gp[dd[i] * 64 + lane] += wt[i] * gw[i];
+            }
+        }
+        __syncthreads();
+    };
+
+    const bool up = g_map || g_w;
+    const float m = stats[(size_t)b * 2 * hw + p], rs = 1.0f / stats[(size_t)b * 2 * hw + hw + p];
+    const float* l = logits + (size_t)b * D * hw + p;
+    const int nchunks = (D + kBwdPlanes - 1) / kBwdPlanes;
+    float dot = 0.0f;
+    if (up) {
+        for (int c = 0; c < nchunks; ++c) {
+            gather(c * kBwdPlanes, c == 0);
+            if (g_w) {
+                const int dend = min(D, (c + 1) * kBwdPlanes);
+                for (int d = c * kBwdPlanes + w; d < dend; d += 4)
+                    dot += expf(l[(size_t)d * hw] - m) * rs * s_gp[(d - c * kBwdPlanes) * 64 + lane];
+            }
+        }
+        if (g_w) {
+            s_dot[w][lane] = dot;
+            __syncthreads();
+            dot = (s_dot[0][lane] + s_dot[1][lane]) + (s_dot[2][lane] + s_dot[3][lane]);
+        }
+    } else {
+        __syncthreads();     // (s_gEw's zeros)
+    }
+    const float E = coarse[ee];
+    float gE = ((s_gEw[0][lane] + s_gEw[1][lane]) + s_gEw[2][lane]) + s_gEw[3][lane];
+    if (g_coarse) gE += g_coarse[ee];
+    if (g_depth) gE += log_planes ? g_depth[ee] * depth[ee] : -g_depth[ee] * depth[ee] * depth[ee];
+    float* go = g_logits + (size_t)b * D * hw + p;
+    for (int c = 0; c < nchunks; ++c) {
+        if (up && nchunks > 1) gather(c * kBwdPlanes, false);      // (one chunk: the gather above is still in LDS)
+        const int dend = min(D, (c + 1) * kBwdPlanes);
+        if (live) {
+            for (int d = c * kBwdPlanes + w; d < dend; d += 4) {
+                const float pd = expf(l[(size_t)d * hw] - m) * rs;
+                const float gpd = g_w ? s_gp[(d - c * kBwdPlanes) * 64 + lane] : 0.0f;
+                go[(size_t)d * hw] = pd * ((cand[d] - E) * gE + gpd - dot);
+            }
+        }
+    }
+}
+
 }  // namespace fs
 
 using namespace fs;
@@ -431,5 +536,25 @@ FS_API int fs_depth_tail_backward(int32_t B, int32_t D, int32_t h2, int32_t w2, 
     };
     if (D <= kBwdPlanes) go(depth_tail_bwd_kernel<true>); else go(depth_tail_bwd_kernel<false>);
     FS_CHECK_LAUNCH("depth_tail_backward");
+    return FS_OK;
+}
+
+// Deterministic backward (ABI 9): depth_tail_bwd_det_kernel, bitwise repeatable; the arguments of fs_depth_tail_backward
+// without its two unused scratch pointers.
+FS_API int fs_depth_tail_backward_det(int32_t B, int32_t D, int32_t h2, int32_t w2, const float* logits,
+                                      const float* candidates, int32_t log_planes, const float* stats,
+                                      const float* coarse, const float* depth, const float* depth_map,
+                                      const int32_t* argmax, const float* g_coarse, const float* g_depth,
+                                      const float* g_map, const float* g_weights, float* g_logits, void* stream_)
+{
+    if (B <= 0 || D <= 0 || h2 <= 0 || w2 <= 0 || !logits || !candidates || !stats || !coarse || !depth || !g_logits)
+        return FS_ERR_INVALID_ARG;
+    if ((g_map || g_weights) && (!depth_map || !argmax)) return FS_ERR_INVALID_ARG;
+    hipStream_t st = (hipStream_t)stream_;
+    const long long n = (long long)B * h2 * w2;
+    ScopedStage prof_(kStEncoderTail, st);
+    hipLaunchKernelGGL(depth_tail_bwd_det_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, B, D, h2, w2, logits, candidates,
+                       log_planes, stats, coarse, depth, depth_map, argmax, g_coarse, g_depth, g_map, g_weights, g_logits);
+    FS_CHECK_LAUNCH("depth_tail_backward_det");
     return FS_OK;
 }

@@ -633,6 +633,181 @@ __host__ __device__ inline size_t ptf_scratch_layout(int M, int P, size_t off[7]
     return o;
 }
 
+// ---- deterministic backward (fs_ptf_*_backward_det) ----
+// Several fused rows can share a pixel p of view i (exact z-buffer ties), and the default kernels add their terms into the view's
+// per-pixel gradients with float atomics: arrival order.  Here the adds happen in ascending fuse-row order.  An inverted index
+// pixel -> rows is built with integer atomics only (count; a segment for every pixel with two or more rows; fill), and a row's
+// rank in its segment is the number of rows of the segment before it.  A row whose pixel has no other row adds its terms
+// directly (a plain read-modify-write: no other thread of the launch touches that pixel); a tied row stores its terms at
+// (segment + rank), and ptf_det_tie_sum_kernel adds them to the pixel in rank order.
+// scratch: cnt[P], fill[P], total (zeroed together), seg[P], slot[n], list[n], terms[n][kPtfDetTerms]
+constexpr int kPtfDetTerms = 66;          // the most terms a fused row adds: 64 latent floats + rho + om (gru inputs)
+__host__ __device__ inline size_t ptf_det_layout(int n, int P, size_t off[6])
+{
+    size_t o = 0;
+    off[0] = o; o += align_up(((size_t)2 * P + 1) * 4, 256);     // cnt, fill, total
+    off[1] = o; o += align_up((size_t)P * 4, 256);               // seg
+    off[2] = o; o += align_up((size_t)n * 4, 256);               // slot
+    off[3] = o; o += align_up((size_t)n * 4, 256);               // list
+    off[4] = o; o += align_up((size_t)n * kPtfDetTerms * 4, 256);   // terms
+    off[5] = o;
+    return o;
+}
+struct PtfDetIndex { int* cnt; int* fill; int* total; int* seg; int* slot; int* list; float* terms; };
+
+__global__ __launch_bounds__(256) void ptf_det_count_kernel(int n, const long long* __restrict__ fuse_pix, int* __restrict__ cnt)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t < n) atomicAdd(&cnt[fuse_pix[t]], 1);
+}
+__global__ __launch_bounds__(256) void ptf_det_segment_kernel(int n, const long long* __restrict__ fuse_pix, PtfDetIndex ix)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    const long long p = fuse_pix[t];
+    const int c = ix.cnt[p];
+    if (c < 2) return;
+    const int s = atomicAdd(&ix.fill[p], 1);
+    if (s == 0) ix.seg[p] = atomicAdd(ix.total, c);     // (where a segment lies does not matter, only the ranks inside it)
+    ix.slot[t] = s;
+}
+__global__ __launch_bounds__(256) void ptf_det_fill_kernel(int n, const long long* __restrict__ fuse_pix, PtfDetIndex ix)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    const long long p = fuse_pix[t];
+    if (ix.cnt[p] >= 2) ix.list[ix.seg[p] + ix.slot[t]] = t;
+}
+// row t of pixel p: -1 if p has no other row, else its position (segment + rank) in the list
+__device__ __forceinline__ int ptf_det_pos(const PtfDetIndex& ix, long long p, int t)
+{
+    const int c = ix.cnt[p];
+    if (c < 2) return -1;
+    const int s = ix.seg[p];
+    int r = 0;
+    for (int j = 0; j < c; ++j) r += ix.list[s + j] < t ? 1 : 0;
+    return s + r;
+}
+// MODE 0: the write-state terms (x[3], d, om, rho); MODE 1: the gru-input terms (latent[64], rho, om).  The lowest row of a
+// tied pixel adds every row's terms, in rank order.
+template <int MODE>
+__global__ __launch_bounds__(256) void ptf_det_tie_sum_kernel(int n, const long long* __restrict__ fuse_pix, PtfDetIndex ix,
+                                                              float* __restrict__ g_lat_i, float* __restrict__ g_x_i,
+                                                              float* __restrict__ g_rho_i, float* __restrict__ g_om_i,
+                                                              float* __restrict__ g_d_i)
+{
+    constexpr int NT = MODE == 0 ? 6 : 66;
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int t = (int)(e / NT), k = (int)(e % NT);
+    if (t >= n) return;
+    const long long p = fuse_pix[t];
+    const int c = ix.cnt[p];
+    if (c < 2) return;
+    const int s = ix.seg[p];
+    int first = ix.list[s];
+    for (int j = 1; j < c; ++j) first = min(first, ix.list[s + j]);
+    if (first != t) return;
+    float* dst;
+    if (MODE == 0) dst = k < 3 ? g_x_i + 3 * p + k : (k == 3 ? g_d_i + p : (k == 4 ? g_om_i + p : g_rho_i + p));
+    else dst = k < 64 ? g_lat_i + 64 * p + k : (k == 64 ? g_rho_i + p : g_om_i + p);
+    float v = *dst;
+    for (int j = 0; j < c; ++j) v += ix.terms[(size_t)(s + j) * kPtfDetTerms + k];
+    *dst = v;
+}
+
+// ptf_write_state_bwd_fused_kernel with the four per-pixel adds made order-fixed (same arithmetic per term)
+__global__ __launch_bounds__(256) void ptf_write_state_bwd_fused_det_kernel(
+    int n_keep, int n_fuse, const long long* __restrict__ fuse_idx, const long long* __restrict__ fuse_pix, PtfState s,
+    const float* __restrict__ x_i, const float* __restrict__ rho_i, const float* __restrict__ d_i,
+    const float* __restrict__ E_i, PtfGrad go, PtfGrad gs, float* __restrict__ g_x_i,
+    float* __restrict__ g_rho_i, float* __restrict__ g_om_i, float* __restrict__ g_d_i, PtfDetIndex ix)
+{
+    const int t = blockIdx.x * 64 + (threadIdx.x >> 2), c = threadIdx.x & 3;
+    if (t >= n_fuse) return;                  // (whole quads leave together: the shuffles below stay inside a quad)
+    const int row = n_keep + t;
+    const float4 z4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    const long long m = fuse_idx[t], p = fuse_pix[t];
+    const int pos = ptf_det_pos(ix, p, t);
+    float* const tm = pos >= 0 ? ix.terms + (size_t)pos * kPtfDetTerms : nullptr;
+    auto put = [&](float* dst, int k, float v) { if (tm) tm[k] = v; else *dst += v; };
+    const float w0 = s.R[m], w1 = rho_i[p], ws = w0 + w1, inv = 1.0f / ws;
+    float dw0 = 0.0f, dw1 = 0.0f;
+    {
+        const float4 a = ((const float4*)(s.E + m * 16))[c], b = ((const float4*)E_i)[c];
+        const float4 g = go.E ? ((const float4*)(go.E + (size_t)row * 16))[c] : z4;
+        const float ox = (a.x * w0 + b.x * w1) * inv, oy = (a.y * w0 + b.y * w1) * inv;
+        const float oz = (a.z * w0 + b.z * w1) * inv, ow = (a.w * w0 + b.w * w1) * inv;
+        ((float4*)(gs.E + m * 16))[c] = make_float4(g.x * w0 * inv, g.y * w0 * inv, g.z * w0 * inv, g.w * w0 * inv);
+        dw0 += (g.x * (a.x - ox) + g.y * (a.y - oy) + g.z * (a.z - oz) + g.w * (a.w - ow)) * inv;
+        dw1 += (g.x * (b.x - ox) + g.y * (b.y - oy) + g.z * (b.z - oz) + g.w * (b.w - ow)) * inv;
+    }
+    if (c == 0) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float a = s.X[3 * m + k], b = x_i[3 * p + k], g = go.X ? go.X[3 * (size_t)row + k] : 0.0f;
+            const float o = (a * w0 + b * w1) * inv;
+            gs.X[3 * m + k] = g * w0 * inv;
+            put(&g_x_i[3 * p + k], k, g * w1 * inv);
+            dw0 += g * (a - o) * inv;
+            dw1 += g * (b - o) * inv;
+        }
+    }
+    if (c == 1) {
+        const float a = s.D[m], b = d_i[p], g = go.D ? go.D[row] : 0.0f;
+        const float o = (a * w0 + b * w1) * inv;
+        gs.D[m] = g * w0 * inv;
+        put(&g_d_i[p], 3, g * w1 * inv);
+        dw0 += g * (a - o) * inv;
+        dw1 += g * (b - o) * inv;
+        const float gR = go.R ? go.R[row] : 0.0f, gO = go.O ? go.O[row] : 0.0f;
+        dw0 += gR; dw1 += gR;          // R_out = w0 + w1
+        gs.O[m] = gO;                  // O_out = O[m] + om_i[p]
+        put(&g_om_i[p], 4, gO);
+    }
+#pragma unroll
+    for (int d = 2; d >= 1; d >>= 1) {
+        dw0 += __shfl_xor(dw0, d, 64);
+        dw1 += __shfl_xor(dw1, d, 64);
+    }
+    if (c == 0) {
+        gs.R[m] = dw0;                 // (+ the positional-encoding term: ptf_gru_inputs_bwd adds it)
+        put(&g_rho_i[p], 5, dw1);
+    }
+}
+
+// ptf_gru_inputs_bwd_kernel with the per-pixel adds made order-fixed
+__global__ __launch_bounds__(256) void ptf_gru_inputs_bwd_det_kernel(int n_fuse, const long long* __restrict__ fuse_idx,
+                                                                    const long long* __restrict__ fuse_pix,
+                                                                    const float* __restrict__ R, const float* __restrict__ O,
+                                                                    const float* __restrict__ rho_i,
+                                                                    const float* __restrict__ om_i,
+                                                                    const float* __restrict__ dcat, float* __restrict__ gG,
+                                                                    float* __restrict__ gR, float* __restrict__ gO,
+                                                                    float* __restrict__ g_lat_i, float* __restrict__ g_rho_i,
+                                                                    float* __restrict__ g_om_i, PtfDetIndex ix)
+{
+    const int t = blockIdx.x * 16 + (threadIdx.x >> 4), c = threadIdx.x & 15;
+    if (t >= n_fuse) return;                       // (whole 16-lane groups leave: the quad shuffles below stay inside one)
+    const long long m = fuse_idx[t], p = fuse_pix[t];
+    const int pos = ptf_det_pos(ix, p, t);
+    float* const tm = pos >= 0 ? ix.terms + (size_t)pos * kPtfDetTerms : nullptr;
+    auto put = [&](float* dst, int k, float v) { if (tm) tm[k] = v; else *dst += v; };
+    const float* row = dcat + (size_t)t * 176;
+    ((float4*)(gG + m * 64))[c] = ((const float4*)row)[c];                    // hid: in-row m is fused exactly once
+    float* q = g_lat_i + p * 64 + c;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) put(q + 16 * j, 16 * j + c, row[88 + 16 * j + c]);
+    const int sc = c >> 2;
+    const float v = sc == 0 ? rho_i[p] : sc == 1 ? O[m] : sc == 2 ? R[m] : om_i[p];
+    const float d = pos_enc_bwd_lane(v, row + (sc < 2 ? 64 : 152) + 12 * (sc & 1), c & 3);
+    if ((c & 3) == 0) {
+        if (sc == 0) put(&g_rho_i[p], 64, d);
+        else if (sc == 1) gO[m] += d;
+        else if (sc == 2) gR[m] += d;
+        else put(&g_om_i[p], 65, d);
+    }
+}
+
 }  // namespace fs
 
 using namespace fs;
@@ -988,5 +1163,99 @@ FS_API int fs_ptf_gru_inputs_backward(int32_t n_fuse, const int64_t* fuse_idx, c
                        (const long long*)fuse_idx, (const long long*)fuse_pix, R, O, rho_i, om_i, dcat, g_G, g_R, g_O,
                        g_lat_i, g_rho_i, g_om_i);
     FS_CHECK_LAUNCH("ptf_gru_inputs_bwd");
+    return FS_OK;
+}
+
+// ---- deterministic backward (ABI 9) ----
+FS_API size_t fs_ptf_backward_det_bytes(int32_t n_fuse, int32_t P)
+{
+    if (n_fuse < 0 || P <= 0) return 0;
+    size_t off[6];
+    return ptf_det_layout(n_fuse, P, off);
+}
+
+// builds the pixel -> rows index of the fuse list (integer atomics only); false: a launch failed
+static bool ptf_det_index(int n, int P, const long long* fuse_pix, void* scratch, PtfDetIndex& ix, hipStream_t st)
+{
+    size_t off[6];
+    ptf_det_layout(n, P, off);
+    char* base = (char*)scratch;
+    ix.cnt = (int*)(base + off[0]); ix.fill = ix.cnt + P; ix.total = ix.fill + P;
+    ix.seg = (int*)(base + off[1]); ix.slot = (int*)(base + off[2]); ix.list = (int*)(base + off[3]);
+    ix.terms = (float*)(base + off[4]);
+    if (hipMemsetAsync(ix.cnt, 0, ((size_t)2 * P + 1) * 4, st) != hipSuccess) {
+        set_last_error("ptf det index memset", hipGetLastError());
+        return false;
+    }
+    const dim3 g((unsigned)((n + 255) / 256));
+    hipLaunchKernelGGL(ptf_det_count_kernel, g, dim3(256), 0, st, n, fuse_pix, ix.cnt);
+    hipLaunchKernelGGL(ptf_det_segment_kernel, g, dim3(256), 0, st, n, fuse_pix, ix);
+    hipLaunchKernelGGL(ptf_det_fill_kernel, g, dim3(256), 0, st, n, fuse_pix, ix);
+    return true;
+}
+
+// fs_ptf_write_state_backward, bitwise repeatable: the fused rows add into the view's per-pixel gradients in ascending row
+// order.  P = the view's pixel count (every fuse_pix < P); scratch = fs_ptf_backward_det_bytes(n_fuse, P) bytes.
+FS_API int fs_ptf_write_state_backward_det(int32_t n_keep, int32_t n_fuse, int32_t n_app, const int64_t* keep_idx,
+                                           const int64_t* fuse_idx, const int64_t* fuse_pix, const int64_t* append_pix,
+                                           const float* X, const float* R, const float* E, const float* D,
+                                           const float* x_i, const float* rho_i, const float* d_i, const float* E_i,
+                                           float* const* g_out, float* const* g_in, float* g_lat_i, float* g_x_i,
+                                           float* g_rho_i, float* g_om_i, float* g_d_i, int32_t P, void* scratch, void* stream_)
+{
+    if (n_keep < 0 || n_fuse < 0 || n_app < 0 || P < 0 || !g_out || !g_in) return FS_ERR_INVALID_ARG;
+    const long long n_out = (long long)n_keep + n_fuse + n_app;
+    if (n_out == 0) return FS_OK;
+    if (!g_lat_i || !g_x_i || !g_rho_i || !g_om_i || !g_d_i || !x_i || !rho_i || !d_i || !E_i) return FS_ERR_INVALID_ARG;
+    if (n_keep || n_fuse) {
+        if (!X || !R || !E || !D) return FS_ERR_INVALID_ARG;
+        for (int k = 0; k < 6; ++k)
+            if (!g_in[k]) return FS_ERR_INVALID_ARG;
+    }
+    if (n_fuse > 0 && (!fuse_idx || !fuse_pix || !scratch || P <= 0)) return FS_ERR_INVALID_ARG;
+    hipStream_t st = (hipStream_t)stream_;
+    ScopedStage prof_(kStPtf, st);
+    PtfState s{nullptr, const_cast<float*>(X), const_cast<float*>(R), nullptr, const_cast<float*>(E), const_cast<float*>(D)};
+    PtfGrad go{g_out[0], g_out[1], g_out[2], g_out[3], g_out[4], g_out[5]};
+    PtfGrad gs{g_in[0], g_in[1], g_in[2], g_in[3], g_in[4], g_in[5]};
+    const long long n_ka = (long long)n_keep + n_app;
+    if (n_ka > 0)   // (kept and appended rows: stores and read-modify-writes of pixels no fused row has, no atomics)
+        hipLaunchKernelGGL(ptf_write_state_bwd_kernel, dim3((unsigned)((n_ka + 63) / 64)), dim3(256), 0, st, n_keep, n_fuse,
+                           n_app, (const long long*)keep_idx, (const long long*)fuse_idx, (const long long*)fuse_pix,
+                           (const long long*)append_pix, s, x_i, rho_i, d_i, E_i, go, gs, g_lat_i, g_x_i, g_rho_i, g_om_i, g_d_i);
+    if (n_fuse > 0) {
+        PtfDetIndex ix;
+        if (!ptf_det_index(n_fuse, P, (const long long*)fuse_pix, scratch, ix, st)) return FS_ERR_LAUNCH;
+        hipLaunchKernelGGL(ptf_write_state_bwd_fused_det_kernel, dim3((unsigned)((n_fuse + 63) / 64)), dim3(256), 0, st, n_keep,
+                           n_fuse, (const long long*)fuse_idx, (const long long*)fuse_pix, s, x_i, rho_i, d_i, E_i, go, gs, g_x_i,
+                           g_rho_i, g_om_i, g_d_i, ix);
+        hipLaunchKernelGGL(ptf_det_tie_sum_kernel<0>, dim3((unsigned)(((long long)n_fuse * 6 + 255) / 256)), dim3(256), 0, st, n_fuse,
+                           (const long long*)fuse_pix, ix, g_lat_i, g_x_i, g_rho_i, g_om_i, g_d_i);
+    }
+    FS_CHECK_LAUNCH("ptf_write_state_bwd_det");
+    return FS_OK;
+}
+
+// fs_ptf_gru_inputs_backward, bitwise repeatable (as fs_ptf_write_state_backward_det; same P and scratch size)
+FS_API int fs_ptf_gru_inputs_backward_det(int32_t n_fuse, const int64_t* fuse_idx, const int64_t* fuse_pix, const float* R,
+                                          const float* O, const float* rho_i, const float* om_i, const float* dcat,
+                                          float* g_G, float* g_R, float* g_O, float* g_lat_i, float* g_rho_i, float* g_om_i,
+                                          int32_t P, void* scratch, void* stream_)
+{
+    if (n_fuse < 0 || P < 0) return FS_ERR_INVALID_ARG;
+    if (n_fuse == 0) return FS_OK;
+    if (!fuse_idx || !fuse_pix || !R || !O || !rho_i || !om_i || !dcat || !g_G || !g_R || !g_O || !g_lat_i || !g_rho_i ||
+        !g_om_i || !scratch || P <= 0)
+        return FS_ERR_INVALID_ARG;
+    hipStream_t st = (hipStream_t)stream_;
+    ScopedStage prof_(kStPtf, st);
+    PtfDetIndex ix;
+    if (!ptf_det_index(n_fuse, P, (const long long*)fuse_pix, scratch, ix, st)) return FS_ERR_LAUNCH;
+    hipLaunchKernelGGL(ptf_gru_inputs_bwd_det_kernel, dim3((n_fuse + 15) / 16), dim3(256), 0, st, n_fuse,
+                       (const long long*)fuse_idx, (const long long*)fuse_pix, R, O, rho_i, om_i, dcat, g_G, g_R, g_O,
+                       g_lat_i, g_rho_i, g_om_i, ix);
+    hipLaunchKernelGGL(ptf_det_tie_sum_kernel<1>, dim3((unsigned)(((long long)n_fuse * 66 + 255) / 256)), dim3(256), 0, st, n_fuse,
+                       (const long long*)fuse_pix, ix, g_lat_i, (float*)nullptr, g_rho_i, g_om_i, (float*)nullptr);
+    FS_CHECK_LAUNCH("ptf_gru_inputs_bwd_det");
     return FS_OK;
 }

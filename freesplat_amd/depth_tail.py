@@ -13,6 +13,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
+from .rasterizer import deterministic
 
 
 class _DepthTail(torch.autograd.Function):
@@ -50,6 +51,13 @@ class _DepthTail(torch.autograd.Function):
         g_logits = torch.empty_like(logits)
         p = _lib.ptr
         gc_, gd_, gm_, gw_ = c(g_coarse), c(g_depth), c(g_map), c(g_w)   # (kept alive until the launch is queued)
+        if deterministic():
+            # (bitwise repeatable: the wavefronts add into the LDS gradient in a fixed order; rasterizer.deterministic())
+            _lib.check(_lib.lib().fs_depth_tail_backward_det(B, D, h2, w2, p(logits), p(cand), int(log_planes), p(stats),
+                                                             p(coarse), p(depth), p(dmap), p(am), p(gc_), p(gd_), p(gm_),
+                                                             p(gw_), p(g_logits), _lib.current_stream()),
+                       "fs_depth_tail_backward_det")
+            return g_logits, None, None, None
         _lib.check(_lib.lib().fs_depth_tail_backward(B, D, h2, w2, p(logits), p(cand), int(log_planes), p(stats), p(coarse),
                                                      p(depth), p(dmap), p(am), p(gc_), p(gd_), p(gm_), p(gw_), p(sE), p(sP),
                                                      p(g_logits), _lib.current_stream()), "fs_depth_tail_backward")

@@ -11,6 +11,8 @@ from __future__ import annotations
 import torch
 from torch import Tensor
 
+from .rasterizer import deterministic
+
 
 def rotation_distance(rotations: Tensor) -> Tensor:
     """encoder_freesplat.py:40-48: pairwise rotation angle, rotations [1,V,3,3] -> [V,V]."""
@@ -24,6 +26,29 @@ def calculate_distance_matrix(poses: Tensor) -> Tensor:
     """encoder_freesplat.py:50-60: poses [1,V,4,4] (c2w) -> [V,V] translation + rotation distance."""
     t = poses[:, :, :3, 3]
     return torch.cdist(t, t).squeeze(0) + rotation_distance(poses[:, :, :3, :3])
+
+
+class _PickSources(torch.autograd.Function):
+    """t [b,V,...], idx [b,Vr,Ks] -> t[bi, idx] [b,Vr,Ks,...], with a backward that adds the gradient of every copy of a view in
+    a fixed order: current view by current view (ascending), each adding its Ks rows, which name Ks DIFFERENT views
+    (select_source_views never repeats a view in a row), so no step writes one row twice and nothing depends on arrival order."""
+
+    @staticmethod
+    def forward(ctx, t, idx):
+        ctx.save_for_backward(idx)
+        ctx.shape = t.shape
+        bi = torch.arange(t.shape[0], device=t.device)[:, None]
+        return t[bi[:, :, None], idx]
+
+    @staticmethod
+    def backward(ctx, g):
+        idx, = ctx.saved_tensors
+        out = g.new_zeros(ctx.shape)
+        bi = torch.arange(out.shape[0], device=out.device)[:, None]
+        for v in range(idx.shape[1]):
+            rows = (bi, idx[:, v])                                   # [b,Ks] distinct views per scene: plain stores
+            out.index_put_(rows, out[rows] + g[:, v])
+        return out, None
 
 
 def select_source_views(extrinsics: Tensor, num_context_views: int) -> Tensor:
@@ -69,7 +94,12 @@ def prepare_cost_volume_inputs(extrinsics: Tensor, intrinsics: Tensor, matching_
         src_indices = src_indices[:, cur]
     Vr, Ks = src_indices.shape[1:]
     bi = torch.arange(b, device=dev)[:, None, None]
-    pick = lambda t: t[bi, src_indices]                                             # [b,V,...] -> [b,Vr,Ks,...]
+    if deterministic():
+        # every view is a source of several others: the indexing's backward would add the copies with an accumulating
+        # index_put_ (atomics unless torch's own switch is on); _PickSources adds them in ascending current-view order
+        pick = lambda t: _PickSources.apply(t, src_indices)
+    else:
+        pick = lambda t: t[bi, src_indices]                                         # [b,V,...] -> [b,Vr,Ks,...]
     src_extr = pick(extrinsics)                                                      # [b,Vr,Ks,4,4]
     src_K3 = pick(K)
     inv = lambda t: torch.linalg.inv_ex(t).inverse

@@ -30,6 +30,7 @@ import torch
 from torch import Tensor, nn
 
 from . import _lib
+from .rasterizer import deterministic
 
 
 class _GruRows(torch.autograd.Function):
@@ -253,13 +254,19 @@ def save_gru_activations(V: int = 2, P: int = 0, device=None) -> bool:
     backward runs the transposed layers only (fs_ptf_gru_backward_saved: 704 instead of 1 400 MFMAs per 16 pairs) -- 4 KB per
     possible fused pair and step held until the backward: (V - 1) * P * 4 KB, 10 GB for config 3's three views at 968x1296.
     FREESPLAT_GRU_SAVE=1 / 0 forces it on / off (A/B); otherwise it is on when that fits a quarter of the memory currently free
-    on the device (a 288 GB MI355X: always; a small card falls back to the re-running backward instead of running out of memory)."""
+    on the device (a 288 GB MI355X: always; a small card falls back to the re-running backward instead of running out of memory).
+    In the deterministic mode (rasterizer.deterministic()) it is a quarter of the device's TOTAL memory instead: the two GRU
+    backwards round differently, so the choice must not follow the memory that happens to be free."""
     e = os.environ.get("FREESPLAT_GRU_SAVE")
     if e is not None:
         return e != "0"
     if P <= 0 or device is None:
         return True
     need = (V - 1) * P * 4 * (_lib.lib().fs_ptf_gru_side_cols() + _lib.lib().fs_ptf_gru_act_cols() + 176)
+    if deterministic():
+        # (the two GRU backwards round differently: in the deterministic mode the choice must not follow the memory that happens
+        #  to be free, so it follows the device's total memory)
+        return need <= torch.cuda.get_device_properties(device).total_memory // 4
     try:
         free, _total = torch.cuda.mem_get_info(device)
     except Exception:
@@ -527,6 +534,11 @@ class _PtfFold(torch.autograd.Function):
         c = lambda t: None if t is None else t.contiguous()
         g_out = [c(gG), c(gX), None, None, c(gE), None if gD is None else gD.contiguous().view(n, 1)]
         vp = lambda ts: (C.c_void_p * 6)(*[None if t is None else t.data_ptr() for t in ts])
+        det_scratch = None
+        if deterministic():
+            # tied fused rows add into the view's pixels in row order (fs_ptf_*_backward_det): one scratch for every step
+            nf_max = max(cnt[i][1] for i in range(1, V))
+            det_scratch = torch.empty(max(L.fs_ptf_backward_det_bytes(nf_max, P), 1), dtype=torch.uint8, device=dev)
         for i in range(V - 1, 0, -1):
             nk, nf, na, _ = cnt[i]
             M_in = cnt[i - 1][3]
@@ -541,10 +553,13 @@ class _PtfFold(torch.autograd.Function):
                         torch.empty(M_in, 16, dtype=torch.float32, device=dev), g_dep[0].view(P, 1)]
             else:
                 g_in = [torch.empty(M_in, k, dtype=torch.float32, device=dev) for k in (64, 3, 1, 1, 16, 1)]
-            _lib.check(L.fs_ptf_write_state_backward(
-                nk, nf, na, keep, fuse, fpix, app, p(X), p(R), p(E), p(D), p(xs[i]), p(rho[i]), p(dep[i]), p(Es[i]),
-                vp(g_out), vp(g_in), p(g_lat[i]), p(g_xs[i]), p(g_rho[i]), p(g_om[i]), p(g_dep[i]),
-                _lib.current_stream()), "fs_ptf_write_state_backward")
+            ws_args = (nk, nf, na, keep, fuse, fpix, app, p(X), p(R), p(E), p(D), p(xs[i]), p(rho[i]), p(dep[i]), p(Es[i]),
+                       vp(g_out), vp(g_in), p(g_lat[i]), p(g_xs[i]), p(g_rho[i]), p(g_om[i]), p(g_dep[i]))
+            if det_scratch is not None:
+                _lib.check(L.fs_ptf_write_state_backward_det(*ws_args, P, p(det_scratch), _lib.current_stream()),
+                           "fs_ptf_write_state_backward_det")
+            else:
+                _lib.check(L.fs_ptf_write_state_backward(*ws_args, _lib.current_stream()), "fs_ptf_write_state_backward")
             if nf > 0:
                 # the GRU rows: re-gather their inputs (HIP), GRU backward on the matrix cores (+ the weight-gradient GEMMs)
                 sv = ctx.saves[i]
@@ -560,9 +575,13 @@ class _PtfFold(torch.autograd.Function):
                 dcat, g_params = gru_backward(params, ctx.tables, ctx.operand_stream, cat, g_fused, g_flat,
                                               saved=None if sv is None else (sv[0], sv[1], ctx.stream_t))
                 ctx.saves[i] = None
-                _lib.check(L.fs_ptf_gru_inputs_backward(nf, fuse, fpix, p(R), p(O), p(rho[i]), p(om[i]), p(dcat),
-                                                        p(g_in[0]), p(g_in[2]), p(g_in[3]), p(g_lat[i]), p(g_rho[i]),
-                                                        p(g_om[i]), _lib.current_stream()), "fs_ptf_gru_inputs_backward")
+                gi_args = (nf, fuse, fpix, p(R), p(O), p(rho[i]), p(om[i]), p(dcat), p(g_in[0]), p(g_in[2]), p(g_in[3]),
+                           p(g_lat[i]), p(g_rho[i]), p(g_om[i]))
+                if det_scratch is not None:
+                    _lib.check(L.fs_ptf_gru_inputs_backward_det(*gi_args, P, p(det_scratch), _lib.current_stream()),
+                               "fs_ptf_gru_inputs_backward_det")
+                else:
+                    _lib.check(L.fs_ptf_gru_inputs_backward(*gi_args, _lib.current_stream()), "fs_ptf_gru_inputs_backward")
             g_out = g_in
         need = ctx.needs_input_grad
         pick = lambda k, t: t if need[k] else None

@@ -48,8 +48,9 @@ const char* fs_version(void);
  * it right after loading the library (freesplat_amd/_lib.py does): a stale build would otherwise accept calls with
  * shifted pointers.  3 = round 3 (single-pass binning: scratch = per-tile key areas, counters[1] = largest tile list on
  * overflow, geom without the mask / depth arrays; fused sort + blend).  8 = the evaluation metrics (fs_image_metrics,
- * fs_depth_metrics). */
-#define FS_ABI_VERSION 8
+ * fs_depth_metrics).  9 = deterministic backwards of the cost volume, the PTF fold and the depth tail
+ * (fs_cost_volume_backward_det, fs_ptf_*_backward_det, fs_depth_tail_backward_det and their size queries). */
+#define FS_ABI_VERSION 9
 int fs_abi_version(void);
 /* Last HIP error string observed by a failing call on this thread (never NULL). */
 const char* fs_last_error(void);
@@ -308,6 +309,29 @@ int fs_cost_volume_backward_train(int32_t B, int32_t K, int32_t C, int32_t h, in
                                   float* d_w1, float* d_b1, float* d_w2, float* d_b2, float* d_w3, float* d_b3,
                                   void* stream);
 
+/* Deterministic backward (ABI 9): the two-pass form with no float atomics, bitwise repeatable.  Pass 1 stores each
+ * workgroup's summed MLP gradients into a row of a slab and, for planes split over workgroups, each plane slice's d cur into
+ * a slab of its own; pass 2 stores each plane chunk's source tiles into a slab of its own; fixed-order kernels add the rows
+ * of one view, then the views in ascending order, and the slabs in slice / chunk order.  The slice and chunk counts depend
+ * on one view's (K, C, h, w, D) only, never on B or the environment (FS_CV_SG_CHUNKS and FS_CV_BWD_ATOMIC are ignored): a
+ * view's d_cur_feats / d_src_feats are the same bits alone or inside any batch, and the MLP gradients of B views are the
+ * fp32 sum, in view order, of each view's own.
+ * Arguments: those of fs_cost_volume_backward_train; `saved` may be NULL (the forward is recomputed, as
+ * fs_cost_volume_backward does); workspace = fs_cost_volume_backward_workspace_bytes(B, K, C, h, w, D) bytes;
+ * det_scratch = fs_cost_volume_backward_det_bytes(B, K, C, h, w, D) bytes.  NULL required pointers or non-positive sizes:
+ * FS_ERR_INVALID_ARG; then K > 16 or per-pixel planes (plane_stride_pix != 0), which only the atomic scatter form handles,
+ * and C other than 48 / 16: FS_ERR_UNSUPPORTED. */
+size_t fs_cost_volume_backward_det_bytes(int32_t B, int32_t K, int32_t C, int32_t h, int32_t w, int32_t D);
+int fs_cost_volume_backward_det(int32_t B, int32_t K, int32_t C, int32_t h, int32_t w, int32_t D,
+                                const float* cur_feats, const float* src_feats,
+                                const float* src_extrinsics, const float* src_Ks, const float* cur_invK,
+                                const float* planes, int64_t plane_stride_b, int64_t plane_stride_d,
+                                int64_t plane_stride_pix, const float* w1, const float* b1,
+                                const float* w2, const float* b2, const float* w3, const float* grad_out,
+                                void* workspace, const void* saved, float* d_cur_feats, float* d_src_feats,
+                                float* d_w1, float* d_b1, float* d_w2, float* d_b2, float* d_w3, float* d_b3,
+                                void* det_scratch, void* stream);
+
 /* ------------------------------------------------------------------------------------ *
  * Pixel-wise Triplet Fusion: matching step                                              *
  * ------------------------------------------------------------------------------------ */
@@ -526,6 +550,14 @@ int fs_depth_tail_backward(int32_t B, int32_t D, int32_t h2, int32_t w2, const f
                            const int32_t* argmax, const float* g_coarse, const float* g_depth,
                            const float* g_map, const float* g_weights, float* scratch_gE,
                            float* scratch_gprob, float* g_logits, void* stream);
+/* Deterministic form (ABI 9), bitwise repeatable for every D: the four wavefronts of a workgroup add their fine pixels'
+ * terms into the LDS gradient one wavefront after the other instead of with LDS float atomics.  The arguments of
+ * fs_depth_tail_backward without the two unused scratch pointers; same checks. */
+int fs_depth_tail_backward_det(int32_t B, int32_t D, int32_t h2, int32_t w2, const float* logits,
+                               const float* candidates, int32_t log_planes, const float* stats,
+                               const float* coarse, const float* depth, const float* depth_map,
+                               const int32_t* argmax, const float* g_coarse, const float* g_depth,
+                               const float* g_map, const float* g_weights, float* g_logits, void* stream);
 
 /* Backward of v views of ONE Gaussian set in one host call (counterpart of fs_raster_forward_views; same packed
  * per-view arrays and buffer strides[0..2] = geom / binning / image; counters [v,2] | NULL as in fs_raster_backward).
@@ -592,6 +624,23 @@ int fs_ptf_write_state_backward(int32_t n_keep, int32_t n_fuse, int32_t n_app, c
 int fs_ptf_gru_inputs_backward(int32_t n_fuse, const int64_t* fuse_idx, const int64_t* fuse_pix, const float* R,
                                const float* O, const float* rho_i, const float* om_i, const float* dcat, float* g_G,
                                float* g_R, float* g_O, float* g_lat_i, float* g_rho_i, float* g_om_i, void* stream);
+/* Deterministic forms of the two (ABI 9), bitwise repeatable: where several fused rows share a pixel of the view (exact
+ * z-buffer ties), their terms are added to that pixel in ascending fuse-row order, after whatever the pixel already holds.
+ * A pixel -> rows index of the fuse list is built with integer atomics only; a row alone on its pixel adds directly.
+ * Arguments: those of the default forms, then P = the view's pixel count (every fuse_pix < P) and scratch =
+ * fs_ptf_backward_det_bytes(n_fuse, P) bytes (0 for n_fuse < 0 or P <= 0).  Same checks as the default forms, and with
+ * n_fuse > 0 a NULL scratch or P <= 0 is FS_ERR_INVALID_ARG. */
+size_t fs_ptf_backward_det_bytes(int32_t n_fuse, int32_t P);
+int fs_ptf_write_state_backward_det(int32_t n_keep, int32_t n_fuse, int32_t n_app, const int64_t* keep_idx,
+                                    const int64_t* fuse_idx, const int64_t* fuse_pix, const int64_t* append_pix,
+                                    const float* X, const float* R, const float* E, const float* D, const float* x_i,
+                                    const float* rho_i, const float* d_i, const float* E_i, float* const* g_out,
+                                    float* const* g_in, float* g_lat_i, float* g_x_i, float* g_rho_i, float* g_om_i,
+                                    float* g_d_i, int32_t P, void* scratch, void* stream);
+int fs_ptf_gru_inputs_backward_det(int32_t n_fuse, const int64_t* fuse_idx, const int64_t* fuse_pix, const float* R,
+                                   const float* O, const float* rho_i, const float* om_i, const float* dcat, float* g_G,
+                                   float* g_R, float* g_O, float* g_lat_i, float* g_rho_i, float* g_om_i, int32_t P,
+                                   void* scratch, void* stream);
 
 /* ------------------------------------------------------------------------------------ *
  * Evaluation metrics (metrics.py:11-52, model_wrapper.py:74-110)                        *
