@@ -1,8 +1,8 @@
 #!/usr/bin/env python
-"""bench.py -- rendered views/sec of the MI355X rasterizer on BASELINE.json's metric config, plus (N=1) the
+"""bench.py -- rendered views/sec of the MI355X rasterizer on BASELINE.json's metric config; with `--full`, also (N=1) the
 other rows of the hot path under the same clock.
 
-  python bench.py [--gpus N --steps K --warmup W]            (N=1)
+  python bench.py [--gpus N --steps K --warmup W] [--full]            (N=1)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W    (N>1, one rank per GPU)
 
@@ -20,17 +20,22 @@ the gradients of the Gaussian parameters) as DIR/<name>.npy in float32, rank 0's
 run with the same arguments can be compared array for array.  Above 64 MB in all, every array is replaced by the same fixed,
 seeded sample of its flattened elements (`dump_outputs` in the result line records shapes and sample sizes).
 
-Rank 0 prints ONE JSON line.  Top level = the headline metric (forward rendering, config 3's size) with
-`roofline` (render kernel, HIP-event timed inside the timed region through the library's fs_profile_* hooks),
-`cpu_baseline` (the CPU oracle, OpenMP, on whole views of the same workload) and `parity`.  At N=1 the same line
-carries sub-objects measured in the same run, each with its own roofline / cpu_baseline / parity:
+A plain run does only what the headline figure needs: set-up, warm-up, the timed region, the dump, and rank 0 prints ONE
+JSON line -- the headline metric (forward rendering, config 3's size) with `roofline` (render kernel, HIP-event timed inside
+the timed region through the library's fs_profile_* hooks) and `raster_buffers`.
+
+`--full` adds every measurement that takes runs of its own and prints two lines: the full sectioned object, then the compact
+object `headline()` builds from it (the driver parses the LAST line).  On the headline: `cpu_baseline` (the CPU oracle,
+OpenMP, on whole views of the same workload), `parity`, `hipgraph_replay`, `kernel_ms_per_view` and the isolated and
+VALU-issue rooflines (extra untimed steps), and at N>1 `multi_gpu` (per-rank diagnostics, extra untimed steps).  At N=1 the
+same line carries sub-objects measured in the same run, each with its own roofline / cpu_baseline / parity:
   "train"        fwd+bwd training step at config 3 (roofline: render_bwd kernel)
   "c2"           config 2 (640x480, 300 k Gaussians, forward)
   "cost_volume"  plane-sweep cost volume: native 96x128 K=1 and config-3 scale 242x324 K=2 (roofline: fp32 MFMA)
   "c3_fp16_sh"   the headline workload with the SH coefficients stored in fp16 (BASELINE config 5's storage option)
   "ptf"          Pixel-wise Triplet Fusion folds: 2, 10 and 30 views at 384x512, 3 views at 968x1296 (roofline: HBM)
   "encoder_tail" the depth-regression tail of the DepthDecoder and the latent -> Gaussian head at the native size (roofline: HBM)
-(`--sections raster` restricts the run to the top-level metric.)
+(`--full --sections raster` keeps the headline's own additions and runs no sub-object.)
 """
 from __future__ import annotations
 
@@ -58,8 +63,12 @@ def parse():
                     help="c3_968x1296_1M (metric config) | c2_640x480_300k | c1_256x256_plumbing")
     ap.add_argument("--mode", default="fwd", choices=["fwd", "train"],
                     help="top-level measurement. fwd: forward rendering (the metric); train: fwd + bwd (+ grad exchange)")
-    ap.add_argument("--sections", default="all",
-                    help="N=1 only: comma list of extra sub-objects (train,c2,closeup,c5,cost_volume,ptf,encoder_tail,c3_step), 'all', or 'raster' for none")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline: the sub-objects, CPU baseline and parity, hipGraph "
+                         "replay, per-stage breakdown, N>1 diagnostics (see the module docstring)")
+    ap.add_argument("--sections", default=None,
+                    help="--full, N=1 only: comma list of extra sub-objects (train,c2,closeup,c5,cost_volume,ptf,encoder_tail,c3_step), "
+                         "'all' (the default with --full), or 'raster' for none")
     ap.add_argument("--grad-exchange", default="reduce_scatter", choices=["reduce_scatter", "all_reduce", "chunked"],
                     help="N>1 train mode: how the per-Gaussian gradients of the view shards are summed.  chunked = the reduce-scatter "
                          "issued chunk by chunk of the rows from inside the backward (--grad-chunks), overlapping the per-Gaussian pass")
@@ -82,10 +91,15 @@ def parse():
                     help="N>1: element type of the gathered images.  fp32 (default) = what the decoder returns; fp16 / uint8 "
                          "(clamped to [0,1], x255, rounded) halve / quarter the bytes every GPU receives over its 7 xGMI links "
                          "(241 MB per 16-view step and rank in fp32) for evaluation runs that end in 8-bit images anyway")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines and parity checks")
     ap.add_argument("--no-profile", action="store_true", help="do not bracket kernels with HIP events")
-    ap.add_argument("--no-graph", action="store_true", help="skip the hipGraph capture / replay measurement")
-    return ap.parse_args()
+    ap.add_argument("--no-graph", action="store_true", help="--full: skip the hipGraph capture / replay measurement")
+    args = ap.parse_args()
+    if args.sections is None:
+        args.sections = "all" if args.full else "raster"
+    elif args.sections != "raster" and not args.full:
+        ap.error("--sections selects sub-objects of --full")
+    return args
 
 
 class Ctx:
@@ -260,6 +274,7 @@ def bench_raster(cx: Ctx, workload: str, mode: str, views: int, steps: int, warm
     if profile:
         _lib.profile_enable(False)
         stages = _lib.profile_collect()
+    if profile and args.full:
         # per-stage breakdown from two extra, untimed steps with every stage bracketed
         from freesplat_amd import rasterizer as _R
         streams, _R.NUM_STREAMS = _R.NUM_STREAMS, 1      # one stream: launches back to back, durations not shared
@@ -276,7 +291,7 @@ def bench_raster(cx: Ctx, workload: str, mode: str, views: int, steps: int, warm
     # N > 1 diagnostics: a few extra untimed steps with the render, the all-gather and the render
     # stream's wait for the gather (the EXPOSED, non-overlapped part) event-timed separately on every rank
     multi = None
-    if gather is not None:
+    if gather is not None and args.full:
         gather.timing = True
         spans = []
         for _ in range(4):
@@ -304,7 +319,7 @@ def bench_raster(cx: Ctx, workload: str, mode: str, views: int, steps: int, warm
                          "and that wait alone = the part of the gather the rendering did not hide",
                  "gather_bytes_per_rank_per_step": int(n_total_views * H * W * (4 if args.gather_depth else 3)
                                                        * {"fp32": 4, "fp16": 2, "uint8": 1}[args.gather_dtype])}
-    if exchange is not None:
+    if exchange is not None and args.full:
         # training mode: the gradient exchange runs on the render stream after the backward -- all of it is exposed
         diag_events, spans = [], []
         for _ in range(3):
@@ -324,7 +339,7 @@ def bench_raster(cx: Ctx, workload: str, mode: str, views: int, steps: int, warm
                          f"and the {args.grad_exchange} of the Gaussian gradients alone (on the render stream: none of it is hidden)",
                  "exchange_bytes_per_rank_per_step": int(N * 37 * 4)}
     graph_views_per_s = None
-    if world == 1 and not cx.dist_on and not train and not args.no_graph:
+    if world == 1 and not cx.dist_on and not train and args.full and not args.no_graph:
         # the same step recorded once into a hipGraph (the C ABI never allocates or syncs: framing + 5 kernels per view
         # over two forked streams capture as they are) and replayed: what is left when the host-side launch train is
         # taken out of the loop
@@ -421,12 +436,13 @@ def bench_raster(cx: Ctx, workload: str, mode: str, views: int, steps: int, warm
                            "traffic_source": traffic_src,
                            "algorithmic_bytes_per_launch": alg, "avg_launch_ms": per * 1e3,
                            "launches": cnt}
-        out["kernel_ms_per_view"] = {k: v[0] / max(v[1], 1) for k, v in breakdown.items() if v[1]}
-        out["kernel_ms_per_view_note"] = ("2 extra untimed single-stream steps with every stage event-timed (isolated "
-                                          "durations); roofline.avg_launch_ms is from the timed region, where the "
-                                          "launches of adjacent views overlap on config.raster_streams streams")
         iso = breakdown.get(dominant, (0.0, 0))
-        out["roofline"]["isolated_launch_ms"] = iso[0] / max(iso[1], 1)
+        if breakdown:
+            out["kernel_ms_per_view"] = {k: v[0] / max(v[1], 1) for k, v in breakdown.items() if v[1]}
+            out["kernel_ms_per_view_note"] = ("2 extra untimed single-stream steps with every stage event-timed (isolated "
+                                              "durations); roofline.avg_launch_ms is from the timed region, where the "
+                                              "launches of adjacent views overlap on config.raster_streams streams")
+            out["roofline"]["isolated_launch_ms"] = iso[0] / max(iso[1], 1)
         # the three numbers one could mean by "fraction of the HBM roofline", named:
         #   frac_overlapped    = `frac`: algorithmic bytes / AVERAGE launch duration inside the timed region, where the launches
         #                        of adjacent views run concurrently on the raster streams (each is slowed by its neighbour)
@@ -457,7 +473,7 @@ def bench_raster(cx: Ctx, workload: str, mode: str, views: int, steps: int, warm
                                     "note": "frac = microbenchmark-priced issue cycles / available SIMD cycles; hw_valu_busy_frac = "
                                             "SQ_ACTIVE_INST_VALU x 4 / (1024 x GRBM_GUI_ACTIVE per XCD): the wave-cycles spent IN "
                                             "VALU instructions, which at 6 wavefronts per SIMD includes their latency"}
-        ksum = sum(out["kernel_ms_per_view"].values())
+        ksum = sum(out.get("kernel_ms_per_view", {}).values())
         if ksum > 0:   # the whole pipeline of one view against the same algorithmic bytes
             out["roofline"]["pipeline_frac_isolated"] = (alg_fwd + (alg_bwd if train else 0)) / (ksum * 1e-3) / 8e12
     if world == 1 and cpu_baseline:
@@ -763,7 +779,7 @@ def main():
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(respawn_under_launcher(args))
     cx = Ctx(args)
-    cpu = not args.no_cpu_baseline
+    cpu = args.full and not args.no_cpu_baseline
     out = bench_raster(cx, args.workload, args.mode, args.views, args.steps, args.warmup, cpu, dump_dir=args.dump_outputs)
     sections = []
     if cx.world == 1 and args.sections != "raster":
@@ -849,7 +865,10 @@ def main():
                                                                        train=False, num_views=9, workload="c5_eval_step_hotpath",
                                                                        sh_fp16=True))
     if cx.rank == 0:
-        emit(out)
+        if args.full:
+            emit(out)
+        else:
+            print(json.dumps(out), flush=True)
     if cx.dist_on:
         dist.destroy_process_group()
 

@@ -9,7 +9,7 @@ for tag, lib in variants * 2:
     env = dict(os.environ)
     if lib:
         env["FREESPLAT_LIB"] = os.path.join(os.getcwd(), lib)
-    res = subprocess.run([sys.executable, "bench.py", "--sections", "raster", "--no-cpu-baseline", "--no-graph"] + mode, env=env, capture_output=True, text=True)
+    res = subprocess.run([sys.executable, "bench.py", "--full", "--sections", "raster", "--no-cpu-baseline", "--no-graph"] + mode, env=env, capture_output=True, text=True)
     out = res.stdout
     if res.returncode != 0 or not [l for l in out.splitlines() if l.startswith("{")]:
         print(tag, "FAILED rc", res.returncode, res.stderr[-1500:], flush=True)

@@ -13,7 +13,7 @@ for tag, envs in variants * int(os.environ.get("AB_REPEAT", "2")):
     env = dict(os.environ)
     for k, v in envs.items():
         env[k] = os.path.join(os.getcwd(), v) if k == "FREESPLAT_LIB" else v
-    res = subprocess.run([sys.executable, "bench.py", "--sections", "raster", "--no-cpu-baseline", "--no-graph"] + mode, env=env, capture_output=True, text=True)
+    res = subprocess.run([sys.executable, "bench.py", "--full", "--sections", "raster", "--no-cpu-baseline", "--no-graph"] + mode, env=env, capture_output=True, text=True)
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
     if res.returncode != 0 or not lines:
         print(tag, "FAILED rc", res.returncode, res.stderr[-1500:], flush=True)

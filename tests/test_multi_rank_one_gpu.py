@@ -44,7 +44,7 @@ def test_sharded_decoder_and_cost_volume_two_ranks(hip_device):
 def test_bench_two_ranks_chunked_gradient_exchange(hip_device):
     """bench.py --gpus 2 --mode train --grad-exchange chunked: the per-Gaussian backward pass runs in row chunks
     (fs_raster_backward_views_rows) with one reduce-scatter per chunk on a side stream; same JSON contract as the other exchanges."""
-    out = _torchrun([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--views", "3",
+    out = _torchrun([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--views", "3", "--full",
                      "--workload", "c1_256x256_plumbing", "--mode", "train", "--grad-exchange", "chunked", "--grad-chunks", "3"])
     lines = [l for l in out.splitlines() if l.startswith("{")]
     d = json.loads(lines[-2])
@@ -58,7 +58,7 @@ def test_bench_two_ranks_runs_the_sharded_branch(hip_device, mode):
     """bench.py --gpus 2 end to end (small workload): NCCL-free init, view sharding, AsyncViewGather on a side stream
     (fwd) / reduce-scatter gradient exchange (train), max-over-ranks timing, one JSON line from rank 0."""
     out = _torchrun([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--views", "3",
-                     "--workload", "c1_256x256_plumbing", "--mode", mode])
+                     "--workload", "c1_256x256_plumbing", "--mode", mode, "--full"])
     lines = [l for l in out.splitlines() if l.startswith("{")]
     d, compact = json.loads(lines[-2]), json.loads(lines[-1])      # the full line, then the compact one the driver parses
     assert len(lines[-1]) <= 4096 and compact["value"] == pytest.approx(d["value"], rel=1e-4) and compact["n_gpus"] == 2
@@ -80,13 +80,14 @@ def test_bench_two_ranks_runs_the_sharded_branch(hip_device, mode):
 
 def test_bench_gpus_2_launches_itself(hip_device):
     """`python bench.py --gpus 2` with no launcher environment (the driver's command shape) re-launches itself under
-    torch.distributed.run with two ranks: same two lines from rank 0, exit status 0."""
+    torch.distributed.run with two ranks: exit status 0 and, the run being plain, ONE JSON line from rank 0
+    without the `--full` diagnostics."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(FS_DIST_BACKEND="gloo", FS_SHARE_GPU="1", OMP_NUM_THREADS="8")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--views", "2",
                         "--workload", "c1_256x256_plumbing"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-3000:] + "\n" + p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
-    compact = json.loads(lines[-1])
-    assert compact["n_gpus"] == 2 and compact["value"] > 0 and compact["config"]["parallelism"].startswith("view-sharded x2")
-    assert len(lines[-1]) <= 4096 and json.loads(lines[-2])["n_gpus"] == 2
+    d = json.loads(lines[-1])
+    assert d["n_gpus"] == 2 and d["value"] > 0 and d["config"]["parallelism"].startswith("view-sharded x2")
+    assert len(lines) == 1 and len(lines[-1]) <= 4096 and "multi_gpu" not in d
