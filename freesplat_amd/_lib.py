@@ -76,6 +76,10 @@ SIGNATURES = {
     "fs_unproject_backward": (C.c_int, [C.c_int32] * 3 + [_VP] * 5),
     "fs_gaussian_head_forward": (C.c_int, [C.c_int64] + [_VP] * 4 + [C.c_int64, _VP, C.c_float, C.c_float] + [_VP] * 5),
     "fs_gaussian_head_backward": (C.c_int, [C.c_int64] + [_VP] * 4 + [C.c_int64, _VP, C.c_float, C.c_float] + [_VP] * 8),
+    "fs_gaussian_head_forward_sh": (C.c_int, [C.c_int64, C.c_int32] + [_VP] * 4 + [C.c_int64, _VP, C.c_float, C.c_float]
+                                    + [_VP] * 5),
+    "fs_gaussian_head_backward_sh": (C.c_int, [C.c_int64, C.c_int32] + [_VP] * 4 + [C.c_int64, _VP, C.c_float, C.c_float]
+                                     + [_VP] * 8),
     "fs_latents_pack_forward": (C.c_int, [C.c_int32, C.c_int64, C.c_int32] + [_VP] * 5),
     "fs_latents_pack_backward": (C.c_int, [C.c_int32, C.c_int64, C.c_int32] + [_VP] * 5),
     "fs_ptf_scratch_bytes": (C.c_size_t, [C.c_int32] * 3),

@@ -4,10 +4,11 @@
 //       (src/model/encoder/common/gaussian_adapter.py:36-79, 174-188): per-pixel depth -> world xyz.
 //       The reference runs Python loops over batch and views with ~10 small kernels each.
 //  a14  GaussianAdapter.forward(fusion=False, coords=...) (gaussian_adapter.py:151-172, 191-201) with
-//       quaternion_to_matrix / build_covariance (common/gaussians.py:8-44): 34 raw channels + depth +
-//       blended extrinsics -> world covariance, masked SH, scales, unit quaternion (xyzw).
-// Both are streaming per-element kernels (HBM-bound: a14 moves 34+1+16 floats in and 43 out per
-// Gaussian); forward AND backward are provided so the ops stay differentiable.
+//       quaternion_to_matrix / build_covariance (common/gaussians.py:8-44): 7 + 3 d_sh raw channels + depth +
+//       blended extrinsics -> world covariance, masked SH, scales, unit quaternion (xyzw); d_sh = (sh_degree + 1)^2
+//       for sh_degree 0 - 3 (the degrees the rasterizer evaluates), one instantiation each.
+// Both are streaming per-element kernels (HBM-bound: a14 moves (7+3 d_sh)+1+16 floats in and 3 d_sh+16 out per
+// Gaussian, 34+1+16 / 43 at sh_degree 2); forward AND backward are provided so the ops stay differentiable.
 #include "fs_common.h"
 
 namespace fs {
@@ -110,7 +111,7 @@ __device__ __forceinline__ void mat3_mul_at(const float* X, const float* Y, floa
 // The [M, PER] arrays of this step are arrays of structures: thread m touching raw[m * 34 + c] makes every load
 // instruction of a wavefront span 64 x 136 bytes (2.5 - 3.5 TB/s of the algorithmic bytes in rounds 2 - 3).  A workgroup's 256
 // consecutive rows are ONE contiguous slab, so they cross HBM as 16-byte coalesced accesses and meet their threads in LDS
-// (row strides 34 / 27 / 9 words: at most 2-way bank conflicts).
+// (sh_degree 2: row strides 34 / 27 / 9 words, at most 2-way bank conflicts).
 // One 4-float row of a per-Gaussian 4x4: a 16-byte access when the array is 16-byte aligned (the rows are 16-byte multiples
 // apart, so the base decides), four scalar ones otherwise -- in the inference fold the extrinsics are a view at float offset
 // rows * 69 inside one buffer, 4-byte aligned when h * w is not a multiple of 4.
@@ -125,32 +126,43 @@ __device__ __forceinline__ void store_row4(float* __restrict__ p, float4 v)
     p[0] = v.x; p[1] = v.y; p[2] = v.z; p[3] = v.w;
 }
 
-template <int PER>
+// (NT = threads of the workgroup)
+template <int PER, int NT = 256>
 __device__ __forceinline__ void rows_in(float* __restrict__ lds, const float* __restrict__ src, long long m0, int cnt)
 {
     const float* g = src + m0 * PER;
     const int total = cnt * PER;
     if ((reinterpret_cast<uintptr_t>(g) & 15) == 0) {
-        for (int k = 4 * threadIdx.x; k + 3 < total; k += 1024) *(float4*)(lds + k) = *(const float4*)(g + k);
-        for (int k = (total & ~3) + threadIdx.x; k < total; k += 256) lds[k] = g[k];
+        for (int k = 4 * threadIdx.x; k + 3 < total; k += 4 * NT) *(float4*)(lds + k) = *(const float4*)(g + k);
+        for (int k = (total & ~3) + threadIdx.x; k < total; k += NT) lds[k] = g[k];
     } else {
-        for (int k = threadIdx.x; k < total; k += 256) lds[k] = g[k];
+        for (int k = threadIdx.x; k < total; k += NT) lds[k] = g[k];
     }
 }
-template <int PER>
+template <int PER, int NT = 256>
 __device__ __forceinline__ void rows_out(float* __restrict__ dst, const float* __restrict__ lds, long long m0, int cnt)
 {
     float* g = dst + m0 * PER;
     const int total = cnt * PER;
     if ((reinterpret_cast<uintptr_t>(g) & 15) == 0) {
-        for (int k = 4 * threadIdx.x; k + 3 < total; k += 1024) *(float4*)(g + k) = *(const float4*)(lds + k);
-        for (int k = (total & ~3) + threadIdx.x; k < total; k += 256) g[k] = lds[k];
+        for (int k = 4 * threadIdx.x; k + 3 < total; k += 4 * NT) *(float4*)(g + k) = *(const float4*)(lds + k);
+        for (int k = (total & ~3) + threadIdx.x; k < total; k += NT) g[k] = lds[k];
     } else {
-        for (int k = threadIdx.x; k < total; k += 256) g[k] = lds[k];
+        for (int k = threadIdx.x; k < total; k += NT) g[k] = lds[k];
     }
 }
 
-__global__ __launch_bounds__(256) void head_fwd_kernel(long long M, const float* __restrict__ raw,
+// Rows (= threads) per workgroup of the head kernels.  The LDS staging holds max(in, out) floats per row: 19 / 28 / 43 / 64
+// forward and 10 / 19 / 34 / 55 backward at d_sh 1 / 4 / 9 / 16.  At d_sh = 16 a 256-row workgroup would stage 64 KiB
+// (forward) / 55 KiB (backward), so only two fit a CU's 160 KiB: 512 rows in flight per CU.  128-row workgroups stage 32 /
+// 27.5 KiB, five fit, 640 rows in flight, with the same code (staging in two halves would keep 256 rows but add a pass and a
+// barrier, and the backward's 55-float input rows would still allow only two workgroups).  d_sh 1 / 4 / 9 keep 256 rows
+// (at most 28 / 19 KiB forward / backward below d_sh 9; 43 / 34 KiB at d_sh 9, unchanged).
+template <int D_SH>
+constexpr int kHeadRows = D_SH == 16 ? 128 : 256;
+
+template <int D_SH>
+__global__ __launch_bounds__(kHeadRows<D_SH>) void head_fwd_kernel(long long M, const float* __restrict__ raw,
                                                        const float* __restrict__ depths,
                                                        const float* __restrict__ E,
                                                        const float* __restrict__ mult, long long mult_stride,
@@ -158,16 +170,17 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(long long M, const float*
                                                        float* __restrict__ cov, float* __restrict__ sh,
                                                        float* __restrict__ scales, float* __restrict__ rot)
 {
-    __shared__ float s_rows[256 * 43];          // in: 34 raw floats per row; out: sh 27 | cov 9 | scales 3 | rotation 4
-    const long long m0 = (long long)blockIdx.x * 256;
-    const int cnt = (int)min((long long)256, M - m0), t = threadIdx.x;
+    constexpr int NT = kHeadRows<D_SH>, NR = 7 + 3 * D_SH, NS = 3 * D_SH, NO = NS + 16;
+    __shared__ float s_rows[NT * (NR > NO ? NR : NO)];   // in: NR raw floats per row; out: sh NS | cov 9 | scales 3 | rotation 4
+    const long long m0 = (long long)blockIdx.x * NT;
+    const int cnt = (int)min((long long)NT, M - m0), t = threadIdx.x;
     const long long m = m0 + t;
     const bool live = t < cnt;
-    rows_in<34>(s_rows, raw, m0, cnt);
+    rows_in<NR, NT>(s_rows, raw, m0, cnt);
     __syncthreads();
-    float rw[34];
+    float rw[NR];
 #pragma unroll
-    for (int c = 0; c < 34; ++c) rw[c] = live ? s_rows[t * 34 + c] : 1.0f;
+    for (int c = 0; c < NR; ++c) rw[c] = live ? s_rows[t * NR + c] : 1.0f;
     __syncthreads();                             // (the outputs below reuse the rows' LDS)
     if (live) {
         HeadFwd f;
@@ -180,12 +193,12 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(long long M, const float*
         }
         mat3_mul(Rc, f.A, B);        // c2w @ cov
         mat3_mul_bt(B, Rc, S);       // ... @ c2w^T                 gaussian_adapter.py:171-172
-        float* o_sh = s_rows + t * 27;
-        float* o_cov = s_rows + 256 * 27 + t * 9;
-        float* o_sc = s_rows + 256 * 36 + t * 3;
-        float* o_rot = s_rows + 256 * 39 + t * 4;
+        float* o_sh = s_rows + t * NS;
+        float* o_cov = s_rows + NT * NS + t * 9;
+        float* o_sc = s_rows + NT * (NS + 9) + t * 3;
+        float* o_rot = s_rows + NT * (NS + 12) + t * 4;
 #pragma unroll
-        for (int c = 0; c < 27; ++c) o_sh[c] = rw[7 + c] * sh_mask[c % 9];   // "(xyz d_sh)" * mask :166-167
+        for (int c = 0; c < NS; ++c) o_sh[c] = rw[7 + c] * sh_mask[c % D_SH];   // "(xyz d_sh)" * mask :166-167
 #pragma unroll
         for (int c = 0; c < 9; ++c) o_cov[c] = S[c];
 #pragma unroll
@@ -194,13 +207,14 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(long long M, const float*
         for (int c = 0; c < 4; ++c) o_rot[c] = f.q[c];
     }
     __syncthreads();
-    rows_out<27>(sh, s_rows, m0, cnt);
-    rows_out<9>(cov, s_rows + 256 * 27, m0, cnt);
-    rows_out<3>(scales, s_rows + 256 * 36, m0, cnt);
-    rows_out<4>(rot, s_rows + 256 * 39, m0, cnt);
+    rows_out<NS, NT>(sh, s_rows, m0, cnt);
+    rows_out<9, NT>(cov, s_rows + NT * NS, m0, cnt);
+    rows_out<3, NT>(scales, s_rows + NT * (NS + 9), m0, cnt);
+    rows_out<4, NT>(rot, s_rows + NT * (NS + 12), m0, cnt);
 }
 
-__global__ __launch_bounds__(256) void head_bwd_kernel(long long M, const float* __restrict__ raw,
+template <int D_SH>
+__global__ __launch_bounds__(kHeadRows<D_SH>) void head_bwd_kernel(long long M, const float* __restrict__ raw,
                                                        const float* __restrict__ depths,
                                                        const float* __restrict__ E,
                                                        const float* __restrict__ mult, long long mult_stride,
@@ -211,27 +225,28 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(long long M, const float*
                                                        const float* __restrict__ g_rot, float* __restrict__ g_raw,
                                                        float* __restrict__ g_depths, float* __restrict__ g_E)
 {
-    __shared__ float s_rows[256 * 34];          // raw rows in, then g_sh rows in, then g_raw rows out
-    const long long m0 = (long long)blockIdx.x * 256;
-    const int cnt = (int)min((long long)256, M - m0), t = threadIdx.x;
+    constexpr int NT = kHeadRows<D_SH>, NR = 7 + 3 * D_SH, NS = 3 * D_SH;
+    __shared__ float s_rows[NT * NR];           // raw rows in, then g_sh rows in, then g_raw rows out
+    const long long m0 = (long long)blockIdx.x * NT;
+    const int cnt = (int)min((long long)NT, M - m0), t = threadIdx.x;
     const bool live = t < cnt;
     const long long m = live ? m0 + t : m0;     // (a dead thread works on the workgroup's first row and stores nothing)
-    rows_in<34>(s_rows, raw, m0, cnt);
+    rows_in<NR, NT>(s_rows, raw, m0, cnt);
     __syncthreads();
-    float rw[34];
+    float rw[NR];
 #pragma unroll
-    for (int c = 0; c < 34; ++c) rw[c] = s_rows[(live ? t : 0) * 34 + c];
+    for (int c = 0; c < NR; ++c) rw[c] = s_rows[(live ? t : 0) * NR + c];
     __syncthreads();
-    float gsh[27];
+    float gsh[NS];
     if (g_sh) {
-        rows_in<27>(s_rows, g_sh, m0, cnt);
+        rows_in<NS, NT>(s_rows, g_sh, m0, cnt);
         __syncthreads();
 #pragma unroll
-        for (int c = 0; c < 27; ++c) gsh[c] = s_rows[(live ? t : 0) * 27 + c];
+        for (int c = 0; c < NS; ++c) gsh[c] = s_rows[(live ? t : 0) * NS + c];
         __syncthreads();
     } else {
 #pragma unroll
-        for (int c = 0; c < 27; ++c) gsh[c] = 0.0f;
+        for (int c = 0; c < NS; ++c) gsh[c] = 0.0f;
     }
     const float depth = depths[m], mu = mult[m * mult_stride];
     HeadFwd f;
@@ -295,7 +310,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(long long M, const float*
 #pragma unroll
     for (int a = 0; a < 4; ++a) dot += dq[a] * rw[3 + a];
     const float cq = f.nq > 0.0f ? dot / (D * D * f.nq) : 0.0f;
-    float gr[34];
+    float gr[NR];
 #pragma unroll
     for (int a = 0; a < 4; ++a) gr[3 + a] = dq[a] / D - cq * rw[3 + a];
     float gdepth = 0.0f;
@@ -305,10 +320,10 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(long long M, const float*
         gdepth += dsc[b] * (smin + (smax - smin) * f.sig[b]) * mu;
     }
 #pragma unroll
-    for (int c = 0; c < 27; ++c) gr[7 + c] = gsh[c] * sh_mask[c % 9];
+    for (int c = 0; c < NS; ++c) gr[7 + c] = gsh[c] * sh_mask[c % D_SH];
     if (live) {
 #pragma unroll
-        for (int c = 0; c < 34; ++c) s_rows[t * 34 + c] = gr[c];
+        for (int c = 0; c < NR; ++c) s_rows[t * NR + c] = gr[c];
         g_depths[m] = gdepth;
 #pragma unroll
         for (int a = 0; a < 4; ++a)
@@ -316,8 +331,31 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(long long M, const float*
                                                    : make_float4(0.0f, 0.0f, 0.0f, 0.0f));
     }
     __syncthreads();
-    rows_out<34>(g_raw, s_rows, m0, cnt);
+    rows_out<NR, NT>(g_raw, s_rows, m0, cnt);
 }
+
+template <int D_SH>
+void launch_head_fwd(long long M, const float* raw, const float* depths, const float* E, const float* mult,
+                     long long mult_stride, const float* sh_mask, float smin, float smax, float* cov, float* sh,
+                     float* scales, float* rot, hipStream_t st)
+{
+    constexpr int NT = kHeadRows<D_SH>;
+    hipLaunchKernelGGL(head_fwd_kernel<D_SH>, dim3((unsigned)((M + NT - 1) / NT)), dim3(NT), 0, st, M, raw, depths, E, mult,
+                       mult_stride, sh_mask, smin, smax, cov, sh, scales, rot);
+}
+
+template <int D_SH>
+void launch_head_bwd(long long M, const float* raw, const float* depths, const float* E, const float* mult,
+                     long long mult_stride, const float* sh_mask, float smin, float smax, const float* g_cov,
+                     const float* g_sh, const float* g_scales, const float* g_rot, float* g_raw, float* g_depths,
+                     float* g_E, hipStream_t st)
+{
+    constexpr int NT = kHeadRows<D_SH>;
+    hipLaunchKernelGGL(head_bwd_kernel<D_SH>, dim3((unsigned)((M + NT - 1) / NT)), dim3(NT), 0, st, M, raw, depths, E, mult,
+                       mult_stride, sh_mask, smin, smax, g_cov, g_sh, g_scales, g_rot, g_raw, g_depths, g_E);
+}
+
+inline bool head_d_sh_supported(int d_sh) { return d_sh == 1 || d_sh == 4 || d_sh == 9 || d_sh == 16; }
 
 
 // ------------------------------------------------------------------ per-pixel latents: head + skip, channel-major -> pixel-major
@@ -415,20 +453,64 @@ FS_API int fs_unproject_backward(int32_t V, int32_t h, int32_t w, const float* e
     return FS_OK;
 }
 
+FS_API int fs_gaussian_head_forward_sh(int64_t M, int32_t d_sh, const float* raw, const float* depths,
+                                       const float* extrinsics, const float* multiplier, int64_t mult_stride,
+                                       const float* sh_mask, float scale_min, float scale_max, float* cov,
+                                       float* harmonics, float* scales, float* rotations, void* stream_)
+{
+    if (M < 0 || !multiplier || !sh_mask) return FS_ERR_INVALID_ARG;
+    if (!head_d_sh_supported(d_sh)) return FS_ERR_UNSUPPORTED;
+    if (M == 0) return FS_OK;
+    if (!raw || !depths || !extrinsics || !cov || !harmonics || !scales || !rotations) return FS_ERR_INVALID_ARG;
+    ScopedStage prof_(kStEncoderTail, (hipStream_t)stream_);
+    const hipStream_t st = (hipStream_t)stream_;
+#define FS_HEAD_FWD(D) launch_head_fwd<D>((long long)M, raw, depths, extrinsics, multiplier, (long long)mult_stride, sh_mask, \
+                                          scale_min, scale_max, cov, harmonics, scales, rotations, st)
+    switch (d_sh) {
+        case 1: FS_HEAD_FWD(1); break;
+        case 4: FS_HEAD_FWD(4); break;
+        case 9: FS_HEAD_FWD(9); break;
+        default: FS_HEAD_FWD(16); break;
+    }
+#undef FS_HEAD_FWD
+    FS_CHECK_LAUNCH("gaussian_head_forward");
+    return FS_OK;
+}
+
+FS_API int fs_gaussian_head_backward_sh(int64_t M, int32_t d_sh, const float* raw, const float* depths,
+                                        const float* extrinsics, const float* multiplier, int64_t mult_stride,
+                                        const float* sh_mask, float scale_min, float scale_max, const float* g_cov,
+                                        const float* g_harmonics, const float* g_scales, const float* g_rotations,
+                                        float* g_raw, float* g_depths, float* g_extrinsics, void* stream_)
+{
+    if (M < 0 || !multiplier || !sh_mask) return FS_ERR_INVALID_ARG;
+    if (!head_d_sh_supported(d_sh)) return FS_ERR_UNSUPPORTED;
+    if (M == 0) return FS_OK;
+    if (!raw || !depths || !extrinsics || !g_raw || !g_depths || !g_extrinsics) return FS_ERR_INVALID_ARG;
+    ScopedStage prof_(kStEncoderTail, (hipStream_t)stream_);
+    const hipStream_t st = (hipStream_t)stream_;
+#define FS_HEAD_BWD(D) launch_head_bwd<D>((long long)M, raw, depths, extrinsics, multiplier, (long long)mult_stride, sh_mask, \
+                                          scale_min, scale_max, g_cov, g_harmonics, g_scales, g_rotations, g_raw, g_depths, \
+                                          g_extrinsics, st)
+    switch (d_sh) {
+        case 1: FS_HEAD_BWD(1); break;
+        case 4: FS_HEAD_BWD(4); break;
+        case 9: FS_HEAD_BWD(9); break;
+        default: FS_HEAD_BWD(16); break;
+    }
+#undef FS_HEAD_BWD
+    FS_CHECK_LAUNCH("gaussian_head_backward");
+    return FS_OK;
+}
+
+// sh_degree 2 (d_sh = 9): the entry points of ABI 4 and later, unchanged in behaviour
 FS_API int fs_gaussian_head_forward(int64_t M, const float* raw, const float* depths, const float* extrinsics,
                                     const float* multiplier, int64_t mult_stride, const float* sh_mask,
                                     float scale_min, float scale_max, float* cov, float* harmonics, float* scales,
                                     float* rotations, void* stream_)
 {
-    if (M < 0 || !multiplier || !sh_mask) return FS_ERR_INVALID_ARG;
-    if (M == 0) return FS_OK;
-    if (!raw || !depths || !extrinsics || !cov || !harmonics || !scales || !rotations) return FS_ERR_INVALID_ARG;
-    ScopedStage prof_(kStEncoderTail, (hipStream_t)stream_);
-    hipLaunchKernelGGL(head_fwd_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, (hipStream_t)stream_,
-                       (long long)M, raw, depths, extrinsics, multiplier, (long long)mult_stride, sh_mask, scale_min,
-                       scale_max, cov, harmonics, scales, rotations);
-    FS_CHECK_LAUNCH("gaussian_head_forward");
-    return FS_OK;
+    return fs_gaussian_head_forward_sh(M, 9, raw, depths, extrinsics, multiplier, mult_stride, sh_mask, scale_min, scale_max,
+                                       cov, harmonics, scales, rotations, stream_);
 }
 
 FS_API int fs_gaussian_head_backward(int64_t M, const float* raw, const float* depths, const float* extrinsics,
@@ -437,15 +519,9 @@ FS_API int fs_gaussian_head_backward(int64_t M, const float* raw, const float* d
                                      const float* g_scales, const float* g_rotations, float* g_raw, float* g_depths,
                                      float* g_extrinsics, void* stream_)
 {
-    if (M < 0 || !multiplier || !sh_mask) return FS_ERR_INVALID_ARG;
-    if (M == 0) return FS_OK;
-    if (!raw || !depths || !extrinsics || !g_raw || !g_depths || !g_extrinsics) return FS_ERR_INVALID_ARG;
-    ScopedStage prof_(kStEncoderTail, (hipStream_t)stream_);
-    hipLaunchKernelGGL(head_bwd_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, (hipStream_t)stream_,
-                       (long long)M, raw, depths, extrinsics, multiplier, (long long)mult_stride, sh_mask, scale_min,
-                       scale_max, g_cov, g_harmonics, g_scales, g_rotations, g_raw, g_depths, g_extrinsics);
-    FS_CHECK_LAUNCH("gaussian_head_backward");
-    return FS_OK;
+    return fs_gaussian_head_backward_sh(M, 9, raw, depths, extrinsics, multiplier, mult_stride, sh_mask, scale_min,
+                                        scale_max, g_cov, g_harmonics, g_scales, g_rotations, g_raw, g_depths, g_extrinsics,
+                                        stream_);
 }
 
 FS_API int fs_latents_pack_forward(int32_t V, int64_t P, int32_t C, const float* head, const float* skip, float* latents,

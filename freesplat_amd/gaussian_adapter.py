@@ -7,7 +7,8 @@ with the same argument shapes as encoder_freesplat.py:317-326 (fusion=True -> wo
 :376-386 (fusion=False with `coords` -> Gaussians), `d_sh` / `d_in`, the non-persistent `sh_mask`
 buffer and `get_scale_multiplier`.  Compute = fs_unproject_* / fs_gaussian_head_* in
 libfreesplat_hip.so (forward and backward kernels; differentiable w.r.t. depths, raw channels and
-the blended extrinsics).  The pixelSplat-only branch (fusion=False without coords: per-ray means +
+the blended extrinsics).  sh_degree 0 - 3 (d_sh 1 / 4 / 9 / 16, the degrees the rasterizer evaluates); a
+higher degree raises.  The pixelSplat-only branch (fusion=False without coords: per-ray means +
 SH rotation) is not on FreeSplat's path and raises.
 """
 from __future__ import annotations
@@ -72,16 +73,20 @@ class _Head(torch.autograd.Function):
     @staticmethod
     def forward(ctx, raw, depths, extrinsics, mult, sh_mask, smin, smax):
         M = raw.shape[0]
+        d_sh = sh_mask.numel()
+        if raw.shape[-1] != 7 + 3 * d_sh:
+            raise RuntimeError(f"gaussian head: raw rows of {raw.shape[-1]} channels, expected 7 + 3 * d_sh = {7 + 3 * d_sh}")
         dev = raw.device
         cov = torch.empty(M, 3, 3, device=dev)
-        sh = torch.empty(M, 3, 9, device=dev)
+        sh = torch.empty(M, 3, d_sh, device=dev)
         scales = torch.empty(M, 3, device=dev)
         rot = torch.empty(M, 4, device=dev)
         stride = 0 if mult.numel() == 1 else 1
         p = _lib.ptr
-        _lib.check(_lib.lib().fs_gaussian_head_forward(M, p(raw), p(depths), p(extrinsics), p(mult), stride, p(sh_mask),
-                                                       C.c_float(smin), C.c_float(smax), p(cov), p(sh), p(scales), p(rot),
-                                                       _lib.current_stream()), "fs_gaussian_head_forward")
+        _lib.check(_lib.lib().fs_gaussian_head_forward_sh(M, d_sh, p(raw), p(depths), p(extrinsics), p(mult), stride,
+                                                          p(sh_mask), C.c_float(smin), C.c_float(smax), p(cov), p(sh),
+                                                          p(scales), p(rot), _lib.current_stream()),
+                   "fs_gaussian_head_forward_sh")
         ctx.save_for_backward(raw, depths, extrinsics, mult, sh_mask)
         ctx.cfg = (smin, smax, stride)
         ctx.set_materialize_grads(False)
@@ -96,10 +101,11 @@ class _Head(torch.autograd.Function):
         c = lambda t: None if t is None else t.contiguous()
         p = _lib.ptr
         gc_, gs_, gsc_, gr_ = c(g_cov), c(g_sh), c(g_scales), c(g_rot)   # (kept alive until the launch is queued)
-        _lib.check(_lib.lib().fs_gaussian_head_backward(M, p(raw), p(depths), p(extrinsics), p(mult), stride, p(sh_mask),
-                                                        C.c_float(smin), C.c_float(smax), p(gc_), p(gs_), p(gsc_), p(gr_),
-                                                        p(g_raw), p(g_dep), p(g_E), _lib.current_stream()),
-                   "fs_gaussian_head_backward")
+        _lib.check(_lib.lib().fs_gaussian_head_backward_sh(M, sh_mask.numel(), p(raw), p(depths), p(extrinsics), p(mult),
+                                                           stride, p(sh_mask), C.c_float(smin), C.c_float(smax), p(gc_),
+                                                           p(gs_), p(gsc_), p(gr_), p(g_raw), p(g_dep), p(g_E),
+                                                           _lib.current_stream()),
+                   "fs_gaussian_head_backward_sh")
         return g_raw, g_dep, g_E, None, None, None, None
 
 
@@ -193,8 +199,9 @@ class GaussianAdapter(nn.Module):
             raise NotImplementedError("GaussianAdapter.forward(fusion=False, coords=None) is pixelSplat's per-ray path "
                                       "(get_world_rays + rotate_sh); FreeSplat never takes it "
                                       "(gaussian_adapter.py:174-192)")
-        if self.d_sh != 9:
-            raise NotImplementedError("the HIP Gaussian head implements sh_degree 2 (d_in = 34)")
+        if not 0 <= self.cfg.sh_degree <= 3:
+            raise NotImplementedError(f"sh_degree {self.cfg.sh_degree}: the HIP rasterizer evaluates spherical harmonics of "
+                                      "degree 0 - 3 only, so the Gaussian head stops there too")
         lead = opacities.shape
         M = opacities.numel()
         pixel_size = 1 / torch.tensor((w, h), dtype=torch.float32, device=extrinsics.device)
@@ -205,5 +212,5 @@ class GaussianAdapter(nn.Module):
         cov, sh, scales, rot = _Head.apply(_chk(raw, "raw_gaussians"), _chk(depths.expand(lead).reshape(M), "depths"),
                                            _chk(E, "extrinsics"), _chk(mult, "multiplier"), self.sh_mask,
                                            float(self.cfg.gaussian_scale_min), float(self.cfg.gaussian_scale_max))
-        return Gaussians(means=coords, covariances=cov.reshape(*lead, 3, 3), harmonics=sh.reshape(*lead, 3, 9),
+        return Gaussians(means=coords, covariances=cov.reshape(*lead, 3, 3), harmonics=sh.reshape(*lead, 3, self.d_sh),
                          opacities=opacities, scales=scales.reshape(*lead, 3), rotations=rot.reshape(*lead, 4))

@@ -49,7 +49,9 @@ const char* fs_version(void);
  * shifted pointers.  3 = round 3 (single-pass binning: scratch = per-tile key areas, counters[1] = largest tile list on
  * overflow, geom without the mask / depth arrays; fused sort + blend).  8 = the evaluation metrics (fs_image_metrics,
  * fs_depth_metrics).  9 = deterministic backwards of the cost volume, the PTF fold and the depth tail
- * (fs_cost_volume_backward_det, fs_ptf_*_backward_det, fs_depth_tail_backward_det and their size queries). */
+ * (fs_cost_volume_backward_det, fs_ptf_*_backward_det, fs_depth_tail_backward_det and their size queries); later in 9,
+ * additively, fs_gaussian_head_forward_sh / _backward_sh (sh_degree 0 - 3): no existing signature changed, and a library
+ * without them fails at binding time (freesplat_amd/_lib.py looks up every declared symbol). */
 #define FS_ABI_VERSION 9
 int fs_abi_version(void);
 /* Last HIP error string observed by a failing call on this thread (never NULL). */
@@ -494,6 +496,20 @@ int fs_gaussian_head_backward(int64_t M, const float* raw, const float* depths, 
                               float scale_min, float scale_max, const float* g_cov, const float* g_harmonics,
                               const float* g_scales, const float* g_rotations, float* g_raw, float* g_depths,
                               float* g_extrinsics, void* stream);
+/* The same step at any sh_degree the rasterizer evaluates (0 - 3): d_sh = (sh_degree + 1)^2 in {1, 4, 9, 16},
+ * raw[M, 7 + 3 d_sh] = (scale 3, rotation xyzw 4, SH 3 d_sh as (xyz, d_sh)), sh_mask[d_sh], harmonics / g_harmonics
+ * [M, 3 d_sh], g_raw[M, 7 + 3 d_sh]; everything else as above (fs_gaussian_head_forward / _backward = d_sh 9, the same
+ * kernels).  NULL sizes / pointers as above -> FS_ERR_INVALID_ARG, checked first; then any other d_sh ->
+ * FS_ERR_UNSUPPORTED. */
+int fs_gaussian_head_forward_sh(int64_t M, int32_t d_sh, const float* raw, const float* depths, const float* extrinsics,
+                                const float* multiplier, int64_t mult_stride, const float* sh_mask, float scale_min,
+                                float scale_max, float* cov, float* harmonics, float* scales, float* rotations,
+                                void* stream);
+int fs_gaussian_head_backward_sh(int64_t M, int32_t d_sh, const float* raw, const float* depths, const float* extrinsics,
+                                 const float* multiplier, int64_t mult_stride, const float* sh_mask, float scale_min,
+                                 float scale_max, const float* g_cov, const float* g_harmonics, const float* g_scales,
+                                 const float* g_rotations, float* g_raw, float* g_depths, float* g_extrinsics,
+                                 void* stream);
 
 /*
  * Per-pixel latents of the fold (encoder_freesplat.py:311-316: `gaussians = head[:, 1:] + skip`, rearranged
