@@ -34,6 +34,7 @@ RASTER_COV_FULL = 8
 RASTER_FAST_EXP = 16
 RASTER_NO_BACKWARD_STATE = 32
 RASTER_DETERMINISTIC = 64
+RASTER_SCALE_ROT = 128
 
 
 def build(force: bool = False) -> str:
@@ -59,6 +60,8 @@ SIGNATURES = {
     "fs_raster_buffer_sizes": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_size_t)]),
     "fs_raster_forward": (C.c_int, [C.POINTER(RasterDims)] + [_VP] * 15 + [C.c_int64] + [_VP] * 6),
     "fs_raster_backward": (C.c_int, [C.POINTER(RasterDims)] + [_VP] * 24 + [C.c_int, _VP]),
+    "fs_raster_backward_alpha": (C.c_int, [C.POINTER(RasterDims)] + [_VP] * 25 + [C.c_int, _VP]),
+    "fs_raster_cov3d_from_scale_rot": (C.c_int, [C.c_int32, _VP, _VP, _VP]),
     "fs_raster_backward_scratch_bytes": (C.c_size_t, [C.POINTER(RasterDims), C.c_int32, C.c_int32, C.c_int64]),
     "fs_cost_volume_workspace_bytes": (C.c_size_t, [C.c_int32] * 5),
     "fs_cost_volume_forward": (C.c_int, [C.c_int32] * 6 + [_VP] * 6 + [C.c_int64] * 3 + [_VP] * 9),
@@ -107,6 +110,11 @@ SIGNATURES = {
                                  + [C.c_int32, C.c_int32, C.POINTER(C.c_void_p), _VP]),
     "fs_raster_backward_views_rows": (C.c_int, [C.POINTER(RasterDims), C.c_int32] + [_VP] * 15 + [C.POINTER(C.c_size_t)] + [_VP] * 9
                                       + [C.c_int32, C.c_int32, C.POINTER(C.c_void_p), _VP, C.c_int32, C.c_int32, C.c_int32]),
+    "fs_raster_backward_views_alpha": (C.c_int, [C.POINTER(RasterDims), C.c_int32] + [_VP] * 15 + [C.POINTER(C.c_size_t)]
+                                       + [_VP] * 10 + [C.c_int32, C.c_int32, C.POINTER(C.c_void_p), _VP]),
+    "fs_raster_backward_views_rows_alpha": (C.c_int, [C.POINTER(RasterDims), C.c_int32] + [_VP] * 15 + [C.POINTER(C.c_size_t)]
+                                            + [_VP] * 10 + [C.c_int32, C.c_int32, C.POINTER(C.c_void_p), _VP, C.c_int32,
+                                                            C.c_int32, C.c_int32]),
     "fs_ptf_fold_scratch_bytes": (C.c_size_t, [C.c_int32] * 3),
     "fs_ptf_fold_step": (C.c_int, [C.c_int32, _VP, C.c_int32, C.c_int32] + [_VP] * 14 + [C.c_float] + [_VP] * 10),
     "fs_ptf_fold_step_save": (C.c_int, [C.c_int32, _VP, C.c_int32, C.c_int32] + [_VP] * 14 + [C.c_float] + [_VP] * 13),

@@ -285,6 +285,80 @@ __device__ __forceinline__ Cov2D project_cov(const float* __restrict__ V, float3
     return o;
 }
 
+// (scales, rotations) -> 3D covariance (FS_RASTER_SCALE_ROT).  row = {sx, sy, sz, qw, qx, qy, qz}; c = upper triangle of
+// Sigma = M M^T with M = R(q / |q|) diag(s): the steps of rasterizer.build_cov3d, every operation rounded on its own (no
+// contraction whatever the build flags), so that the projection, the backward and fs_raster_cov3d_from_scale_rot all form
+// the same bits from one row.
+struct ScaleRot {
+    float s[3];
+    float q[4];      // normalised (w, x, y, z)
+    float inv_n;     // 1 / |q| of the row
+    float R[3][3];
+};
+__device__ __forceinline__ ScaleRot scale_rot_setup(const float (&row)[7])
+{
+#pragma clang fp contract(off)
+    ScaleRot o;
+    o.s[0] = row[0]; o.s[1] = row[1]; o.s[2] = row[2];
+    const float n = sqrtf(row[3] * row[3] + row[4] * row[4] + row[5] * row[5] + row[6] * row[6]);
+    o.inv_n = 1.0f / n;
+    const float r = row[3] / n, x = row[4] / n, y = row[5] / n, z = row[6] / n;
+    o.q[0] = r; o.q[1] = x; o.q[2] = y; o.q[3] = z;
+    o.R[0][0] = 1.0f - 2.0f * (y * y + z * z); o.R[0][1] = 2.0f * (x * y - r * z); o.R[0][2] = 2.0f * (x * z + r * y);
+    o.R[1][0] = 2.0f * (x * y + r * z); o.R[1][1] = 1.0f - 2.0f * (x * x + z * z); o.R[1][2] = 2.0f * (y * z - r * x);
+    o.R[2][0] = 2.0f * (x * z - r * y); o.R[2][1] = 2.0f * (y * z + r * x); o.R[2][2] = 1.0f - 2.0f * (x * x + y * y);
+    return o;
+}
+__device__ __forceinline__ void cov_from_scale_rot(const float (&row)[7], float (&c)[6])
+{
+#pragma clang fp contract(off)
+    const ScaleRot g = scale_rot_setup(row);
+    float M[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) M[i][j] = g.R[i][j] * g.s[j];
+    constexpr int kI[6] = {0, 0, 0, 1, 1, 2}, kK[6] = {0, 1, 2, 1, 2, 2};
+#pragma unroll
+    for (int e = 0; e < 6; ++e) {
+        const int i = kI[e], k = kK[e];
+        c[e] = M[i][0] * M[k][0] + M[i][1] * M[k][1] + M[i][2] * M[k][2];
+    }
+}
+// Gradient of cov_from_scale_rot: g = dL/d(upper triangle) as the [N,6] gradient rows carry it (an off-diagonal entry once)
+// -> out = dL/d row, through the normalisation (w.r.t. the caller's unnormalised quaternion).  dL/dM = (G + G^T) M with G the
+// upper-triangular matrix of g; dL/ds_j = sum_i dM_ij R_ij; dL/dR_ij = dM_ij s_j; dL/du = (dq - q (q . dq)) / |u|.
+__device__ __forceinline__ void cov_from_scale_rot_bwd(const float (&row)[7], const float (&g)[6], float (&out)[7])
+{
+    const ScaleRot sr = scale_rot_setup(row);
+    const float Gs[3][3] = {{2.0f * g[0], g[1], g[2]}, {g[1], 2.0f * g[3], g[4]}, {g[2], g[4], 2.0f * g[5]}};
+    float dR[3][3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        float ds = 0.0f;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const float dM = (Gs[i][0] * sr.R[0][j] + Gs[i][1] * sr.R[1][j] + Gs[i][2] * sr.R[2][j]) * sr.s[j];
+            ds += dM * sr.R[i][j];
+            dR[i][j] = dM * sr.s[j];
+        }
+        out[j] = ds;
+    }
+    const float r = sr.q[0], x = sr.q[1], y = sr.q[2], z = sr.q[3];
+    const float dr = 2.0f * (z * (dR[1][0] - dR[0][1]) + y * (dR[0][2] - dR[2][0]) + x * (dR[2][1] - dR[1][2]));
+    const float dx = 2.0f * (y * (dR[1][0] + dR[0][1]) + z * (dR[2][0] + dR[0][2]) + r * (dR[2][1] - dR[1][2])) -
+                     4.0f * x * (dR[2][2] + dR[1][1]);
+    const float dy = 2.0f * (x * (dR[1][0] + dR[0][1]) + r * (dR[0][2] - dR[2][0]) + z * (dR[2][1] + dR[1][2])) -
+                     4.0f * y * (dR[2][2] + dR[0][0]);
+    const float dz = 2.0f * (r * (dR[1][0] - dR[0][1]) + x * (dR[2][0] + dR[0][2]) + y * (dR[2][1] + dR[1][2])) -
+                     4.0f * z * (dR[1][1] + dR[0][0]);
+    const float qd = r * dr + x * dx + y * dy + z * dz;
+    out[3] = (dr - r * qd) * sr.inv_n;
+    out[4] = (dx - x * qd) * sr.inv_n;
+    out[5] = (dy - y * qd) * sr.inv_n;
+    out[6] = (dz - z * qd) * sr.inv_n;
+}
+
 // ---- rasterizer buffer layouts (opaque to the caller; see fs_raster_buffer_sizes) ------------
 // geom: [N] x 3 float4 screen-space records, [N] ushort4 tile rects, [N] u8 clamp bits.
 //   r0 = {px, py, -A/2, -C/2}   r1 = {-B, opacity, power_skip_threshold, view_z}

@@ -11,6 +11,8 @@
 //   preprocess_bwd  1 thread / Gaussian: conic -> cov2D -> Sigma & view position, mean2D ->
 //                   mean through the perspective divide, RGB -> SH & view direction.
 //                   SH gradients leave through LDS so the [N, M, 3] rows are written coalesced.
+#include <type_traits>
+
 #include "fs_common.h"
 
 namespace fs {
@@ -107,13 +109,16 @@ constexpr int kSlabStride = 10;  // floats per (list position, quadrant) row of 
 // row of (list position, quadrant) -- slab [cap][4][kSlabStride] -- instead of atomics into grad (unused then); every slab
 // row whose entry carries this quadrant's bit is written, with zeros where the pair left early or the entry lies past the
 // quadrant's last contributor, so det_rank_sum never reads an unwritten row.  Positions >= cap_lim are not stored.
-template <bool FAST_EXP, bool DEPTH, bool STORE>
+// ALPHA = true (dL_dalpha != NULL): the accumulated alpha A = 1 - Tf has dA/da_j = Tf / (1 - a_j), the form of the background
+// term, so the pixel's alpha gradient gA only enters Tb = Tf * (bg . dL/dC - gA); no other partial changes.
+template <bool FAST_EXP, bool DEPTH, bool STORE, bool ALPHA>
 __global__ __launch_bounds__(64) void render_bwd_kernel(
     int H, int W, int T, const uint32_t* __restrict__ offsets,
     const uint32_t* __restrict__ point_list, const float4* __restrict__ rec,
     const float* __restrict__ bg, const uint32_t* __restrict__ counters, const float* __restrict__ final_T,
     const int32_t* __restrict__ n_contrib, const float* __restrict__ dL_dcolor,
-    const float* __restrict__ dL_ddepth, float* __restrict__ grad, float* __restrict__ slab, uint32_t cap_lim)
+    const float* __restrict__ dL_ddepth, float* __restrict__ grad, float* __restrict__ slab, uint32_t cap_lim,
+    const float* __restrict__ dL_dalpha)
 {
     __shared__ float4 s_pair[33 * kBwdQuads];   // up to 1 carried + 64 new survivors, two per slot
     if (counters && counters[1]) return;  // the forward overflowed its capacity: no image, no lists -> zero gradients
@@ -138,7 +143,9 @@ __global__ __launch_bounds__(64) void render_bwd_kernel(
     const int last = inside ? n_contrib[pix] : 0;
     const f32x2 g01 = {inside ? dL_dcolor[pix] : 0.0f, inside ? dL_dcolor[HW + pix] : 0.0f};
     const f32x2 g23 = {inside ? dL_dcolor[2 * HW + pix] : 0.0f, (DEPTH && inside && dL_ddepth) ? dL_ddepth[pix] : 0.0f};
-    const float Tb = Tf * (bg[0] * g01.x + bg[1] * g01.y + bg[2] * g23.x);
+    float bgg = bg[0] * g01.x + bg[1] * g01.y + bg[2] * g23.x;
+    if constexpr (ALPHA) bgg = bgg - (inside ? dL_dalpha[pix] : 0.0f);
+    const float Tb = Tf * bgg;
 
     int maxlast = last;
 #pragma unroll
@@ -371,10 +378,14 @@ __device__ __forceinline__ void sh_backward(const float* __restrict__ sh, float 
 // registers before the single write (per view only the 48-byte record, the tile rect and the 48-byte screen-space
 // gradient row are read).  view / proj [V,16], campos [V,3], tanfov [V,2] | NULL, scale [V] | NULL; geom and grad
 // hold V buffers geom_stride / grad_stride bytes apart.  `accumulate` adds to what the outputs already hold.
+// SR (FS_RASTER_SCALE_ROT): cov3D / dL_dcov3D rows are (scales, rotation) [N,7]; the covariance is formed from the row as the
+// forward formed it, dL/dSigma is summed over the views as before and turned into dL/d(scales, rotation) once, before the
+// previous row is added (the chain rule is linear in dL/dSigma).
 // (two wavefronts per SIMD beat one wavefront at 310 registers by 13 %)
 #ifndef FS_PBWD_WAVES
 #define FS_PBWD_WAVES 2
 #endif
+template <bool SR>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FS_PBWD_WAVES, FS_PBWD_WAVES))) void preprocess_bwd_kernel(
     fs_raster_dims d, int V, const float* __restrict__ means3D, const float* __restrict__ cov3D,
     const float* __restrict__ shs, const float* __restrict__ opacities, const float* __restrict__ view_all, const float* __restrict__ proj_all,
@@ -406,8 +417,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FS_PBWD_WAV
         // inputs, once
         const float3 p0 = make_float3(means3D[3 * (size_t)i], means3D[3 * (size_t)i + 1], means3D[3 * (size_t)i + 2]);
         float c0[6];
+        if constexpr (SR) {
+            float row[7];
 #pragma unroll
-        for (int k = 0; k < 6; ++k) c0[k] = cov_full ? cov3D[9 * (size_t)i + kTriu[k]] : cov3D[6 * (size_t)i + k];
+            for (int k = 0; k < 7; ++k) row[k] = cov3D[7 * (size_t)i + k];
+            cov_from_scale_rot(row, c0);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) c0[k] = cov_full ? cov3D[9 * (size_t)i + kTriu[k]] : cov3D[6 * (size_t)i + k];
+        }
         // (the blend summed the moments of dL/dalpha * G: the Gaussian's opacity completes w = dL/dG * G -- see render_bwd)
         const float opac = opacities[i];
         // the Gaussian's SH coefficients wait in the thread's own slots of the LDS staging area (idle until the gradients are staged
@@ -557,13 +575,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FS_PBWD_WAV
             for (int k = 0; k < 6; ++k) acov[k] += scale_dev ? gcov[k] * s2 : gcov[k];
         }
       }  // views
+        float asr[7];   // (SR) dL/d(scales, rotation): the row is re-read (28 B) rather than kept live across the view loop
+        if constexpr (SR) {
+            float row[7];
+#pragma unroll
+            for (int k = 0; k < 7; ++k) row[k] = cov3D[7 * (size_t)i + k];
+            cov_from_scale_rot_bwd(row, acov, asr);
+        }
         if (accumulate) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) am[k] += dL_dmeans3D[3 * (size_t)i + k];
             am2x += dL_dmeans2D[3 * (size_t)i];
             am2y += dL_dmeans2D[3 * (size_t)i + 1];
+            if constexpr (SR) {
 #pragma unroll
-            for (int k = 0; k < 6; ++k) acov[k] += cov_full ? dL_dcov3D[9 * (size_t)i + kTriu[k]] : dL_dcov3D[6 * (size_t)i + k];
+                for (int k = 0; k < 7; ++k) asr[k] += dL_dcov3D[7 * (size_t)i + k];
+            } else {
+#pragma unroll
+                for (int k = 0; k < 6; ++k) acov[k] += cov_full ? dL_dcov3D[9 * (size_t)i + kTriu[k]] : dL_dcov3D[6 * (size_t)i + k];
+            }
             aop += dL_dopac[i];
             if (!have_sh) {
 #pragma unroll
@@ -575,12 +605,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FS_PBWD_WAV
         dL_dmeans2D[3 * (size_t)i] = am2x;
         dL_dmeans2D[3 * (size_t)i + 1] = am2y;
         dL_dmeans2D[3 * (size_t)i + 2] = 0.0f;
+        if constexpr (SR) {
 #pragma unroll
-        for (int k = 0; k < 6; ++k) {
-            if (cov_full) dL_dcov3D[9 * (size_t)i + kTriu[k]] = acov[k];
-            else dL_dcov3D[6 * (size_t)i + k] = acov[k];
+            for (int k = 0; k < 7; ++k) dL_dcov3D[7 * (size_t)i + k] = asr[k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                if (cov_full) dL_dcov3D[9 * (size_t)i + kTriu[k]] = acov[k];
+                else dL_dcov3D[6 * (size_t)i + k] = acov[k];
+            }
         }
-        if (cov_full) {  // the reference reads the upper triangle only (cuda_splatting.py:126): no gradient below it
+        if (!SR && cov_full) {  // the reference reads the upper triangle only (cuda_splatting.py:126): no gradient below it
             dL_dcov3D[9 * (size_t)i + 3] = 0.0f; dL_dcov3D[9 * (size_t)i + 6] = 0.0f; dL_dcov3D[9 * (size_t)i + 7] = 0.0f;
         }
         dL_dopac[i] = aop;
@@ -895,8 +930,8 @@ void launch_det_reduce(const fs_raster_dims& d, const uint32_t* offsets, const u
 // blend backward of ONE view into its screen-space gradient rows (grad [N, 12], zeroed here; with det != NULL written by the
 // deterministic reduction instead, from the slab rows of det's region)
 int launch_render_bwd(const fs_raster_dims& d, const float* bg, const void* geom, const void* binning, const void* image,
-                      const uint32_t* counters, const float* dL_dcolor, const float* dL_ddepth, float* grad, hipStream_t st,
-                      const DetRegion* det = nullptr, uint32_t cap_lim = 0xffffffffu)
+                      const uint32_t* counters, const float* dL_dcolor, const float* dL_ddepth, const float* dL_dalpha,
+                      float* grad, hipStream_t st, const DetRegion* det = nullptr, uint32_t cap_lim = 0xffffffffu)
 {
     const int T = num_tiles(d.H, d.W);
     const size_t P = (size_t)d.H * d.W;
@@ -921,16 +956,20 @@ int launch_render_bwd(const fs_raster_dims& d, const float* bg, const void* geom
         ScopedStage prof_(kStRenderBwd, st);
         auto go = [&](auto kernel) {
             hipLaunchKernelGGL(kernel, dim3(4 * nblk), dim3(64), 0, st, d.H, d.W, T, offsets, point_list, g.rec, bg, counters,
-                               final_T, n_contrib, dL_dcolor, dL_ddepth, grad, det ? det->slab : nullptr, cap_lim);
+                               final_T, n_contrib, dL_dcolor, dL_ddepth, grad, det ? det->slab : nullptr, cap_lim, dL_dalpha);
         };
         const bool depth = dL_ddepth != nullptr, fast = (d.flags & FS_RASTER_FAST_EXP) != 0;
-        if (det) {
-            if (fast) { if (depth) go(render_bwd_kernel<true, true, true>); else go(render_bwd_kernel<true, false, true>); }
-            else { if (depth) go(render_bwd_kernel<false, true, true>); else go(render_bwd_kernel<false, false, true>); }
-        } else {
-            if (fast) { if (depth) go(render_bwd_kernel<true, true, false>); else go(render_bwd_kernel<true, false, false>); }
-            else { if (depth) go(render_bwd_kernel<false, true, false>); else go(render_bwd_kernel<false, false, false>); }
-        }
+        auto pick = [&](auto alpha) {
+            constexpr bool A = decltype(alpha)::value;
+            if (det) {
+                if (fast) { if (depth) go(render_bwd_kernel<true, true, true, A>); else go(render_bwd_kernel<true, false, true, A>); }
+                else { if (depth) go(render_bwd_kernel<false, true, true, A>); else go(render_bwd_kernel<false, false, true, A>); }
+            } else {
+                if (fast) { if (depth) go(render_bwd_kernel<true, true, false, A>); else go(render_bwd_kernel<true, false, false, A>); }
+                else { if (depth) go(render_bwd_kernel<false, true, false, A>); else go(render_bwd_kernel<false, false, false, A>); }
+            }
+        };
+        if (dL_dalpha) pick(std::true_type{}); else pick(std::false_type{});
         if (det) launch_det_reduce(d, offsets, point_list, counters, cap_lim, *det, grad, st);
     }
     FS_CHECK_LAUNCH("render_bwd");
@@ -949,10 +988,13 @@ int launch_preprocess_bwd(const fs_raster_dims& d, int V, const float* means3D, 
     if (nrows <= 0) return FS_OK;
     {
         ScopedStage prof_(kStPreprocessBwd, st, V);
-        hipLaunchKernelGGL(preprocess_bwd_kernel, dim3((nrows + 255) / 256), dim3(256), lds, st, d, V, means3D, cov3D, shs,
-                           opacities, view, proj, campos, tanfov, scale, (const char*)geom, geom_stride, (const char*)grad,
-                           grad_stride, dL_dmeans3D, dL_dmeans2D, dL_dcov3D, dL_dshs, dL_dcolors, dL_dopacities,
-                           accumulate, row0, row0 + nrows);
+        auto go = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3((nrows + 255) / 256), dim3(256), lds, st, d, V, means3D, cov3D, shs, opacities, view,
+                               proj, campos, tanfov, scale, (const char*)geom, geom_stride, (const char*)grad, grad_stride,
+                               dL_dmeans3D, dL_dmeans2D, dL_dcov3D, dL_dshs, dL_dcolors, dL_dopacities, accumulate, row0,
+                               row0 + nrows);
+        };
+        if (d.flags & FS_RASTER_SCALE_ROT) go(preprocess_bwd_kernel<true>); else go(preprocess_bwd_kernel<false>);
     }
     FS_CHECK_LAUNCH("preprocess_bwd");
     return FS_OK;
@@ -960,19 +1002,20 @@ int launch_preprocess_bwd(const fs_raster_dims& d, int V, const float* means3D, 
 
 }  // namespace
 
-FS_API int fs_raster_backward(const fs_raster_dims* dims, const float* means3D, const float* cov3D,
-                              const float* shs, const float* colors_precomp, const float* opacities, const float* bg,
-                              const float* viewmatrix, const float* projmatrix, const float* campos,
-                              const float* tanfov_dev, const float* scale_dev,
-                              const void* geom, const void* binning, const void* image, const uint32_t* counters,
-                              const float* dL_dcolor, const float* dL_ddepth, void* grad_scratch,
-                              float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcov3D,
-                              float* dL_dshs, float* dL_dcolors, float* dL_dopacities, int accumulate,
-                              void* stream_)
+FS_API int fs_raster_backward_alpha(const fs_raster_dims* dims, const float* means3D, const float* cov3D,
+                                    const float* shs, const float* colors_precomp, const float* opacities, const float* bg,
+                                    const float* viewmatrix, const float* projmatrix, const float* campos,
+                                    const float* tanfov_dev, const float* scale_dev,
+                                    const void* geom, const void* binning, const void* image, const uint32_t* counters,
+                                    const float* dL_dcolor, const float* dL_ddepth, const float* dL_dalpha, void* grad_scratch,
+                                    float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcov3D,
+                                    float* dL_dshs, float* dL_dcolors, float* dL_dopacities, int accumulate,
+                                    void* stream_)
 {
     if (!dims) return FS_ERR_INVALID_ARG;
     const fs_raster_dims d = *dims;
     if (d.N < 0 || (d.flags & FS_RASTER_NO_BACKWARD_STATE)) return FS_ERR_INVALID_ARG;   // (that forward kept no n_contrib)
+    if ((d.flags & FS_RASTER_SCALE_ROT) && (d.flags & FS_RASTER_COV_FULL)) return FS_ERR_INVALID_ARG;
     if (d.N == 0) return FS_OK;  // an empty Gaussian set has empty gradients; its arrays may be NULL (as in the forward)
     if (!means3D || !cov3D || !opacities || !bg || !viewmatrix || !projmatrix || !campos || !geom ||
         !binning || !image || !dL_dcolor || !grad_scratch || !dL_dmeans3D || !dL_dmeans2D ||
@@ -984,12 +1027,28 @@ FS_API int fs_raster_backward(const fs_raster_dims* dims, const float* means3D, 
     hipStream_t st = (hipStream_t)stream_;
     // deterministic mode: the view's slab and index follow its gradient rows (fs_raster_backward_scratch_bytes with v = 0)
     const DetRegion det((char*)grad_scratch + align_up((size_t)d.N * 48, 256), d.N);
-    int rc = launch_render_bwd(d, bg, geom, binning, image, counters, dL_dcolor, dL_ddepth, (float*)grad_scratch, st,
+    int rc = launch_render_bwd(d, bg, geom, binning, image, counters, dL_dcolor, dL_ddepth, dL_dalpha, (float*)grad_scratch, st,
                                (d.flags & FS_RASTER_DETERMINISTIC) ? &det : nullptr);
     if (rc != FS_OK) return rc;
     return launch_preprocess_bwd(d, 1, means3D, cov3D, shs, opacities, viewmatrix, projmatrix, campos, tanfov_dev, scale_dev, geom, 0,
                                  grad_scratch, 0, dL_dmeans3D, dL_dmeans2D, dL_dcov3D, dL_dshs, dL_dcolors,
                                  dL_dopacities, accumulate, st);
+}
+
+FS_API int fs_raster_backward(const fs_raster_dims* dims, const float* means3D, const float* cov3D,
+                              const float* shs, const float* colors_precomp, const float* opacities, const float* bg,
+                              const float* viewmatrix, const float* projmatrix, const float* campos,
+                              const float* tanfov_dev, const float* scale_dev,
+                              const void* geom, const void* binning, const void* image, const uint32_t* counters,
+                              const float* dL_dcolor, const float* dL_ddepth, void* grad_scratch,
+                              float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcov3D,
+                              float* dL_dshs, float* dL_dcolors, float* dL_dopacities, int accumulate,
+                              void* stream_)
+{
+    return fs_raster_backward_alpha(dims, means3D, cov3D, shs, colors_precomp, opacities, bg, viewmatrix, projmatrix, campos,
+                                    tanfov_dev, scale_dev, geom, binning, image, counters, dL_dcolor, dL_ddepth, nullptr,
+                                    grad_scratch, dL_dmeans3D, dL_dmeans2D, dL_dcov3D, dL_dshs, dL_dcolors, dL_dopacities,
+                                    accumulate, stream_);
 }
 
 namespace {
@@ -1031,14 +1090,15 @@ static int raster_backward_views_impl(const fs_raster_dims* dims, int32_t v, con
                                     const float* viewmatrix, const float* projmatrix, const float* campos,
                                     const float* tanfov, const float* scale, const void* geom, const void* binning,
                                     const void* image, const uint32_t* counters, const size_t strides[3], const float* dL_dcolor,
-                                    const float* dL_ddepth, void* grad_scratch, float* dL_dmeans3D, float* dL_dmeans2D,
-                                    float* dL_dcov3D, float* dL_dshs, float* dL_dcolors, float* dL_dopacities,
+                                    const float* dL_ddepth, const float* dL_dalpha, void* grad_scratch, float* dL_dmeans3D,
+                                    float* dL_dmeans2D, float* dL_dcov3D, float* dL_dshs, float* dL_dcolors, float* dL_dopacities,
                                     int32_t accumulate, int32_t n_streams, void* const* streams, void* main_stream,
                                     int32_t row0, int32_t nrows, int32_t with_blend)
 {
     if (!dims || v < 0 || !strides || n_streams < 0 || n_streams > kMaxStreamsBwd || (n_streams > 0 && !streams))
         return FS_ERR_INVALID_ARG;
     if (row0 < 0 || (nrows >= 0 && (long long)row0 + nrows > dims->N)) return FS_ERR_INVALID_ARG;
+    if ((dims->flags & FS_RASTER_SCALE_ROT) && (dims->flags & FS_RASTER_COV_FULL)) return FS_ERR_INVALID_ARG;
     if (v == 0) return FS_OK;
     const fs_raster_dims d = *dims;
     if (d.N < 0 || (d.flags & FS_RASTER_NO_BACKWARD_STATE)) return FS_ERR_INVALID_ARG;
@@ -1086,7 +1146,7 @@ static int raster_backward_views_impl(const fs_raster_dims* dims, int32_t v, con
         rc = launch_render_bwd(d, bg + 3 * (size_t)i, (const char*)geom + strides[0] * i,
                                (const char*)binning + strides[1] * i, (const char*)image + strides[2] * i,
                                counters ? counters + 2 * (size_t)i : nullptr, dL_dcolor + 3 * P * i, dL_ddepth ? dL_ddepth + P * i : nullptr,
-                               (float*)((char*)grad_scratch + grad_stride * i), st, det ? &region : nullptr,
+                               dL_dalpha ? dL_dalpha + P * i : nullptr, (float*)((char*)grad_scratch + grad_stride * i), st, det ? &region : nullptr,
                                (uint32_t)std::min<size_t>(cap_det, 0xffffffffu));
     }
     for (int s = 0; s < ns; ++s)
@@ -1102,6 +1162,22 @@ static int raster_backward_views_impl(const fs_raster_dims* dims, int32_t v, con
                                  dL_dcolors, dL_dopacities, accumulate, main, row0, nrows);
 }
 
+FS_API int fs_raster_backward_views_alpha(const fs_raster_dims* dims, int32_t v, const float* means3D, const float* cov3D,
+                                          const float* shs, const float* colors_precomp, const float* opacities, const float* bg,
+                                          const float* viewmatrix, const float* projmatrix, const float* campos,
+                                          const float* tanfov, const float* scale, const void* geom, const void* binning,
+                                          const void* image, const uint32_t* counters, const size_t strides[3],
+                                          const float* dL_dcolor, const float* dL_ddepth, const float* dL_dalpha, void* grad_scratch,
+                                          float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcov3D, float* dL_dshs,
+                                          float* dL_dcolors, float* dL_dopacities, int32_t accumulate, int32_t n_streams,
+                                          void* const* streams, void* main_stream)
+{
+    return raster_backward_views_impl(dims, v, means3D, cov3D, shs, colors_precomp, opacities, bg, viewmatrix, projmatrix, campos,
+                                      tanfov, scale, geom, binning, image, counters, strides, dL_dcolor, dL_ddepth, dL_dalpha,
+                                      grad_scratch, dL_dmeans3D, dL_dmeans2D, dL_dcov3D, dL_dshs, dL_dcolors, dL_dopacities,
+                                      accumulate, n_streams, streams, main_stream, 0, -1, 1);
+}
+
 FS_API int fs_raster_backward_views(const fs_raster_dims* dims, int32_t v, const float* means3D, const float* cov3D,
                                     const float* shs, const float* colors_precomp, const float* opacities, const float* bg,
                                     const float* viewmatrix, const float* projmatrix, const float* campos,
@@ -1111,16 +1187,35 @@ FS_API int fs_raster_backward_views(const fs_raster_dims* dims, int32_t v, const
                                     float* dL_dcov3D, float* dL_dshs, float* dL_dcolors, float* dL_dopacities,
                                     int32_t accumulate, int32_t n_streams, void* const* streams, void* main_stream)
 {
-    return raster_backward_views_impl(dims, v, means3D, cov3D, shs, colors_precomp, opacities, bg, viewmatrix, projmatrix, campos,
-                                      tanfov, scale, geom, binning, image, counters, strides, dL_dcolor, dL_ddepth, grad_scratch,
-                                      dL_dmeans3D, dL_dmeans2D, dL_dcov3D, dL_dshs, dL_dcolors, dL_dopacities, accumulate,
-                                      n_streams, streams, main_stream, 0, -1, 1);
+    return fs_raster_backward_views_alpha(dims, v, means3D, cov3D, shs, colors_precomp, opacities, bg, viewmatrix, projmatrix,
+                                          campos, tanfov, scale, geom, binning, image, counters, strides, dL_dcolor, dL_ddepth,
+                                          nullptr, grad_scratch, dL_dmeans3D, dL_dmeans2D, dL_dcov3D, dL_dshs, dL_dcolors,
+                                          dL_dopacities, accumulate, n_streams, streams, main_stream);
 }
 
 // The same backward with its per-Gaussian pass restricted to rows [row0, row0 + nrows) of the Gaussian set: a caller that
 // exchanges the gradients between GPUs chunk by chunk (view_sharding.GradExchange("chunked")) runs the blend backward of all views
 // with the first chunk (with_blend = 1) and only the per-Gaussian pass for the others (with_blend = 0), so that the
 // reduce-scatter of chunk c overlaps the pass over chunk c + 1.
+FS_API int fs_raster_backward_views_rows_alpha(const fs_raster_dims* dims, int32_t v, const float* means3D, const float* cov3D,
+                                               const float* shs, const float* colors_precomp, const float* opacities,
+                                               const float* bg, const float* viewmatrix, const float* projmatrix,
+                                               const float* campos, const float* tanfov, const float* scale, const void* geom,
+                                               const void* binning, const void* image, const uint32_t* counters,
+                                               const size_t strides[3], const float* dL_dcolor, const float* dL_ddepth,
+                                               const float* dL_dalpha, void* grad_scratch, float* dL_dmeans3D,
+                                               float* dL_dmeans2D, float* dL_dcov3D, float* dL_dshs, float* dL_dcolors,
+                                               float* dL_dopacities, int32_t accumulate, int32_t n_streams,
+                                               void* const* streams, void* main_stream, int32_t row0, int32_t nrows,
+                                               int32_t with_blend)
+{
+    if (nrows < 0) return FS_ERR_INVALID_ARG;
+    return raster_backward_views_impl(dims, v, means3D, cov3D, shs, colors_precomp, opacities, bg, viewmatrix, projmatrix, campos,
+                                      tanfov, scale, geom, binning, image, counters, strides, dL_dcolor, dL_ddepth, dL_dalpha,
+                                      grad_scratch, dL_dmeans3D, dL_dmeans2D, dL_dcov3D, dL_dshs, dL_dcolors, dL_dopacities,
+                                      accumulate, n_streams, streams, main_stream, row0, nrows, with_blend);
+}
+
 FS_API int fs_raster_backward_views_rows(const fs_raster_dims* dims, int32_t v, const float* means3D, const float* cov3D,
                                          const float* shs, const float* colors_precomp, const float* opacities, const float* bg,
                                          const float* viewmatrix, const float* projmatrix, const float* campos,
@@ -1131,9 +1226,9 @@ FS_API int fs_raster_backward_views_rows(const fs_raster_dims* dims, int32_t v, 
                                          float* dL_dcolors, float* dL_dopacities, int32_t accumulate, int32_t n_streams,
                                          void* const* streams, void* main_stream, int32_t row0, int32_t nrows, int32_t with_blend)
 {
-    if (nrows < 0) return FS_ERR_INVALID_ARG;
-    return raster_backward_views_impl(dims, v, means3D, cov3D, shs, colors_precomp, opacities, bg, viewmatrix, projmatrix, campos,
-                                      tanfov, scale, geom, binning, image, counters, strides, dL_dcolor, dL_ddepth, grad_scratch,
-                                      dL_dmeans3D, dL_dmeans2D, dL_dcov3D, dL_dshs, dL_dcolors, dL_dopacities, accumulate,
-                                      n_streams, streams, main_stream, row0, nrows, with_blend);
+    return fs_raster_backward_views_rows_alpha(dims, v, means3D, cov3D, shs, colors_precomp, opacities, bg, viewmatrix, projmatrix,
+                                               campos, tanfov, scale, geom, binning, image, counters, strides, dL_dcolor,
+                                               dL_ddepth, nullptr, grad_scratch, dL_dmeans3D, dL_dmeans2D, dL_dcov3D, dL_dshs,
+                                               dL_dcolors, dL_dopacities, accumulate, n_streams, streams, main_stream, row0,
+                                               nrows, with_blend);
 }

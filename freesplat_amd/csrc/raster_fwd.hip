@@ -363,12 +363,19 @@ __device__ __forceinline__ Projected project_gaussian(
 }
 
 // Mean (12 B) and covariance (24 / 36 B) rows straight into registers: a wavefront's rows are one contiguous
-// 0.8 - 2.3 KB range, every fetched line is fully used.
+// 0.8 - 2.3 KB range, every fetched line is fully used.  SR (FS_RASTER_SCALE_ROT): the 28-byte (scales, rotation) row,
+// turned into the covariance here -- the rest of the projection never sees the difference.
+template <bool SR>
 __device__ __forceinline__ void load_mean_cov(const fs_raster_dims& d, const float* __restrict__ means3D,
                                               const float* __restrict__ cov3D, size_t i, float3& p_in, float (&c_in)[6])
 {
     p_in = make_float3(means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2]);
-    if (d.flags & FS_RASTER_COV_FULL) {  // row-major 3x3, upper triangle
+    if constexpr (SR) {
+        float row[7];
+#pragma unroll
+        for (int k = 0; k < 7; ++k) row[k] = cov3D[7 * i + k];
+        cov_from_scale_rot(row, c_in);
+    } else if (d.flags & FS_RASTER_COV_FULL) {  // row-major 3x3, upper triangle
         const float* cr = cov3D + 9 * i;
         c_in[0] = cr[0]; c_in[1] = cr[1]; c_in[2] = cr[2]; c_in[3] = cr[4]; c_in[4] = cr[5]; c_in[5] = cr[8];
     } else {
@@ -543,7 +550,7 @@ struct ViewBuffers {
 #define FS_PRE_WAVES 6
 #endif
 #define FS_PRE_OCC __attribute__((amdgpu_waves_per_eu(FS_PRE_WAVES, FS_PRE_WAVES)))
-template <int CH>
+template <int CH, bool SR>
 __global__ __launch_bounds__(256) FS_PRE_OCC void preprocess_views_kernel(
     fs_raster_dims d, int v, const float* __restrict__ means3D, const float* __restrict__ cov3D,
     const float* __restrict__ shs, const float* __restrict__ colors, const float* __restrict__ opacities,
@@ -577,7 +584,7 @@ __global__ __launch_bounds__(256) FS_PRE_OCC void preprocess_views_kernel(
         float c_in[6] = {0, 0, 0, 0, 0, 0};
         float op = 0.0f;
         if (live) {
-            load_mean_cov(d, means3D, cov3D, i, p_in, c_in);
+            load_mean_cov<SR>(d, means3D, cov3D, i, p_in, c_in);
             op = opacities[i];
         }
         if (wave < CH) {   // (one wavefront per chunk writes; the others loaded the same rows -- L1 hits -- for nothing: 40 B)
@@ -1369,6 +1376,7 @@ static int check_forward_args(const fs_raster_dims& d, const float* means3D, con
                               const float* colors_precomp, const float* opacities, const int32_t* radii, int64_t cap)
 {
     if (d.N < 0 || d.H <= 0 || d.W <= 0 || cap < 1) return FS_ERR_INVALID_ARG;
+    if ((d.flags & FS_RASTER_SCALE_ROT) && (d.flags & FS_RASTER_COV_FULL)) return FS_ERR_INVALID_ARG;  // two row layouts
     if (d.N > 0) {  // an empty Gaussian set renders the background; its arrays may be NULL
         if (!means3D || !cov3D || !opacities || !radii) return FS_ERR_INVALID_ARG;
         if ((shs == nullptr) == (colors_precomp == nullptr)) return FS_ERR_INVALID_ARG;
@@ -1406,10 +1414,14 @@ static int launch_binning(const fs_raster_dims& d, int nv, const float* means3D,
                            + (size_t)(10 * 64 * ch) * sizeof(float);
         const dim3 grid((d.N + 64 * ch - 1) / (64 * ch));
         ScopedStage prof_(kStPreprocess, st, nv);
-#define FS_LAUNCH_PRE(CH)                                                                                            \
-        hipLaunchKernelGGL((preprocess_views_kernel<CH>), grid, dim3(256), lds, st, d, nv, means3D, cov3D, shs,      \
+#define FS_LAUNCH_PRE(CH, SR)                                                                                        \
+        hipLaunchKernelGGL((preprocess_views_kernel<CH, SR>), grid, dim3(256), lds, st, d, nv, means3D, cov3D, shs,  \
                            colors_precomp, opacities, viewmatrix, projmatrix, campos, tanfov, scale, vb, tile_cap)
-        if (ch == 1) FS_LAUNCH_PRE(1); else if (ch == 2) FS_LAUNCH_PRE(2); else FS_LAUNCH_PRE(4);
+        if (d.flags & FS_RASTER_SCALE_ROT) {
+            if (ch == 1) FS_LAUNCH_PRE(1, true); else if (ch == 2) FS_LAUNCH_PRE(2, true); else FS_LAUNCH_PRE(4, true);
+        } else {
+            if (ch == 1) FS_LAUNCH_PRE(1, false); else if (ch == 2) FS_LAUNCH_PRE(2, false); else FS_LAUNCH_PRE(4, false);
+        }
 #undef FS_LAUNCH_PRE
     }
     FS_CHECK_LAUNCH("preprocess_views");
@@ -1453,7 +1465,32 @@ static int launch_blend(const fs_raster_dims& d, const float* bg, void* geom, vo
     return FS_OK;
 }
 
+// (scales, rotation) rows [N,7] -> covariances [N,6] with the projection's own device function (fs_raster_cov3d_from_scale_rot)
+__global__ __launch_bounds__(256) void cov3d_from_scale_rot_kernel(int N, const float* __restrict__ rows,
+                                                                   float* __restrict__ cov)
+{
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < N; i += gridDim.x * 256) {
+        float row[7], c[6];
+#pragma unroll
+        for (int k = 0; k < 7; ++k) row[k] = rows[7 * (size_t)i + k];
+        cov_from_scale_rot(row, c);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) cov[6 * (size_t)i + k] = c[k];
+    }
+}
 }  // namespace fs
+
+FS_API int fs_raster_cov3d_from_scale_rot(int32_t N, const float* rows7, float* cov6_out, void* stream_)
+{
+    if (N < 0) return FS_ERR_INVALID_ARG;
+    if (N == 0) return FS_OK;
+    if (!rows7 || !cov6_out) return FS_ERR_INVALID_ARG;
+    const int nb = (N + 255) / 256;
+    const unsigned blocks = (unsigned)(nb < 8192 ? nb : 8192);
+    hipLaunchKernelGGL(fs::cov3d_from_scale_rot_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, N, rows7, cov6_out);
+    FS_CHECK_LAUNCH("cov3d_from_scale_rot");
+    return FS_OK;
+}
 
 FS_API int fs_raster_forward(const fs_raster_dims* dims, const float* means3D, const float* cov3D,
                              const float* shs, const float* colors_precomp, const float* opacities,

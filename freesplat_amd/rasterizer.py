@@ -193,17 +193,19 @@ def _f32c(t: Tensor, name: str, allow_half: bool = False) -> Tensor:
 
 
 def make_dims(N, M, settings: GaussianRasterizationSettings, sh_fp16: bool = False, native_layout: bool = False,
-              inference: bool = False) -> _lib.RasterDims:
+              inference: bool = False, scale_rot: bool = False) -> _lib.RasterDims:
     """`native_layout`: shs is the reference's harmonics [N,3,M] and cov3D its covariances [N,3,3]
     (FS_RASTER_SH_CHANNEL_MAJOR | FS_RASTER_COV_FULL) instead of the rasterizer API's [N,M,3] / [N,6].
-    `inference`: no backward will follow (FS_RASTER_NO_BACKWARD_STATE: the blend skips the contributor count)."""
+    `inference`: no backward will follow (FS_RASTER_NO_BACKWARD_STATE: the blend skips the contributor count).
+    `scale_rot`: cov3D holds (scales, rotation) rows [N,7] (FS_RASTER_SCALE_ROT; not with `native_layout`)."""
     d = _lib.RasterDims()
     d.N, d.M = int(N), int(M)
     d.H, d.W = int(settings.image_height), int(settings.image_width)
     d.sh_degree = int(settings.sh_degree)
     d.tanfovx, d.tanfovy = float(settings.tanfovx), float(settings.tanfovy)
     d.flags = ((_lib.RASTER_TILE_CULL if TILE_CULL else 0) | (_lib.RASTER_SH_FP16 if sh_fp16 else 0)
-               | (_lib.RASTER_FAST_EXP if FAST_EXP else 0) | (_lib.RASTER_NO_BACKWARD_STATE if inference else 0))
+               | (_lib.RASTER_FAST_EXP if FAST_EXP else 0) | (_lib.RASTER_NO_BACKWARD_STATE if inference else 0)
+               | (_lib.RASTER_SCALE_ROT if scale_rot else 0))
     if native_layout:
         d.flags |= _lib.RASTER_SH_CHANNEL_MAJOR | _lib.RASTER_COV_FULL
     return d
@@ -254,9 +256,9 @@ def rasterize_forward_checked(dims, means3D, cov3D, shs, colors, opacities, bg, 
 
 
 def rasterize_backward(rs: RasterState, means3D, cov3D, shs, colors, opacities, g_color, g_depth, out=None,
-                       accumulate: bool = False):
+                       accumulate: bool = False, g_alpha=None):
     """Launch the backward of one view.  `out` = dict of preallocated gradient tensors (for the
-    multi-view accumulate path) or None to allocate."""
+    multi-view accumulate path) or None to allocate.  `g_alpha` [H,W] | None: cotangent of the accumulated alpha."""
     dev = means3D.device
     d = backward_dims(rs.dims)
     N = d.N
@@ -278,23 +280,26 @@ def rasterize_backward(rs: RasterState, means3D, cov3D, shs, colors, opacities, 
     g_color = g_color.contiguous()
     if g_depth is not None:
         g_depth = g_depth.contiguous()
+    if g_alpha is not None:
+        g_alpha = g_alpha.contiguous()
     p = _lib.ptr
-    _lib.check(_lib.lib().fs_raster_backward(
+    _lib.check(_lib.lib().fs_raster_backward_alpha(
         C.byref(d), p(means3D), p(cov3D), p(shs), p(colors), p(opacities), p(rs.bg), p(rs.view), p(rs.proj),
         p(rs.campos), p(rs.tanfov), p(rs.scale), p(rs.geom), p(rs.binning), p(rs.image), p(rs.counters), p(g_color),
-        p(g_depth), p(scratch),
+        p(g_depth), p(g_alpha), p(scratch),
         p(out["means3D"]), p(out["means2D"]), p(out["cov3D"]), p(out["shs"]), p(out["colors"]),
-        p(out["opacities"]), 1 if accumulate else 0, _lib.current_stream()), "fs_raster_backward")
+        p(out["opacities"]), 1 if accumulate else 0, _lib.current_stream()), "fs_raster_backward_alpha")
     return out
 
 
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, means3D, means2D, shs, colors_precomp, opacities, cov3D, settings):
+    def forward(ctx, means3D, means2D, shs, colors_precomp, opacities, cov3D, settings, scale_rot=False):
+        # scale_rot: cov3D = (scales, rotation) rows [N,7] (FS_RASTER_SCALE_ROT), else the covariances [N,6]
         N = means3D.shape[0]
         M = 0 if shs is None else shs.shape[1]
         dims = make_dims(N, M, settings, sh_fp16=shs is not None and shs.dtype == torch.float16,
-                         inference=not any(ctx.needs_input_grad[:6]))
+                         inference=not any(ctx.needs_input_grad[:6]), scale_rot=scale_rot)
         bg = _f32c(settings.bg, "bg")
         view = _f32c(settings.viewmatrix, "viewmatrix")
         proj = _f32c(settings.projmatrix, "projmatrix")
@@ -311,20 +316,18 @@ class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_color, _g_radii, g_depth, g_alpha):
         means3D, cov3D, shs, colors, opacities = ctx.saved_tensors
-        if g_alpha is not None:
-            raise NotImplementedError("gradient through the accumulated-alpha output is not supported "
-                                      "(no reference caller uses it; cuda_splatting.py:120)")
-        if g_color is None and g_depth is None:
-            return (None,) * 7
-        g = rasterize_backward(ctx.rs, means3D, cov3D, shs, colors, opacities, g_color, g_depth)
+        if g_color is None and g_depth is None and g_alpha is None:
+            return (None,) * 8
+        g = rasterize_backward(ctx.rs, means3D, cov3D, shs, colors, opacities, g_color, g_depth, g_alpha=g_alpha)
         g_shs = g["shs"] if (shs is None or shs.dtype == torch.float32) else g["shs"].to(shs.dtype)
-        return g["means3D"], g["means2D"], g_shs, g["colors"], g["opacities"], g["cov3D"], None
+        return g["means3D"], g["means2D"], g_shs, g["colors"], g["opacities"], g["cov3D"], None, None
 
 
 def build_cov3d(scales: Tensor, rotations: Tensor, scale_modifier: float) -> Tensor:
     """cov3D 6-vector from scales [N,3] and rotations [N,4] (w,x,y,z) -- the (scales, rotations)
-    input form of the original extension; plain differentiable torch ops (host-side plumbing, not
-    on FreeSplat's path, which always passes cov3D_precomp: cuda_splatting.py:126)."""
+    input form of the original extension, as plain differentiable torch ops.  The definition the kernels follow
+    (FS_RASTER_SCALE_ROT forms the same covariance in registers; GaussianRasterizer no longer calls this): kept as the
+    eager yardstick of the tests and profiles/scale_rot_alpha_bench.py."""
     q = rotations / rotations.norm(dim=-1, keepdim=True)
     r, x, y, z = q.unbind(-1)
     R = torch.stack([
@@ -352,9 +355,17 @@ class GaussianRasterizer(nn.Module):
             raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
         means3D = _f32c(means3D, "means3D")
         N = means3D.shape[0]
-        if cov3D_precomp is None:
-            cov3D_precomp = build_cov3d(scales, rotations, float(s.scale_modifier))
-        cov3D = _f32c(cov3D_precomp, "cov3D_precomp").reshape(N, 6)
+        scale_rot = cov3D_precomp is None
+        if scale_rot:
+            # (scales, rotations): one [N,7] row per Gaussian, the covariance is formed in the kernels (FS_RASTER_SCALE_ROT);
+            # autograd of the cat splits the row gradients back into the two inputs
+            scales = _f32c(scales, "scales").reshape(N, 3)
+            rotations = _f32c(rotations, "rotations").reshape(N, 4)
+            if float(s.scale_modifier) != 1.0:
+                scales = scales * float(s.scale_modifier)
+            cov3D = torch.cat([scales, rotations], 1)
+        else:
+            cov3D = _f32c(cov3D_precomp, "cov3D_precomp").reshape(N, 6)
         opac = _f32c(opacities, "opacities").reshape(N)
         if shs is not None:
             shs = _f32c(shs, "shs", allow_half=True)   # fp16 = storage-only SH (FS_RASTER_SH_FP16)
@@ -367,7 +378,7 @@ class GaussianRasterizer(nn.Module):
             colors_precomp = _f32c(colors_precomp, "colors_precomp").reshape(N, 3)
         if means2D is None:
             means2D = torch.zeros(N, 3, dtype=torch.float32, device=means3D.device)
-        return _RasterizeGaussians.apply(means3D, means2D, shs, colors_precomp, opac, cov3D, s)
+        return _RasterizeGaussians.apply(means3D, means2D, shs, colors_precomp, opac, cov3D, s, scale_rot)
 
 
 # --- debug views into the opaque buffers (tests only) -------------------------------------------

@@ -50,8 +50,9 @@ const char* fs_version(void);
  * overflow, geom without the mask / depth arrays; fused sort + blend).  8 = the evaluation metrics (fs_image_metrics,
  * fs_depth_metrics).  9 = deterministic backwards of the cost volume, the PTF fold and the depth tail
  * (fs_cost_volume_backward_det, fs_ptf_*_backward_det, fs_depth_tail_backward_det and their size queries); later in 9,
- * additively, fs_gaussian_head_forward_sh / _backward_sh (sh_degree 0 - 3): no existing signature changed, and a library
- * without them fails at binding time (freesplat_amd/_lib.py looks up every declared symbol). */
+ * additively, fs_gaussian_head_forward_sh / _backward_sh (sh_degree 0 - 3), then FS_RASTER_SCALE_ROT with
+ * fs_raster_cov3d_from_scale_rot and the alpha-gradient backwards fs_raster_backward(_views, _views_rows)_alpha: no existing
+ * signature changed, and a library without them fails at binding time (freesplat_amd/_lib.py looks up every declared symbol). */
 #define FS_ABI_VERSION 9
 int fs_abi_version(void);
 /* Last HIP error string observed by a failing call on this thread (never NULL). */
@@ -126,6 +127,14 @@ typedef struct fs_raster_dims {
  * order of the fp32 sums.  Costs scratch (fs_raster_backward_scratch_bytes) and time.  The forward entry points
  * accept the flag and ignore it. */
 #define FS_RASTER_DETERMINISTIC 64
+/* The original extension's other covariance form (ABI 9, additive): `cov3D` of every rasterizer forward and backward entry
+ * point holds [N,7] rows sx, sy, sz, qw, qx, qy, qz instead of the [N,6] covariance, and dL_dcov3D receives [N,7] gradient
+ * rows in the same layout.  The covariance is the one freesplat_amd.rasterizer.build_cov3d forms: the quaternion normalised,
+ * Sigma = R S S^T R^T, upper triangle -- computed in the kernels (fs_raster_cov3d_from_scale_rot gives the same bits), and its
+ * gradient goes through the normalisation (w.r.t. the unnormalised quaternion of the row).  A scale_modifier is the
+ * caller's to fold into the scales.  scale_dev (the 1/near rescale) multiplies the formed covariance by s^2 as it does a
+ * [N,6] row, i.e. the scales by s.  Combined with FS_RASTER_COV_FULL: FS_ERR_INVALID_ARG before anything is launched. */
+#define FS_RASTER_SCALE_ROT 128
 
 /* Byte sizes of the four caller-owned device buffers for (N, H, W, instance capacity):
  *   out[0] geom    : per-Gaussian screen-space state            (saved for backward)
@@ -211,6 +220,22 @@ int fs_raster_backward(const fs_raster_dims* dims, const float* means3D, const f
                        const float* dL_dcolor, const float* dL_ddepth, void* grad_scratch,
                        float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcov3D, float* dL_dshs,
                        float* dL_dcolors, float* dL_dopacities, int accumulate, void* stream);
+/* The same backward with a cotangent for the accumulated alpha too: dL_dalpha [H,W] | NULL (NULL = fs_raster_backward).
+ * Alpha = 1 - prod_j (1 - a_j), so dAlpha/da_j = T_final / (1 - a_j): it enters the blend backward beside the background term
+ * (bg . dL/dC - dL/dalpha).  Colour, depth and alpha cotangents combine freely; dL_dcolor stays required (zeros for an
+ * alpha-only loss). */
+int fs_raster_backward_alpha(const fs_raster_dims* dims, const float* means3D, const float* cov3D,
+                             const float* shs, const float* colors_precomp, const float* opacities, const float* bg,
+                             const float* viewmatrix, const float* projmatrix, const float* campos,
+                             const float* tanfov_dev, const float* scale_dev,
+                             const void* geom, const void* binning, const void* image, const uint32_t* counters,
+                             const float* dL_dcolor, const float* dL_ddepth, const float* dL_dalpha, void* grad_scratch,
+                             float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcov3D, float* dL_dshs,
+                             float* dL_dcolors, float* dL_dopacities, int accumulate, void* stream);
+
+/* FS_RASTER_SCALE_ROT rows [N,7] (sx, sy, sz, qw, qx, qy, qz) -> covariances [N,6] (upper triangle), with the device function
+ * the rasterizer kernels use, so a [N,6] render of the result is bit-identical to the [N,7] render of the rows.  Stream-ordered. */
+int fs_raster_cov3d_from_scale_rot(int32_t N, const float* rows7, float* cov6_out, void* stream);
 
 /* ------------------------------------------------------------------------------------ *
  * Plane-sweep cost volume                                                               *
@@ -592,6 +617,16 @@ int fs_raster_backward_views(const fs_raster_dims* dims, int32_t v, const float*
                              const float* dL_ddepth, void* grad_scratch, float* dL_dmeans3D, float* dL_dmeans2D,
                              float* dL_dcov3D, float* dL_dshs, float* dL_dcolors, float* dL_dopacities,
                              int32_t accumulate, int32_t n_streams, void* const* streams, void* main_stream);
+/* The same with alpha cotangents dL_dalpha [v,H,W] | NULL (see fs_raster_backward_alpha). */
+int fs_raster_backward_views_alpha(const fs_raster_dims* dims, int32_t v, const float* means3D, const float* cov3D,
+                                   const float* shs, const float* colors_precomp, const float* opacities, const float* bg,
+                                   const float* viewmatrix, const float* projmatrix, const float* campos,
+                                   const float* tanfov, const float* scale, const void* geom, const void* binning,
+                                   const void* image, const uint32_t* counters, const size_t strides[3], const float* dL_dcolor,
+                                   const float* dL_ddepth, const float* dL_dalpha, void* grad_scratch, float* dL_dmeans3D,
+                                   float* dL_dmeans2D, float* dL_dcov3D, float* dL_dshs, float* dL_dcolors,
+                                   float* dL_dopacities, int32_t accumulate, int32_t n_streams, void* const* streams,
+                                   void* main_stream);
 
 /* The same backward with its per-Gaussian pass restricted to rows [row0, row0 + nrows) of the Gaussian set (ABI revision 6): a
  * caller that sums the gradients over GPUs chunk by chunk (view_sharding.GradExchange("chunked")) passes with_blend = 1 with its
@@ -607,6 +642,16 @@ int fs_raster_backward_views_rows(const fs_raster_dims* dims, int32_t v, const f
                                   float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcov3D, float* dL_dshs,
                                   float* dL_dcolors, float* dL_dopacities, int32_t accumulate, int32_t n_streams,
                                   void* const* streams, void* main_stream, int32_t row0, int32_t nrows, int32_t with_blend);
+int fs_raster_backward_views_rows_alpha(const fs_raster_dims* dims, int32_t v, const float* means3D, const float* cov3D,
+                                        const float* shs, const float* colors_precomp, const float* opacities, const float* bg,
+                                        const float* viewmatrix, const float* projmatrix, const float* campos,
+                                        const float* tanfov, const float* scale, const void* geom, const void* binning,
+                                        const void* image, const uint32_t* counters, const size_t strides[3],
+                                        const float* dL_dcolor, const float* dL_ddepth, const float* dL_dalpha,
+                                        void* grad_scratch, float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcov3D,
+                                        float* dL_dshs, float* dL_dcolors, float* dL_dopacities, int32_t accumulate,
+                                        int32_t n_streams, void* const* streams, void* main_stream, int32_t row0,
+                                        int32_t nrows, int32_t with_blend);
 
 /* Bytes of `grad_scratch` the backward needs.  v = 0: fs_raster_backward (one view); v >= 1: fs_raster_backward_views(_rows)
  * with v views on n_streams streams.  Without FS_RASTER_DETERMINISTIC in dims->flags: N*12*4 (v = 0) or v*align_up(N*48, 256),
