@@ -137,6 +137,12 @@ SIGNATURES = {
     "fs_image_metrics": (C.c_int, [C.c_int32] * 4 + [_VP] * 7),
     "fs_depth_metrics_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
     "fs_depth_metrics": (C.c_int, [C.c_int32, C.c_int64, _VP, _VP, C.c_float, _VP, _VP, _VP]),
+    "fs_lpips_scratch_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "fs_lpips_saved_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "fs_lpips_layer_forward": (C.c_int, [_VP] * 3 + [C.c_int32] * 4 + [_VP] * 4),
+    "fs_lpips_layer_backward": (C.c_int, [_VP] * 5 + [C.c_int32] * 4 + [_VP] * 3),
+    "fs_lpips_prepare_forward": (C.c_int, [_VP] * 4 + [C.c_int32] * 5 + [_VP] * 2),
+    "fs_lpips_prepare_backward": (C.c_int, [_VP] * 2 + [C.c_int32] * 5 + [_VP] * 3),
     "fs_raster_scratch_slots": (C.c_int, [C.c_int32, C.c_int32]),
     "fs_raster_tile_ranges": (_VP, [_VP, C.c_int32, C.c_int32]),
     "fs_raster_point_list": (_VP, [_VP, C.c_int32, C.c_int32]),

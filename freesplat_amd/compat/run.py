@@ -13,7 +13,10 @@ does, in this order,
 
 `--dry-run` after the module name stops after step 2 and prints what was rebound (used to check the wiring against the reference tree).
 `--gpu-metrics` after the module name also rebinds the evaluation metrics (compat.patch_metrics(): compute_psnr, compute_ssim,
-depth_render_metrics on the device).  Both flags are removed from the target's argv.
+depth_render_metrics on the device).
+`--hip-lpips` after the module name (or FREESPLAT_LPIPS=hip in the environment) registers the `lpips` shim and rebinds LPIPS
+(compat.install(lpips=True), compat.patch_lpips()): the loss and the metric then run without the third-party package, from
+the weights file(s) named by FREESPLAT_LPIPS_WEIGHTS.  All three flags are removed from the target's argv.
 """
 import os
 import runpy
@@ -28,13 +31,15 @@ def main(argv=None) -> dict:
     module, rest = argv[0], argv[1:]
     dry = "--dry-run" in rest
     gpu_metrics = "--gpu-metrics" in rest
-    rest = [a for a in rest if a not in ("--dry-run", "--gpu-metrics")]
+    hip_lpips = "--hip-lpips" in rest or os.environ.get("FREESPLAT_LPIPS", "") == "hip"
+    rest = [a for a in rest if a not in ("--dry-run", "--gpu-metrics", "--hip-lpips")]
     if os.getcwd() not in sys.path:
         sys.path.insert(0, os.getcwd())
     from freesplat_amd import _lib, compat
     _lib.lib()                      # fail now, loudly, if libfreesplat_hip.so is missing: there is no fallback path
-    compat.install()
-    done = compat.patch_reference(metrics=gpu_metrics)
+    compat.install(lpips=hip_lpips)
+    # (the keyword is passed only when asked for: a plain run calls patch_reference exactly as before)
+    done = compat.patch_reference(metrics=gpu_metrics, **({"lpips": True} if hip_lpips else {}))
     for name, obj in done.items():
         print(f"[freesplat_amd] {name} -> {getattr(obj, '__module__', '?')}.{getattr(obj, '__qualname__', obj)}", file=sys.stderr)
     if dry:

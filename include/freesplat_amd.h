@@ -24,6 +24,9 @@
  *       compute_ssim and compute_psnr, src/evaluation/metrics.py:11-19, 37-52 (as called from
  *       src/model/model_wrapper.py:74-86 and src/evaluation/metric_computer.py:54-55), and the masked
  *       per-view sums of depth_render_metrics, src/model/model_wrapper.py:90-110.
+ *   fs_lpips_*
+ *       the distance head and the input side of LPIPS as src/loss/loss_lpips.py:27-55 and
+ *       src/evaluation/metrics.py:22-34 use it (the VGG-16 convolutions in between stay on torch / MIOpen).
  */
 #ifndef FREESPLAT_AMD_H
 #define FREESPLAT_AMD_H
@@ -51,7 +54,8 @@ const char* fs_version(void);
  * fs_depth_metrics).  9 = deterministic backwards of the cost volume, the PTF fold and the depth tail
  * (fs_cost_volume_backward_det, fs_ptf_*_backward_det, fs_depth_tail_backward_det and their size queries); later in 9,
  * additively, fs_gaussian_head_forward_sh / _backward_sh (sh_degree 0 - 3), then FS_RASTER_SCALE_ROT with
- * fs_raster_cov3d_from_scale_rot and the alpha-gradient backwards fs_raster_backward(_views, _views_rows)_alpha: no existing
+ * fs_raster_cov3d_from_scale_rot and the alpha-gradient backwards fs_raster_backward(_views, _views_rows)_alpha, then the
+ * LPIPS head fs_lpips_*: no existing
  * signature changed, and a library without them fails at binding time (freesplat_amd/_lib.py looks up every declared symbol). */
 #define FS_ABI_VERSION 9
 int fs_abi_version(void);
@@ -730,6 +734,40 @@ int fs_image_metrics(int32_t B, int32_t C, int32_t H, int32_t W, const float* gt
 size_t fs_depth_metrics_scratch_bytes(int32_t B, int64_t HW);
 int fs_depth_metrics(int32_t B, int64_t HW, const float* gt, const float* pred, float threshold, double* out,
                      void* scratch, void* stream);
+
+/* ------------------------------------------------------------------------------------ *
+ * LPIPS: the distance head and the input side (loss_lpips.py:27-55, metrics.py:22-34)   *
+ * ------------------------------------------------------------------------------------ *
+ * Additive to ABI 9.  The VGG-16 convolutions between the two stay the caller's (torch / MIOpen).
+ *
+ * fs_lpips_prepare_forward: in0, in1 [B,C,H,W] -> out [2B,C,H,W] (images 0..B-1 from in0, B..2B-1 from in1):
+ *   out = ((normalize ? 2 x - 1 : x) - shift[c]) / scale[c].  shift, scale: [C] device floats.
+ * fs_lpips_prepare_backward: g_out [2B,C,H,W] -> g_in0, g_in1 [B,C,H,W] (written; either may be NULL, not both).
+ *
+ * fs_lpips_layer_forward: f0, f1 [B,C,H,W] fp32 contiguous NCHW, w [C] ->
+ *   dist[b] += mean_{h,w} sum_c w_c (f0_c / (|f0| + eps) - f1_c / (|f1| + eps))^2,  eps = 1e-10, |.| the L2 norm over the
+ *   channels of a pixel.  ADDS: the caller zeroes dist [B] once and calls once per tap layer.  The differences are formed
+ *   directly, so identical maps give exactly 0 and nearly identical ones keep full relative accuracy.
+ *   saved: fs_lpips_saved_bytes(B, C, H, W) bytes = four floats per pixel (|f0|, |f1| and two channel sums) for the backward.
+ *   scratch: fs_lpips_scratch_bytes(B, C, H, W) bytes (one partial per 64-pixel workgroup; dead when the call's work is done).
+ *   Deterministic always: fixed-order sums, an fp64 finishing step per image, no atomics; an image's value does not depend
+ *   on the batch it is in.
+ * fs_lpips_layer_backward: g_dist [B] -> g_f0 and g_f1 (written, not accumulated; either may be NULL, not both: the
+ *   target of a loss carries no gradient) from one read of f0, f1 and `saved`.  ZERO-NORM PIXELS: where all C channels of a map are 0 torch's autograd returns NaN (sqrt's backward at
+ *   0); here d|f|/df is taken as 0 there, so the gradient is finite: g_f_c = +-2 w_c d_c / (|f| + eps) * g_dist[b] / (H W)
+ *   with |f| = 0.
+ * Sizes <= 0 or a NULL required pointer: FS_ERR_INVALID_ARG (the size queries return 0); C > 512: FS_ERR_UNSUPPORTED
+ * (a thread keeps 32 channels of both maps in registers, 16 wavefronts share a pixel). */
+size_t fs_lpips_scratch_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
+size_t fs_lpips_saved_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
+int fs_lpips_layer_forward(const float* f0, const float* f1, const float* w, int32_t B, int32_t C, int32_t H, int32_t W,
+                           float* dist, float* saved, void* scratch, void* stream);
+int fs_lpips_layer_backward(const float* g_dist, const float* f0, const float* f1, const float* w, const float* saved,
+                            int32_t B, int32_t C, int32_t H, int32_t W, float* g_f0, float* g_f1, void* stream);
+int fs_lpips_prepare_forward(const float* in0, const float* in1, const float* shift, const float* scale, int32_t B,
+                             int32_t C, int32_t H, int32_t W, int32_t normalize, float* out, void* stream);
+int fs_lpips_prepare_backward(const float* g_out, const float* scale, int32_t B, int32_t C, int32_t H, int32_t W,
+                              int32_t normalize, float* g_in0, float* g_in1, void* stream);
 
 /* Debug/test accessors into the opaque buffers (device pointers, no copies). */
 const uint32_t* fs_raster_tile_ranges(const void* binning, int32_t H, int32_t W);  /* [T+1] offsets */
