@@ -143,6 +143,10 @@ SIGNATURES = {
     "fs_lpips_layer_backward": (C.c_int, [_VP] * 5 + [C.c_int32] * 4 + [_VP] * 3),
     "fs_lpips_prepare_forward": (C.c_int, [_VP] * 4 + [C.c_int32] * 5 + [_VP] * 2),
     "fs_lpips_prepare_backward": (C.c_int, [_VP] * 2 + [C.c_int32] * 5 + [_VP] * 3),
+    "fs_skip_latents_saved_bytes": (C.c_size_t, [C.c_int32] * 3),
+    "fs_skip_latents_scratch_bytes": (C.c_size_t, [C.c_int32] * 3),
+    "fs_skip_latents_forward": (C.c_int, [C.c_int32] * 6 + [_VP] * 8),
+    "fs_skip_latents_backward": (C.c_int, [C.c_int32] * 6 + [_VP] * 9),
     "fs_raster_scratch_slots": (C.c_int, [C.c_int32, C.c_int32]),
     "fs_raster_tile_ranges": (_VP, [_VP, C.c_int32, C.c_int32]),
     "fs_raster_point_list": (_VP, [_VP, C.c_int32, C.c_int32]),

@@ -3,13 +3,15 @@ reference's order, with the hot-path glue between them replaced.
 
     compat.patch_reference() binds   src.model.encoder.encoder_freesplat.EncoderFreeSplat.forward = encoder_forward
 
-What is NOT ours stays a module call on `self` (backbone, cv_encoder, depth_decoder, high_resolution_skip,
-to_gaussians, weight_embedding: out of scope).  What changes against
+What is NOT ours stays a module call on `self` (backbone, cv_encoder, depth_decoder, to_gaussians, weight_embedding: out of
+scope).  What changes against
 /root/reference/src/model/encoder/encoder_freesplat.py:190-429:
   * :216-288  the V-fold `repeat` + `gather` of extrinsics / intrinsics / IMAGES / matching features that prepares the
               cost-volume call -> encoder_glue.prepare_cost_volume_inputs (source rows indexed directly; the gathered
               source images, `src_image`, are never used by the reference and are not formed);
   * :280-288  self.cost_volume(...)                         (HIP sweep once patch_reference has rebound the class)
+  * :302-316  self.high_resolution_skip[0](images) + the latents' sum and rearrangement   (fs_skip_latents_*: the 7x7
+              convolution + ReLU inside the latent pack, no [V, 64, h, w] map; FREESPLAT_SKIP_FUSED=0 keeps the module call)
   * :317-326  self.gaussian_adapter.forward(fusion=True)    (fs_unproject_*: no b x V python loop)
   * :364-368  self.fuse_gaussians(...)                      (fs_ptf_fold)
   * :371-386  to_gaussians + gaussian_adapter.forward(fusion=False, coords=...)   (fs_gaussian_head_*)
@@ -19,6 +21,7 @@ reference modules (CPU) and comparing every entry of the two dictionaries.
 """
 from __future__ import annotations
 
+import os
 from typing import Optional
 
 import torch
@@ -33,6 +36,25 @@ def _pixel_grid(h: int, w: int, device) -> Tensor:
     xs = (torch.arange(w, device=device) + 0.5) / w
     gx, gy = torch.meshgrid(xs, ys, indexing="xy")
     return torch.stack([gx, gy], dim=-1).reshape(h * w, 1, 2)
+
+
+def fused_skip_layer(module) -> Optional[nn.Conv2d]:
+    """The convolution of `module` when it is exactly the reference's full-resolution skip layer,
+    Sequential(Conv2d(3, 64, 7, stride 1, padding 3, with bias), ReLU) (encoder_freesplat.py:124-128), and
+    FREESPLAT_SKIP_FUSED is not 0; None otherwise (3x3 stand-ins, the stride-2 layer, a missing bias or ReLU, ...): only that
+    layer has a fused kernel (gaussian_adapter.skip_latents).  The environment variable is read on every call, so it can be
+    switched between two forwards of one process."""
+    if os.environ.get("FREESPLAT_SKIP_FUSED", "1") == "0":
+        return None
+    if not isinstance(module, nn.Sequential) or len(module) != 2:
+        return None
+    conv, act = module[0], module[1]
+    if type(conv) is not nn.Conv2d or type(act) is not nn.ReLU:
+        return None
+    ok = (conv.in_channels == 3 and conv.out_channels == 64 and conv.kernel_size == (7, 7) and conv.stride == (1, 1)
+          and conv.padding == (3, 3) and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == "zeros"
+          and conv.bias is not None and conv.weight.dtype == torch.float32)
+    return conv if ok else None
 
 
 def _bv(t: Tensor, b: int) -> Tensor:
@@ -65,14 +87,24 @@ def encoder_forward(self, context, global_step: int, deterministic: bool = False
     # per-pixel latents (+ full-resolution skip), densities, depths, depth weights
     flat_images = images.reshape(b * V, *images.shape[2:])
     head = dec["output_pred_s-1_b1hw"]
-    skip = self.high_resolution_skip[0](flat_images)
-    if head.is_cuda and head.shape[1] == 65 and skip.shape[1] == 64:
-        # the fold reads pixel-major rows: head[:, 1:] + skip and the channel-major -> pixel-major move in one HIP pass each way
-        # (gaussian_adapter.latents_pack) instead of an add and three transposing 1 GB copies per training step at config 3
-        from .gaussian_adapter import latents_pack
-        lat, dens_raw = latents_pack(head, skip)
-        latents = lat.reshape(b, V, h * w, -1)
-        densities = torch.sigmoid(dens_raw).reshape(b, V, h * w, 1, 1)
+    conv = fused_skip_layer(self.high_resolution_skip[0])
+    packed = None                           # (latents [(b v), h*w, 64], density logits [(b v), h*w]) from one of the HIP packs
+    if conv is not None and head.is_cuda and flat_images.is_cuda and head.shape[1] == 65 and head.dtype == torch.float32 \
+            and flat_images.dtype == torch.float32 and not (flat_images.requires_grad and torch.is_grad_enabled()):
+        # the skip convolution + ReLU inside the latent pack (gaussian_adapter.skip_latents): the [V, 64, h, w] skip map, 963 MB
+        # at config 3 and held for the backward, never exists
+        from .gaussian_adapter import skip_latents
+        packed = skip_latents(head, flat_images, conv.weight, conv.bias)
+    else:
+        skip = self.high_resolution_skip[0](flat_images)
+        if head.is_cuda and head.shape[1] == 65 and skip.shape[1] == 64:
+            # the fold reads pixel-major rows: head[:, 1:] + skip and the channel-major -> pixel-major move in one HIP pass each
+            # way (gaussian_adapter.latents_pack) instead of an add and three transposing 1 GB copies per training step at config 3
+            from .gaussian_adapter import latents_pack
+            packed = latents_pack(head, skip)
+    if packed is not None:
+        latents = packed[0].reshape(b, V, h * w, -1)
+        densities = torch.sigmoid(packed[1]).reshape(b, V, h * w, 1, 1)
     else:       # host tensors (the check against the reference tree runs this glue on the reference's own CPU modules)
         latents = (head[:, 1:] + skip).reshape(b, V, -1, h * w).transpose(-1, -2)
         densities = torch.sigmoid(_bv(head[:, :1], b))

@@ -154,6 +154,70 @@ def latents_pack(head: Tensor, skip: Tensor):
     return _LatentsPack.apply(_chk(head, "head"), _chk(skip, "skip"))
 
 
+class _SkipLatents(torch.autograd.Function):
+    """(head [N,65,h,w], images [N,3,h,w], weight [64,3,7,7], bias [64]) -> (latents [N, h*w, 64], dens [N, h*w]) with the skip
+    convolution + ReLU computed inside the pack: fs_skip_latents_forward / _backward.  Kept for the backward: the images (an
+    input) and one bit per (pixel, channel)."""
+
+    @staticmethod
+    def forward(ctx, head, images, weight, bias):
+        N, h, w = head.shape[0], head.shape[2], head.shape[3]
+        dev = head.device
+        lat = torch.empty(N, h * w, 64, dtype=torch.float32, device=dev)
+        dens = torch.empty(N, h * w, dtype=torch.float32, device=dev)
+        L = _lib.lib()
+        need_w = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
+        mask = torch.empty(L.fs_skip_latents_saved_bytes(N, h, w), dtype=torch.uint8, device=dev) if need_w else None
+        p = _lib.ptr
+        _lib.check(L.fs_skip_latents_forward(N, h, w, 3, 64, 7, p(head), p(images), p(weight), p(bias), p(lat), p(dens), p(mask),
+                                             _lib.current_stream()), "fs_skip_latents_forward")
+        if need_w:
+            ctx.save_for_backward(images, mask)
+        ctx.dims = (N, h, w)
+        ctx.set_materialize_grads(False)
+        return lat, dens
+
+    @staticmethod
+    def backward(ctx, g_lat, g_dens):
+        N, h, w = ctx.dims
+        need_h, _, need_wt, need_b = ctx.needs_input_grad
+        if (g_lat is None and g_dens is None) or not (need_h or need_wt or need_b):
+            return None, None, None, None
+        dev = g_lat.device if g_lat is not None else g_dens.device
+        images, mask = ctx.saved_tensors if (need_wt or need_b) else (None, None)
+        L = _lib.lib()
+        g_head = torch.empty(N, 65, h, w, dtype=torch.float32, device=dev) if need_h else None
+        g_weight = torch.empty(64, 3, 7, 7, dtype=torch.float32, device=dev) if need_wt else None
+        g_bias = torch.empty(64, dtype=torch.float32, device=dev) if need_b else None
+        scratch = torch.empty(L.fs_skip_latents_scratch_bytes(N, h, w), dtype=torch.uint8, device=dev) if images is not None else None
+        gl = None if g_lat is None else g_lat.float().contiguous()
+        gd = None if g_dens is None else g_dens.float().contiguous()
+        p = _lib.ptr
+        _lib.check(L.fs_skip_latents_backward(N, h, w, 3, 64, 7, p(images), p(mask), p(gl), p(gd), p(g_head), p(g_weight),
+                                              p(g_bias), p(scratch), _lib.current_stream()), "fs_skip_latents_backward")
+        return g_head, None, g_weight, g_bias
+
+
+def skip_latents(head: Tensor, images: Tensor, weight: Tensor, bias: Tensor):
+    """`latents_pack(head, relu(conv2d(images, weight, bias, stride=1, padding=3)))` for the encoder's full-resolution skip
+    layer Conv2d(3, 64, 7, 1, 3) + ReLU (encoder_freesplat.py:124-128, :302-316) without the [(b v), 64, h, w] skip map:
+        latents [(b v), h*w, 64] = rearrange(head[:, 1:] + relu(conv(images)), "n c h w -> n (h w) c"),   dens = head[:, 0]
+    -- one HIP pass each way on the fp32 matrix instruction (csrc/skip_conv.hip).  Gradients for `head`, `weight` and `bias`
+    (bit-reproducible: no atomics); the images get none, and images that require one are refused."""
+    if head.device.type != "cuda":
+        raise RuntimeError(f"freesplat_amd skip_latents: tensors must live on a HIP device (got {head.device}); no CPU path")
+    if head.dim() != 4 or images.dim() != 4 or head.shape[1] != 65 or images.shape[1] != 3 or head.shape[0] != images.shape[0] \
+            or head.shape[2:] != images.shape[2:]:
+        raise RuntimeError(f"skip_latents: head {tuple(head.shape)} / images {tuple(images.shape)}: expected [N,65,h,w] and [N,3,h,w]")
+    if tuple(weight.shape) != (64, 3, 7, 7) or tuple(bias.shape) != (64,):
+        raise RuntimeError(f"skip_latents: weight {tuple(weight.shape)} / bias {tuple(bias.shape)}: expected the tensors of "
+                           "Conv2d(3, 64, 7, stride 1, padding 3), [64,3,7,7] and [64]")
+    if images.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError("skip_latents: the fused skip branch gives the images no gradient; use the convolution module and "
+                           "latents_pack when the images require one")
+    return _SkipLatents.apply(_chk(head, "head"), _chk(images, "images"), _chk(weight, "weight"), _chk(bias, "bias"))
+
+
 class GaussianAdapter(nn.Module):
     def __init__(self, cfg: GaussianAdapterCfg):
         super().__init__()

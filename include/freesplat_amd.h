@@ -27,6 +27,9 @@
  *   fs_lpips_*
  *       the distance head and the input side of LPIPS as src/loss/loss_lpips.py:27-55 and
  *       src/evaluation/metrics.py:22-34 use it (the VGG-16 convolutions in between stay on torch / MIOpen).
+ *   fs_skip_latents_*
+ *       high_resolution_skip[0] (Conv2d(3, 64, 7, 1, 3) + ReLU, src/model/encoder/encoder_freesplat.py:124-128) and the
+ *       sum and rearrangement that consume it (:302-316).
  */
 #ifndef FREESPLAT_AMD_H
 #define FREESPLAT_AMD_H
@@ -55,7 +58,7 @@ const char* fs_version(void);
  * (fs_cost_volume_backward_det, fs_ptf_*_backward_det, fs_depth_tail_backward_det and their size queries); later in 9,
  * additively, fs_gaussian_head_forward_sh / _backward_sh (sh_degree 0 - 3), then FS_RASTER_SCALE_ROT with
  * fs_raster_cov3d_from_scale_rot and the alpha-gradient backwards fs_raster_backward(_views, _views_rows)_alpha, then the
- * LPIPS head fs_lpips_*: no existing
+ * LPIPS head fs_lpips_*, then the fused skip branch fs_skip_latents_*: no existing
  * signature changed, and a library without them fails at binding time (freesplat_amd/_lib.py looks up every declared symbol). */
 #define FS_ABI_VERSION 9
 int fs_abi_version(void);
@@ -768,6 +771,32 @@ int fs_lpips_prepare_forward(const float* in0, const float* in1, const float* sh
                              int32_t C, int32_t H, int32_t W, int32_t normalize, float* out, void* stream);
 int fs_lpips_prepare_backward(const float* g_out, const float* scale, int32_t B, int32_t C, int32_t H, int32_t W,
                               int32_t normalize, float* g_in0, float* g_in1, void* stream);
+
+/* ------------------------------------------------------------------------------------ *
+ * Skip branch fused into the latent pack (encoder_freesplat.py:124-128, :302-316)       *
+ * ------------------------------------------------------------------------------------ *
+ * Additive to ABI 9.  fs_latents_pack_* with the skip map computed inside the pass instead of read from memory:
+ *   latents[v, p, c] = head[v, 1 + c, p] + relu(bias[c] + sum_k weight[c, k] patch[v, p, k]),   dens[v, p] = head[v, 0, p]
+ * head [V, 65, H, W], images [V, 3, H, W], weight [64, 3, 7, 7], bias [64] (the tensors of Conv2d(3, 64, 7, stride 1,
+ * padding 3): k runs over the 3 x 7 x 7 taps, zero outside the image), latents [V, H*W, 64], dens [V, H*W] (optional).
+ * fp32 operands and accumulation on the fp32 matrix instruction; the [V, 64, H, W] map exists in neither direction.
+ * saved (optional in the forward; fs_skip_latents_saved_bytes = 8 bytes per pixel): one bit per (pixel, channel), set where
+ *   the pre-activation is > 0; the backward's only state besides the images.
+ * Backward: g_latents [V, H*W, 64] (NULL = zero), g_dens [V, H*W] (NULL = zero) -> g_head [V, 65, H, W] (every channel
+ *   written), g_weight [64, 3, 7, 7], g_bias [64]; any output may be NULL, not all.  images, saved and scratch
+ *   (fs_skip_latents_scratch_bytes; dead when the call's work is done) are needed only with g_weight or g_bias.  The images get
+ *   no gradient.  DETERMINISTIC always: per-workgroup partial sums in scratch, added in a fixed order by a second kernel, no
+ *   atomics; the partition depends on (V, H, W) only.
+ * c_in, c_out, ksize describe the convolution: anything but (3, 64, 7) returns FS_ERR_UNSUPPORTED.  Sizes <= 0 or a NULL
+ * required pointer: FS_ERR_INVALID_ARG, checked first (the size queries return 0). */
+size_t fs_skip_latents_saved_bytes(int32_t V, int32_t H, int32_t W);
+size_t fs_skip_latents_scratch_bytes(int32_t V, int32_t H, int32_t W);
+int fs_skip_latents_forward(int32_t V, int32_t H, int32_t W, int32_t c_in, int32_t c_out, int32_t ksize, const float* head,
+                            const float* images, const float* weight, const float* bias, float* latents, float* dens,
+                            void* saved, void* stream);
+int fs_skip_latents_backward(int32_t V, int32_t H, int32_t W, int32_t c_in, int32_t c_out, int32_t ksize, const float* images,
+                             const void* saved, const float* g_latents, const float* g_dens, float* g_head, float* g_weight,
+                             float* g_bias, void* scratch, void* stream);
 
 /* Debug/test accessors into the opaque buffers (device pointers, no copies). */
 const uint32_t* fs_raster_tile_ranges(const void* binning, int32_t H, int32_t W);  /* [T+1] offsets */
