@@ -159,7 +159,8 @@ int fs_raster_buffer_sizes(int32_t N, int32_t H, int32_t W, int64_t inst_capacit
  * projmatrix[16] (both as torch passes them: transposed, i.e. column-major), campos[3].
  * Outputs (device): out_color[3,H,W], out_depth[H,W] (sum z*alpha*T, un-normalised),
  * out_alpha[H,W] (1 - T_final), radii[N] (int32, 0 = culled),
- * counters[2] (uint32): {number of instances I, overflow}.  overflow == 0: fine.  overflow != 0 (I > inst_capacity, or
+ * counters[2] (uint32): {number of instances I, overflow} -- written by the call, the caller need not clear them, nor any of
+ * geom / binning / image / scratch (tests/test_memory_guards.py test_rasterizer_single_view).  overflow == 0: fine.  overflow != 0 (I > inst_capacity, or
  * a tile list longer than its key area): the value is the LARGEST TILE LIST n_max (>= 1); the image outputs are
  * undefined and the caller must retry with a capacity such that inst_capacity >= I and 4 * inst_capacity / T >= n_max
  * (the library never allocates).
@@ -425,7 +426,9 @@ int fs_ptf_fold_step(int32_t M_max, const int32_t* M_dev, int32_t h, int32_t w, 
  * activations the weight gradients pair with -- and `act` [min(M_max, h w) rounded up to 16, fs_ptf_gru_act_cols()] = the gates r, z, q in the kernels' own lane order
  * (opaque: [group of 16 pairs][r, z, q][4 blocks][64 lanes] float4), and row t of `cat` [min(M_max, h w), 176] = the pair's gathered and
  * encoded input row (exactly what fs_ptf_gru_inputs would re-gather for the backward), so that
- * fs_ptf_gru_backward_saved runs the transposed layers only.  Requires fs_ptf_gru_stream_t_rows() > 0 (the 16-pair kernels). */
+ * fs_ptf_gru_backward_saved runs the transposed layers only.  (The `act` rows padded to whole groups of 16 and the rows of the
+ * worst-case out state beyond counts[3] are the caller's to provide and never read back: tests/test_memory_guards.py
+ * test_training_fold runs the step with them poisoned.)  Requires fs_ptf_gru_stream_t_rows() > 0 (the 16-pair kernels). */
 int fs_ptf_fold_step_save(int32_t M_max, const int32_t* M_dev, int32_t h, int32_t w, const float* G, const float* X,
                           const float* R, const float* O, const float* E, const float* D, const float* g_i,
                           const float* x_i, const float* rho_i, const float* om_i, const float* d_i, const float* E_i,
@@ -677,7 +680,8 @@ size_t fs_raster_backward_scratch_bytes(const fs_raster_dims* dims, int32_t v, i
  * g_x_i [P,3], g_rho_i / g_om_i / g_d_i [P] are ACCUMULATED (zero them first; tied Gaussians may share a pixel).
  * The gradient of the GRU output rows is g_out[0] + n_keep*64 (n_fuse contiguous rows).
  * fs_ptf_gru_inputs_backward: dcat [n_fuse,176] -> g_G rows fuse_idx (stored), g_R / g_O (added), view gradients
- * (accumulated) through the gather and the positional encodings (:62-77, 485-486). */
+ * (accumulated) through the gather and the positional encodings (:62-77, 485-486).  ("zero them first" and "every row of
+ * g_in is written": tests/test_memory_guards.py test_training_fold, test_training_fold_with_tied_pixels.) */
 /* fs_ptf_cameras: kpix [V,4] = (fx w, fy h, cx w, cy h) from the normalised intrinsics Kn [V,9] and E0 [h*w,16] = view 0's
  * camera-to-world matrix on every row (the initial per-Gaussian extrinsics, encoder_freesplat.py:441), one launch: what
  * fs_ptf_fold prepares internally, for a caller that drives fs_ptf_fold_step itself (the training path). */
@@ -749,7 +753,8 @@ int fs_depth_metrics(int32_t B, int64_t HW, const float* gt, const float* pred, 
  *
  * fs_lpips_layer_forward: f0, f1 [B,C,H,W] fp32 contiguous NCHW, w [C] ->
  *   dist[b] += mean_{h,w} sum_c w_c (f0_c / (|f0| + eps) - f1_c / (|f1| + eps))^2,  eps = 1e-10, |.| the L2 norm over the
- *   channels of a pixel.  ADDS: the caller zeroes dist [B] once and calls once per tap layer.  The differences are formed
+ *   channels of a pixel.  ADDS: the caller zeroes dist [B] once and calls once per tap layer (pinned by
+ *   tests/test_memory_guards.py test_lpips_five_layers_into_one_dist; saved / scratch need no initialisation).  The differences are formed
  *   directly, so identical maps give exactly 0 and nearly identical ones keep full relative accuracy.
  *   saved: fs_lpips_saved_bytes(B, C, H, W) bytes = four floats per pixel (|f0|, |f1| and two channel sums) for the backward.
  *   scratch: fs_lpips_scratch_bytes(B, C, H, W) bytes (one partial per 64-pixel workgroup; dead when the call's work is done).

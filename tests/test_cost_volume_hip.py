@@ -76,9 +76,11 @@ def test_native_size_vs_reference_statistics_and_oracle(hip_device, sweep):
     np.testing.assert_allclose(o[0, ::16, 40, 60], stat["probe"], atol=ATOL)
 
 
-@pytest.mark.parametrize("V,K,h4,w4,D,behind,C", [(3, 2, 15, 21, 11, True, 48), (4, 3, 30, 40, 16, False, 48),
-                                                   (2, 1, 5, 7, 3, True, 48), (2, 1, 64, 64, 128, False, 48),
-                                                   (3, 2, 13, 19, 7, True, 16), (2, 1, 24, 32, 16, False, 16)])
+RAGGED_CASES = [(3, 2, 15, 21, 11, True, 48), (4, 3, 30, 40, 16, False, 48), (2, 1, 5, 7, 3, True, 48), (2, 1, 64, 64, 128, False, 48),
+                (3, 2, 13, 19, 7, True, 16), (2, 1, 24, 32, 16, False, 16)]     # (shared with tests/test_memory_guards.py)
+
+
+@pytest.mark.parametrize("V,K,h4,w4,D,behind,C", RAGGED_CASES)
 def test_ragged_shapes_vs_oracle(hip_device, V, K, h4, w4, D, behind, C, sweep):
     """C = 16 is the module's (and SimpleRecon's) default matching dimension: its own kernel instantiations."""
     import inputs

@@ -71,8 +71,7 @@ def test_backward_gather_window_covers_every_tap():
             assert np.all(fi >= 2 * Y - 2) and np.all(fi <= 2 * Y + 3), n
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("B,D,h2,w2,log_planes,which", [
+SEEDED_SHAPES = [                         # (shared with tests/test_memory_guards.py)
     (1, 7, 5, 9, True, "all"),            # D not a multiple of the four plane classes, a ragged 64-pixel workgroup
     (2, 130, 13, 21, True, "all"),        # D > 128: the backward walks two plane chunks
     (1, 300, 6, 11, False, "all"),        # three chunks, inverse-depth planes
@@ -80,7 +79,11 @@ def test_backward_gather_window_covers_every_tap():
     (2, 64, 17, 40, True, "weights"),     # only depth_weights has a gradient (no bilinear-map term)
     (2, 64, 17, 40, False, "map"),        # only the x2 map
     (2, 64, 17, 40, True, "coarse"),      # no gradient through the upsampled outputs at all
-])
+]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("B,D,h2,w2,log_planes,which", SEEDED_SHAPES)
 def test_hip_forward_and_backward_on_seeded_shapes(hip_device, B, D, h2, w2, log_planes, which):
     """Forward outputs and the gradient of the logits against the float64 oracle's autograd on shapes the goldens do not
     cover (fs_depth_tail_forward: 4 plane classes x batches of 8; fs_depth_tail_backward: the 6 x 6 gather of fine pixels
