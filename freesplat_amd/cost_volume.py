@@ -89,27 +89,21 @@ class _CostVolumeFn(torch.autograd.Function):
         # (`train` comes from the caller: INSIDE a Function's forward torch.is_grad_enabled() is always False, and
         #  ctx.needs_input_grad reports the parameters' requires_grad even under no_grad)
         train = bool(train) and strides[2] == 0 and K <= 16 and save_activations(K)
+        common = (B, K, C, h, w, D, p(cur_feats), p(src_feats), p(src_extrinsics), p(src_Ks), p(cur_invK), p(planes), *strides,
+                  p(w1), p(b1), p(w2), p(b2), p(w3), p(b3), p(ws), p(out))
+        saved = None
         if train:
             CALLS["forward_train"] += 1
             saved = torch.empty(L.fs_cost_volume_saved_bytes(B, C, h, w, D), dtype=torch.uint8, device=dev)
-            _lib.check(L.fs_cost_volume_forward_train(B, K, C, h, w, D, p(cur_feats), p(src_feats), p(src_extrinsics),
-                                                      p(src_Ks), p(cur_invK), p(planes), strides[0], strides[1], strides[2],
-                                                      p(w1), p(b1), p(w2), p(b2), p(w3), p(b3), p(ws), p(out), p(saved),
-                                                      _lib.current_stream()), "fs_cost_volume_forward_train")
+            name, own = "fs_cost_volume_forward_train", (p(saved),)
         elif layout:
             # inference on channels_last maps (pixel-major records): read in place, no re-layout pass (AVGFeatureVolumeManager.forward)
-            saved = None
-            _lib.check(L.fs_cost_volume_forward_layout(B, K, C, h, w, D, p(cur_feats), p(src_feats), p(src_extrinsics),
-                                                       p(src_Ks), p(cur_invK), p(planes), strides[0], strides[1], strides[2],
-                                                       p(w1), p(b1), p(w2), p(b2), p(w3), p(b3), p(ws), p(out), layout,
-                                                       _lib.current_stream()), "fs_cost_volume_forward_layout")
-            return out
+            name, own = "fs_cost_volume_forward_layout", (layout,)
         else:
-            saved = None
-            _lib.check(L.fs_cost_volume_forward(B, K, C, h, w, D, p(cur_feats), p(src_feats), p(src_extrinsics),
-                                                p(src_Ks), p(cur_invK), p(planes), strides[0], strides[1], strides[2],
-                                                p(w1), p(b1), p(w2), p(b2), p(w3), p(b3), p(ws), p(out),
-                                                _lib.current_stream()), "fs_cost_volume_forward")
+            name, own = "fs_cost_volume_forward", ()
+        _lib.check(getattr(L, name)(*common, *own, _lib.current_stream()), name)
+        if name == "fs_cost_volume_forward_layout":
+            return out
         ctx.save_for_backward(cur_feats, src_feats, src_extrinsics, src_Ks, cur_invK, planes, w1, b1, w2, b2, w3)
         ctx.strides, ctx.D, ctx.saved = strides, D, saved
         return out
@@ -132,31 +126,19 @@ class _CostVolumeFn(torch.autograd.Function):
         d_w1, d_b1, d_w2, d_b2, d_w3, d_b3 = e(32, C + 1), e(32), e(32, 32), e(32), e(1, 32), e(1)
         p = _lib.ptr
         g_ = g.contiguous()
+        common = (B, K, C, h, w, D, p(cur_feats), p(src_feats), p(src_extrinsics), p(src_Ks), p(cur_invK), p(planes), *strides,
+                  p(w1.detach()), p(b1.detach()), p(w2.detach()), p(b2.detach()), p(w3.detach()), p(g_), p(ws))
+        grads = (p(d_cur), p(d_src), p(d_w1), p(d_b1), p(d_w2), p(d_b2), p(d_w3), p(d_b3))
         if det:
             # no float atomics: per-view fixed-order sums of slab rows (include/freesplat_amd.h fs_cost_volume_backward_det)
             ds = torch.empty(L.fs_cost_volume_backward_det_bytes(B, K, C, h, w, D), dtype=torch.uint8, device=dev)
-            _lib.check(L.fs_cost_volume_backward_det(B, K, C, h, w, D, p(cur_feats), p(src_feats), p(src_extrinsics),
-                                                     p(src_Ks), p(cur_invK), p(planes), strides[0], strides[1], strides[2],
-                                                     p(w1.detach()), p(b1.detach()), p(w2.detach()), p(b2.detach()),
-                                                     p(w3.detach()), p(g_), p(ws), p(ctx.saved), p(d_cur), p(d_src),
-                                                     p(d_w1), p(d_b1), p(d_w2), p(d_b2), p(d_w3), p(d_b3), p(ds),
-                                                     _lib.current_stream()), "fs_cost_volume_backward_det")
-            ctx.saved = None
+            name, args = "fs_cost_volume_backward_det", (*common, p(ctx.saved), *grads, p(ds))
         elif ctx.saved is not None:
-            _lib.check(L.fs_cost_volume_backward_train(B, K, C, h, w, D, p(cur_feats), p(src_feats), p(src_extrinsics),
-                                                       p(src_Ks), p(cur_invK), p(planes), strides[0], strides[1], strides[2],
-                                                       p(w1.detach()), p(b1.detach()), p(w2.detach()), p(b2.detach()),
-                                                       p(w3.detach()), p(g_), p(ws), p(ctx.saved), p(d_cur), p(d_src),
-                                                       p(d_w1), p(d_b1), p(d_w2), p(d_b2), p(d_w3), p(d_b3),
-                                                       _lib.current_stream()), "fs_cost_volume_backward_train")
-            ctx.saved = None
+            name, args = "fs_cost_volume_backward_train", (*common, p(ctx.saved), *grads)
         else:
-            _lib.check(L.fs_cost_volume_backward(B, K, C, h, w, D, p(cur_feats), p(src_feats), p(src_extrinsics),
-                                                 p(src_Ks), p(cur_invK), p(planes), strides[0], strides[1], strides[2],
-                                                 p(w1.detach()), p(b1.detach()), p(w2.detach()), p(b2.detach()),
-                                                 p(w3.detach()), p(g_), p(ws), p(d_cur), p(d_src), p(d_w1), p(d_b1),
-                                                 p(d_w2), p(d_b2), p(d_w3), p(d_b3), _lib.current_stream()),
-                       "fs_cost_volume_backward")
+            name, args = "fs_cost_volume_backward", (*common, *grads)
+        _lib.check(getattr(L, name)(*args, _lib.current_stream()), name)
+        ctx.saved = None
         # (every gradient, the MLP's included, comes out of the one kernel: no per-point workspace, no GEMMs here)
         return d_cur, d_src, None, None, None, None, None, d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, None, None
 

@@ -1386,6 +1386,8 @@ extern "C" __attribute__((visibility("default"))) int fs_debug_cvb_trace(unsigne
 }
 #endif
 
+#include <initializer_list>
+
 using namespace fs;
 
 // Number of plane slices (grid.y): enough wavefronts for ~6+ rounds over the chip's 1024 SIMDs x 2 slots,
@@ -1415,21 +1417,123 @@ static int cv_bwd_plane_split(int B, int groups, int D)
     return split;
 }
 
+// ---- buffer layouts: ONE function per buffer knows the order and the sizes of its regions; the size queries return its
+// `total`, the launchers take their pointers from its offsets (as CvDetLayout below does for the deterministic scratch) ----
+
+static inline bool cv_channels_ok(int C) { return C == 48 || C == 16; }   // matching_dim_size of FreeSplat (48) / SimpleRecon (16)
+// floats of one source texel's record in the forward workspace: features + the projected first-layer block of the K = 1 sweep
+static inline int cv_src_record(int C) { return C + 2 * kCvU; }
+
+// forward workspace: current features [B, h*w, C] | source records [B*K, h*w, C + 32] | projection rows P
+struct CvFwdLayout { size_t o_srcT, o_pmat, total; };
+static CvFwdLayout cv_fwd_layout(int B, int K, int C, int h, int w)
+{
+    const size_t hw = (size_t)h * w;
+    CvFwdLayout L;
+    L.o_srcT = (size_t)B * C * hw * sizeof(float);
+    L.o_pmat = align_up(((size_t)B * C + (size_t)B * K * cv_src_record(C)) * hw * sizeof(float), 256);
+    L.total = L.o_pmat + align_up((size_t)B * K * 12 * 4, 256);
+    return L;
+}
+
 FS_API size_t fs_cost_volume_workspace_bytes(int32_t B, int32_t K, int32_t C, int32_t h, int32_t w)
 {
     if (B < 0 || K < 0 || C <= 0 || h <= 0 || w <= 0) return 0;
-    // current features [B, h*w, C] + source records [B*K, h*w, C + 32] (features + the projected first-layer block) + P
-    return align_up(((size_t)B * C + (size_t)B * K * (C + 2 * kCvU)) * h * w * sizeof(float), 256) + align_up((size_t)B * K * 12 * 4, 256);
+    return cv_fwd_layout(B, K, C, h, w).total;
 }
 
-// layout of the training forward's `saved` buffer: a 256-byte header (word 0: some source had an exactly zero score with
-// taps inside its image), then x = favg / cnt as [B*D][C/4 float4 chunks][h*w] (chunk q = channels 4 q .. 4 q + 3: natural order,
-// what cost_volume16_bwd_kernel<C, true> reads), then (averaged score, validity bits) as [B*D][h*w] float2
-static inline size_t cv_saved_xs_bytes(int B, int C, int h, int w, int D) { return align_up((size_t)B * D * h * w * C * sizeof(float), 256); }
+// the training forward's `saved` buffer: a header (word 0: some source had an exactly zero score with taps inside its image) |
+// x = favg / cnt as [B*D][C/4 float4 chunks][h*w] (chunk q = channels 4 q .. 4 q + 3: natural order, what
+// cost_volume16_bwd_kernel<C, true> reads) | (averaged score, validity bits) as [B*D][h*w] float2
+struct CvSavedLayout { size_t o_xs, o_xm, total; };   // (o_xs = the header's bytes)
+static CvSavedLayout cv_saved_layout(int B, int C, int h, int w, int D)
+{
+    const size_t points = (size_t)B * D * h * w;
+    CvSavedLayout L;
+    L.o_xs = 256;
+    L.o_xm = L.o_xs + align_up(points * C * sizeof(float), 256);
+    L.total = L.o_xm + align_up(points * 2 * sizeof(float), 256);
+    return L;
+}
+
 FS_API size_t fs_cost_volume_saved_bytes(int32_t B, int32_t C, int32_t h, int32_t w, int32_t D)
 {
     if (B <= 0 || C <= 0 || h <= 0 || w <= 0 || D <= 0) return 0;
-    return 256 + cv_saved_xs_bytes(B, C, h, w, D) + align_up((size_t)B * D * h * w * 2 * sizeof(float), 256);
+    return cv_saved_layout(B, C, h, w, D).total;
+}
+
+// the regions of a `saved` buffer, all null without one (the forward writes through them, the backwards only read)
+struct CvSaved { uint32_t* hdr; float* xs; float2* xm; };
+static CvSaved cv_saved_carve(const void* saved, int B, int C, int h, int w, int D)
+{
+    if (!saved) return {nullptr, nullptr, nullptr};
+    const CvSavedLayout L = cv_saved_layout(B, C, h, w, D);
+    char* base = (char*)const_cast<void*>(saved);
+    return {(uint32_t*)base, (float*)(base + L.o_xs), (float2*)(base + L.o_xm)};
+}
+
+// backward workspace: pixel-major copies curT | srcT | their gradients d_curT | d_srcT | the projection rows | and for the
+// two-pass form (constant planes, K <= 16) one record of C + 2 floats per (view, plane, pixel), recS | recM, | the inverse plane
+// homographies.  Without `two_pass` the last three regions are left out (empty, at the end).
+struct CvBwdLayout { size_t n_cur, n_src, o_srcT, o_dcurT, o_dsrcT, o_pmat, o_recS, o_recM, o_ginv, total; };   // (n_*: floats of the maps)
+static CvBwdLayout cv_bwd_layout(int B, int K, int C, int h, int w, int D, bool two_pass)
+{
+    const size_t hw = (size_t)h * w;
+    CvBwdLayout L;
+    L.n_cur = (size_t)B * hw * C;
+    L.n_src = L.n_cur * K;
+    L.o_srcT = L.n_cur * sizeof(float);
+    L.o_dcurT = L.o_srcT + L.n_src * sizeof(float);
+    L.o_dsrcT = L.o_dcurT + L.n_cur * sizeof(float);
+    L.o_pmat = align_up((L.n_cur + L.n_src) * 2 * sizeof(float), 256);
+    L.o_recS = L.o_pmat + align_up((size_t)B * K * 12 * 4, 256);
+    L.o_recM = L.o_recS + (two_pass ? align_up((size_t)B * D * hw * C * sizeof(float), 256) : 0);
+    L.o_ginv = L.o_recM + (two_pass ? align_up((size_t)B * D * hw * 2 * sizeof(float), 256) : 0);
+    L.total = L.o_ginv + (two_pass ? align_up((size_t)B * K * D * 9 * sizeof(float), 256) : 0);
+    return L;
+}
+
+struct CvBwdWorkspace { float *curT, *srcT, *d_curT, *d_srcT, *Pmat; float4* recS; float2* recM; float* Ginv; };
+static CvBwdWorkspace cv_bwd_carve(void* workspace, const CvBwdLayout& L)
+{
+    char* base = (char*)workspace;
+    return {(float*)base, (float*)(base + L.o_srcT), (float*)(base + L.o_dcurT), (float*)(base + L.o_dsrcT),
+            (float*)(base + L.o_pmat), (float4*)(base + L.o_recS), (float2*)(base + L.o_recM), (float*)(base + L.o_ginv)};
+}
+
+// The checks common to all six entry points (FS_OK = 0 when they pass).  `required`: every pointer the entry point needs;
+// `own_valid` / `own_supported`: what only that entry point refuses.  Every FS_ERR_INVALID_ARG answer comes before any
+// FS_ERR_UNSUPPORTED one, and all of them before anything is launched.
+static int cv_check_args(int B, int K, int C, int h, int w, int D, std::initializer_list<const void*> required,
+                         bool own_valid = true, bool own_supported = true)
+{
+    if (B <= 0 || K <= 0 || h <= 0 || w <= 0 || D <= 0) return FS_ERR_INVALID_ARG;
+    if (!own_valid) return FS_ERR_INVALID_ARG;
+    for (const void* ptr : required)
+        if (!ptr) return FS_ERR_INVALID_ARG;
+    if (!own_supported) return FS_ERR_UNSUPPORTED;
+    if (!cv_channels_ok(C)) return FS_ERR_UNSUPPORTED;
+    // (the sweeps address a tap as a wave-uniform map base + a 32-bit per-lane byte offset)
+    if ((unsigned long long)h * w * cv_src_record(C) * sizeof(float) >= (1ull << 32)) return FS_ERR_UNSUPPORTED;
+    return FS_OK;
+}
+
+// The one place that turns the matching dimension (48 / 16: cv_channels_ok) and two run-time flags into template arguments:
+// f(std::integral_constant<int, C>, std::bool_constant<a>, std::bool_constant<b>).  A caller whose kernels do not depend on a
+// flag passes false for it.
+template <class F>
+static void cv_dispatch(int C, bool a, bool b, F&& f)
+{
+    auto with_b = [&](auto c, auto fa) {
+        if (b) f(c, fa, std::true_type{});
+        else f(c, fa, std::false_type{});
+    };
+    auto with_a = [&](auto c) {
+        if (a) with_b(c, std::true_type{});
+        else with_b(c, std::false_type{});
+    };
+    if (C == 48) with_a(std::integral_constant<int, 48>{});
+    else with_a(std::integral_constant<int, 16>{});
 }
 
 static int cv_forward_impl(int32_t B, int32_t K, int32_t C, int32_t h, int32_t w, int32_t D,
@@ -1440,19 +1544,15 @@ static int cv_forward_impl(int32_t B, int32_t K, int32_t C, int32_t h, int32_t w
                            const float* b1, const float* w2, const float* b2, const float* w3,
                            const float* b3, void* workspace, float* out, void* saved, int layout, void* stream_)
 {
-    if (B <= 0 || K <= 0 || h <= 0 || w <= 0 || D <= 0) return FS_ERR_INVALID_ARG;
-    if (layout < 0 || layout > 3) return FS_ERR_INVALID_ARG;
-    if (!cur_feats || !src_feats || !src_extrinsics || !src_Ks || !cur_invK || !planes || !w1 || !b1 ||
-        !w2 || !b2 || !w3 || !b3 || !workspace || !out)
-        return FS_ERR_INVALID_ARG;
-    if (C != 48 && C != 16) return FS_ERR_UNSUPPORTED;  // matching_dim_size of FreeSplat (48) / SimpleRecon (16)
-    // (the sweeps address a tap as a wave-uniform map base + a 32-bit per-lane byte offset)
-    if ((unsigned long long)h * w * (C + 2 * kCvU) * sizeof(float) >= (1ull << 32)) return FS_ERR_UNSUPPORTED;
+    if (const int refused = cv_check_args(B, K, C, h, w, D, {cur_feats, src_feats, src_extrinsics, src_Ks, cur_invK, planes, w1, b1,
+                                                             w2, b2, w3, b3, workspace, out}, layout >= 0 && layout <= 3))
+        return refused;
     hipStream_t st = (hipStream_t)stream_;
     const int hw = h * w;
+    const CvFwdLayout L = cv_fwd_layout(B, K, C, h, w);
     float* curT = (float*)workspace;
-    float* srcT = curT + (size_t)B * hw * C;
-    float* Pmat = (float*)((char*)workspace + align_up(((size_t)B * C + (size_t)B * K * (C + 2 * kCvU)) * hw * sizeof(float), 256));
+    float* srcT = (float*)((char*)workspace + L.o_srcT);
+    float* Pmat = (float*)((char*)workspace + L.o_pmat);
     {
         ScopedStage prof_(kStCostVolume, st);
         const int groups = (hw + 31) / 32;
@@ -1462,17 +1562,13 @@ static int cv_forward_impl(int32_t B, int32_t K, int32_t C, int32_t h, int32_t w
             // K = 1: first layer's feature block applied per source texel, 16 MFMAs per (group, plane); two launches
             // (the sweep reads the current view from the caller's map and forms its projection rows itself)
             const unsigned gproj = (unsigned)std::min<long long>(((long long)B * K * hw * 8 + 255) / 256, 65536);
-            if (C == 48) {
-                hipLaunchKernelGGL(cv_relayout_project_kernel<48>, dim3(gproj), dim3(256), 0, st, src_feats, srcT, w1, h, w, B * K);
-                hipLaunchKernelGGL(cost_volume_proj_kernel<24>, grid, dim3(256), 0, st, B, K, h, w, D, slices, cur_feats, srcT, src_Ks,
+            cv_dispatch(C, false, false, [&](auto c, auto, auto) {
+                constexpr int CC = decltype(c)::value;
+                hipLaunchKernelGGL(cv_relayout_project_kernel<CC>, dim3(gproj), dim3(256), 0, st, src_feats, srcT, w1, h, w, B * K);
+                hipLaunchKernelGGL(cost_volume_proj_kernel<CC / 2>, grid, dim3(256), 0, st, B, K, h, w, D, slices, cur_feats, srcT, src_Ks,
                                    src_extrinsics, cur_invK, planes, (long long)plane_stride_b, (long long)plane_stride_d,
                                    (long long)plane_stride_pix, w1, b1, w2, b2, w3, b3, out);
-            } else {
-                hipLaunchKernelGGL(cv_relayout_project_kernel<16>, dim3(gproj), dim3(256), 0, st, src_feats, srcT, w1, h, w, B * K);
-                hipLaunchKernelGGL(cost_volume_proj_kernel<8>, grid, dim3(256), 0, st, B, K, h, w, D, slices, cur_feats, srcT, src_Ks,
-                                   src_extrinsics, cur_invK, planes, (long long)plane_stride_b, (long long)plane_stride_d,
-                                   (long long)plane_stride_pix, w1, b1, w2, b2, w3, b3, out);
-            }
+            });
         } else {
             hipLaunchKernelGGL(cv_proj_kernel, dim3((B * K * 12 + 255) / 256), dim3(256), 0, st, B * K, src_Ks, src_extrinsics,
                                Pmat);
@@ -1487,27 +1583,19 @@ static int cv_forward_impl(int32_t B, int32_t K, int32_t C, int32_t h, int32_t w
             if (!(layout & 2)) { cv_relayout(false, false, src_feats, srcT, C, hw, B * K, st); srcN = srcT; }
             // (training: the general sweep for every K -- it forms the averaged features the backward wants to keep; the
             //  K = 1 projected sweep never does)
-            uint32_t* xhdr = (uint32_t*)saved;
-            float* xs = saved ? (float*)((char*)saved + 256) : nullptr;
-            float2* xm = saved ? (float2*)((char*)saved + 256 + cv_saved_xs_bytes(B, C, h, w, D)) : nullptr;
-            if (saved && hipMemsetAsync(saved, 0, 256, st) != hipSuccess) {
+            const CvSaved S = cv_saved_carve(saved, B, C, h, w, D);
+            if (saved && hipMemsetAsync(saved, 0, cv_saved_layout(B, C, h, w, D).o_xs, st) != hipSuccess) {
                 set_last_error("cost volume saved header", hipGetLastError());
                 return FS_ERR_LAUNCH;
             }
-            auto sweep16 = [&](auto kernel) {
-                hipLaunchKernelGGL(kernel, grid16, dim3(256), 0, st, B, K, h, w, D, slices16, curN, srcN, Pmat,
-                                   cur_invK, planes, (long long)plane_stride_b, (long long)plane_stride_d,
-                                   (long long)plane_stride_pix, w1, b1, w2, b2, w3, b3, out, xs, xm, xhdr);
-            };
             // (K <= 2: tap by tap at four wavefronts per SIMD; K >= 3: a source's four taps in flight at three)
-            const bool deep = K >= 3;
-            if (C == 48) {
-                if (deep) { if (saved) sweep16(cost_volume16_kernel<48, true, 4, 3>); else sweep16(cost_volume16_kernel<48, false, 4, 3>); }
-                else { if (saved) sweep16(cost_volume16_kernel<48, true, 1, 4>); else sweep16(cost_volume16_kernel<48, false, 1, 4>); }
-            } else {
-                if (deep) { if (saved) sweep16(cost_volume16_kernel<16, true, 4, 3>); else sweep16(cost_volume16_kernel<16, false, 4, 3>); }
-                else { if (saved) sweep16(cost_volume16_kernel<16, true, 1, 4>); else sweep16(cost_volume16_kernel<16, false, 1, 4>); }
-            }
+            cv_dispatch(C, saved != nullptr, K >= 3, [&](auto c, auto keep, auto deep) {
+                constexpr int CC = decltype(c)::value;
+                constexpr bool KEEP = decltype(keep)::value, DEEP = decltype(deep)::value;
+                hipLaunchKernelGGL((cost_volume16_kernel<CC, KEEP, DEEP ? 4 : 1, DEEP ? 3 : 4>), grid16, dim3(256), 0, st, B, K, h, w, D,
+                                   slices16, curN, srcN, Pmat, cur_invK, planes, (long long)plane_stride_b, (long long)plane_stride_d,
+                                   (long long)plane_stride_pix, w1, b1, w2, b2, w3, b3, out, S.xs, S.xm, S.hdr);
+            });
         }
     }
     FS_CHECK_LAUNCH("cost_volume");
@@ -1563,14 +1651,7 @@ static bool cv_bwd_two_pass(int K, int64_t plane_stride_pix)
 static size_t cv_bwd_workspace_bytes(int32_t B, int32_t K, int32_t C, int32_t h, int32_t w, int32_t D, bool two_pass)
 {
     if (B <= 0 || K <= 0 || C <= 0 || h <= 0 || w <= 0 || D <= 0) return 0;
-    const size_t hw = (size_t)h * w;
-    // pixel-major copies curT, srcT and their gradients d_curT, d_srcT; the projection rows; and for the two-pass form
-    // (constant planes, K <= 16) one record of C + 2 floats per (view, plane, pixel) and the inverse plane homographies
-    size_t n = align_up((size_t)B * (1 + (size_t)K) * C * hw * 2 * sizeof(float), 256) + align_up((size_t)B * K * 12 * 4, 256);
-    if (two_pass)
-        n += align_up((size_t)B * D * hw * C * sizeof(float), 256) + align_up((size_t)B * D * hw * 2 * sizeof(float), 256) +
-             align_up((size_t)B * K * D * 9 * sizeof(float), 256);
-    return n;
+    return cv_bwd_layout(B, K, C, h, w, D, two_pass).total;
 }
 // Upper bound for any call of these dimensions (the two-pass form's records included: B * D * h * w * (C + 2) floats, ~3 GB for
 // 10 views at 96 x 128 with D = 128) ...
@@ -1587,6 +1668,30 @@ FS_API size_t fs_cost_volume_backward_workspace_bytes_for(int32_t B, int32_t K, 
     return cv_bwd_workspace_bytes(B, K, C, h, w, D, cv_bwd_two_pass(K, plane_stride_pix));
 }
 
+// Launch pieces of both backward drivers: the preparation launch (cv_bwd_prep_kernel; `with_ginv`: the two-pass forms) ...
+static void cv_bwd_prep(hipStream_t st, int B, int K, int C, int D, bool with_ginv, const float* src_Ks,
+                        const float* src_extrinsics, const float* cur_invK, const float* planes, int64_t plane_stride_b,
+                        int64_t plane_stride_d, float* Pmat, float* Ginv, float* d_w1, float* d_b1, float* d_w2, float* d_b2,
+                        float* d_w3, float* d_b3)
+{
+    const int n_thr = std::max(std::max(B * K * 12, 32 * (C + 1)), std::max(32 * 32, with_ginv ? B * K * D : 0));
+    hipLaunchKernelGGL(cv_bwd_prep_kernel, dim3((n_thr + 255) / 256), dim3(256), 0, st, B * K, K, D, C, with_ginv ? 1 : 0, src_Ks,
+                       src_extrinsics, cur_invK, planes, (long long)plane_stride_b, (long long)plane_stride_d, Pmat, Ginv, d_w1, d_b1,
+                       d_w2, d_b2, d_w3, d_b3);
+}
+
+// ... and the grid of pass 2's source-tile sweep: one single-wavefront workgroup per (view, source, tile, plane chunk)
+struct CvTiles { int x, y, n; };
+static CvTiles cv_tiles(int h, int w)
+{
+    const int tiles_x = (w + kSgTW - 1) / kSgTW, tiles_y = (h + kSgTH - 1) / kSgTH;
+    return {tiles_x, tiles_y, tiles_x * tiles_y};
+}
+static dim3 cv_tile_sweep_grid(int B, int K, const CvTiles& tiles, int chunks)
+{
+    return dim3(8u * (unsigned)B * (unsigned)((tiles.n + 7) >> 3) * (unsigned)K * (unsigned)chunks);
+}
+
 static int cv_backward_impl(int32_t B, int32_t K, int32_t C, int32_t h, int32_t w, int32_t D,
                             const float* cur_feats, const float* src_feats,
                             const float* src_extrinsics, const float* src_Ks,
@@ -1597,86 +1702,59 @@ static int cv_backward_impl(int32_t B, int32_t K, int32_t C, int32_t h, int32_t 
                             float* d_src_feats, float* d_w1, float* d_b1, float* d_w2, float* d_b2,
                             float* d_w3, float* d_b3, const void* saved, void* stream_)
 {
-    if (B <= 0 || K <= 0 || h <= 0 || w <= 0 || D <= 0) return FS_ERR_INVALID_ARG;
-    if (!cur_feats || !src_feats || !src_extrinsics || !src_Ks || !cur_invK || !planes || !w1 || !b1 || !w2 ||
-        !b2 || !w3 || !grad_out || !workspace || !d_cur_feats || !d_src_feats || !d_w1 || !d_b1 || !d_w2 || !d_b2 ||
-        !d_w3 || !d_b3)
-        return FS_ERR_INVALID_ARG;
-    if (C != 48 && C != 16) return FS_ERR_UNSUPPORTED;
-    if ((unsigned long long)h * w * (C + 2 * kCvU) * sizeof(float) >= (1ull << 32)) return FS_ERR_UNSUPPORTED;   // (32-bit texel offsets)
+    if (const int refused = cv_check_args(B, K, C, h, w, D, {cur_feats, src_feats, src_extrinsics, src_Ks, cur_invK, planes, w1, b1,
+                                                             w2, b2, w3, grad_out, workspace, d_cur_feats, d_src_feats, d_w1, d_b1,
+                                                             d_w2, d_b2, d_w3, d_b3}))
+        return refused;
     hipStream_t st = (hipStream_t)stream_;
     const int hw = h * w;
-    const size_t n_cur = (size_t)B * hw * C, n_src = n_cur * K;
-    float* curT = (float*)workspace;
-    float* srcT = curT + n_cur;
-    float* d_curT = srcT + n_src;
-    float* d_srcT = d_curT + n_cur;
-    float* Pmat = (float*)((char*)workspace + align_up((n_cur + n_src) * 2 * sizeof(float), 256));
-    float4* recS = (float4*)((char*)Pmat + align_up((size_t)B * K * 12 * 4, 256));
-    float2* recM = (float2*)((char*)recS + align_up((size_t)B * D * hw * C * sizeof(float), 256));
-    float* Ginv = (float*)((char*)recM + align_up((size_t)B * D * hw * 2 * sizeof(float), 256));
     const bool two_pass = cv_bwd_two_pass(K, plane_stride_pix);
     if (!two_pass) saved = nullptr;   // (the one-kernel scatter form needs every source's taps: it recomputes the forward)
-    const int tiles_x = (w + kSgTW - 1) / kSgTW, tiles_y = (h + kSgTH - 1) / kSgTH, tiles = tiles_x * tiles_y;
+    const CvBwdLayout L = cv_bwd_layout(B, K, C, h, w, D, two_pass);
+    const CvBwdWorkspace W = cv_bwd_carve(workspace, L);
+    const CvTiles tiles = cv_tiles(h, w);
     // plane chunks of the source-tile sweep: one (plain stores) when there are enough tiles to fill the chip (256 CUs x
     // 11 single-wavefront workgroups), else enough chunks for one full round (their tiles then leave through atomics
     // into a zeroed map)
     int chunks = 1;
-    while ((long long)B * K * tiles * chunks < 2816 && D / (chunks * 2) >= kSgG) chunks *= 2;
+    while ((long long)B * K * tiles.n * chunks < 2816 && D / (chunks * 2) >= kSgG) chunks *= 2;
     if (const char* e = getenv("FS_CV_SG_CHUNKS")) {   // (tests: force the plain-store form, chunks = 1, at small sizes, or any split)
         const int f = atoi(e);
         if (f >= 1 && f <= D) chunks = f;
     }
     ScopedStage prof_(kStCostVolume, st);
-    {
-        const int n_thr = std::max(std::max(B * K * 12, 32 * (C + 1)), std::max(32 * 32, two_pass ? B * K * D : 0));
-        hipLaunchKernelGGL(cv_bwd_prep_kernel, dim3((n_thr + 255) / 256), dim3(256), 0, st, B * K, K, D, C, two_pass ? 1 : 0, src_Ks,
-                           src_extrinsics, cur_invK, planes, (long long)plane_stride_b, (long long)plane_stride_d, Pmat, Ginv, d_w1, d_b1,
-                           d_w2, d_b2, d_w3, d_b3);
-    }
-    if ((two_pass && chunks > 1 && hipMemsetAsync(d_src_feats, 0, n_src * sizeof(float), st) != hipSuccess) ||
-        hipMemsetAsync(d_curT, 0, (two_pass ? n_cur : n_cur + n_src) * sizeof(float), st) != hipSuccess) {
+    cv_bwd_prep(st, B, K, C, D, two_pass, src_Ks, src_extrinsics, cur_invK, planes, plane_stride_b, plane_stride_d, W.Pmat, W.Ginv,
+                d_w1, d_b1, d_w2, d_b2, d_w3, d_b3);
+    if ((two_pass && chunks > 1 && hipMemsetAsync(d_src_feats, 0, L.n_src * sizeof(float), st) != hipSuccess) ||
+        hipMemsetAsync(W.d_curT, 0, (two_pass ? L.n_cur : L.n_cur + L.n_src) * sizeof(float), st) != hipSuccess) {
         set_last_error("cost volume backward memset", hipGetLastError());
         return FS_ERR_LAUNCH;
     }
     // the two-pass form runs the 16-pixel kernels on natural-order maps, the one-kernel scatter form works on [parity][C/2] records
-    const uint32_t* xhdr = (const uint32_t*)saved;
-    const float4* xs = saved ? (const float4*)((const char*)saved + 256) : nullptr;
-    const float2* xm = saved ? (const float2*)((const char*)saved + 256 + cv_saved_xs_bytes(B, C, h, w, D)) : nullptr;
-    cv_relayout(!two_pass, false, cur_feats, curT, C, hw, B, st);
-    cv_relayout(!two_pass, false, src_feats, srcT, C, hw, B * K, st);
+    const CvSaved S = cv_saved_carve(saved, B, C, h, w, D);
+    cv_relayout(!two_pass, false, cur_feats, W.curT, C, hw, B, st);
+    cv_relayout(!two_pass, false, src_feats, W.srcT, C, hw, B * K, st);
     const int groups = (hw + 31) / 32;
     const int bslices = cv_bwd_plane_split(B, groups, D);
-    auto sweep = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(cv_grid(B, groups, bslices)), dim3(256), 0, st, B, K, h, w, D, bslices, curT, srcT,
-                           Pmat, cur_invK, planes, (long long)plane_stride_b,
-                           (long long)plane_stride_d, (long long)plane_stride_pix, w1, b1, w2, b2, w3, grad_out,
-                           d_curT, d_srcT, d_w1, d_b1, d_w2, d_b2, d_w3, d_b3);
-    };
-    auto tile_sweep = [&](auto kernel) {
-        const unsigned grid = 8u * (unsigned)B * (unsigned)((tiles + 7) >> 3) * (unsigned)K * (unsigned)chunks;
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), 0, st, B, K, h, w, D, chunks, tiles_x, tiles_y, curT,
-                           (const float4*)recS, (const float2*)recM, Pmat, Ginv, cur_invK, planes, (long long)plane_stride_b,
-                           (long long)plane_stride_d, d_src_feats);
-    };
-    auto sweep16 = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(cv_grid(B, groups, bslices)), dim3(256), 0, st, B, K, h, w, D, bslices, curT, srcT,
-                           Pmat, cur_invK, planes, (long long)plane_stride_b, (long long)plane_stride_d, w1, b1, w2, b2, w3,
-                           grad_out, d_curT, d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, recS, recM, xs, xm, xhdr);
-    };
-    if (two_pass) {
-        if (C == 48) {
-            if (saved) sweep16(cost_volume16_bwd_kernel<48, true>); else sweep16(cost_volume16_bwd_kernel<48, false>);
-            tile_sweep(cv_src_grad_kernel<48>);
+    const dim3 grid(cv_grid(B, groups, bslices));
+    cv_dispatch(C, saved != nullptr, false, [&](auto c, auto kept, auto) {
+        constexpr int CC = decltype(c)::value;
+        if (two_pass) {
+            hipLaunchKernelGGL((cost_volume16_bwd_kernel<CC, decltype(kept)::value>), grid, dim3(256), 0, st, B, K, h, w, D, bslices,
+                               W.curT, W.srcT, W.Pmat, cur_invK, planes, (long long)plane_stride_b, (long long)plane_stride_d, w1, b1,
+                               w2, b2, w3, grad_out, W.d_curT, d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, W.recS, W.recM,
+                               (const float4*)S.xs, (const float2*)S.xm, (const uint32_t*)S.hdr);
+            hipLaunchKernelGGL(cv_src_grad_kernel<CC>, cv_tile_sweep_grid(B, K, tiles, chunks), dim3(64), 0, st, B, K, h, w, D, chunks,
+                               tiles.x, tiles.y, W.curT, (const float4*)W.recS, (const float2*)W.recM, W.Pmat, W.Ginv, cur_invK, planes,
+                               (long long)plane_stride_b, (long long)plane_stride_d, d_src_feats);
         } else {
-            if (saved) sweep16(cost_volume16_bwd_kernel<16, true>); else sweep16(cost_volume16_bwd_kernel<16, false>);
-            tile_sweep(cv_src_grad_kernel<16>);
+            hipLaunchKernelGGL(cost_volume_bwd_kernel<CC / 2>, grid, dim3(256), 0, st, B, K, h, w, D, bslices, W.curT, W.srcT, W.Pmat,
+                               cur_invK, planes, (long long)plane_stride_b, (long long)plane_stride_d, (long long)plane_stride_pix,
+                               w1, b1, w2, b2, w3, grad_out, W.d_curT, W.d_srcT, d_w1, d_b1, d_w2, d_b2, d_w3, d_b3);
+            cv_relayout(true, true, W.d_srcT, d_src_feats, C, hw, B * K, st);
         }
-    } else {
-        if (C == 48) sweep(cost_volume_bwd_kernel<24>); else sweep(cost_volume_bwd_kernel<8>);
-        cv_relayout(true, true, d_srcT, d_src_feats, C, hw, B * K, st);
-    }
-    cv_relayout(!two_pass, true, d_curT, d_cur_feats, C, hw, B, st);
+    });
+    cv_relayout(!two_pass, true, W.d_curT, d_cur_feats, C, hw, B, st);
     FS_CHECK_LAUNCH("cost_volume_backward");
     return FS_OK;
 }
@@ -1731,12 +1809,11 @@ static int cv_det_chunks(int K, int tiles, int D)
 struct CvDetLayout { int slices, chunks, rows, nseg, nw; size_t o_part, o_dslab, o_sslab, total; };
 static bool cv_det_layout(int B, int K, int C, int h, int w, int D, CvDetLayout& L)
 {
-    if (B <= 0 || K <= 0 || K > 16 || h <= 0 || w <= 0 || D <= 0 || (C != 48 && C != 16)) return false;
+    if (B <= 0 || K <= 0 || K > 16 || h <= 0 || w <= 0 || D <= 0 || !cv_channels_ok(C)) return false;
     const size_t hw = (size_t)h * w;
     const int groups = (int)((hw + 31) / 32);
-    const int tiles = ((w + kSgTW - 1) / kSgTW) * ((h + kSgTH - 1) / kSgTH);
     L.slices = cv_det_slices(groups, D);
-    L.chunks = cv_det_chunks(K, tiles, D);
+    L.chunks = cv_det_chunks(K, cv_tiles(h, w).n, D);
     L.rows = groups * L.slices;
     L.nseg = (L.rows + kCvDetSeg - 1) / kCvDetSeg;
     L.nw = C == 48 ? cv_det_nw<48>() : cv_det_nw<16>();
@@ -1763,80 +1840,52 @@ FS_API int fs_cost_volume_backward_det(int32_t B, int32_t K, int32_t C, int32_t 
                                        float* d_src_feats, float* d_w1, float* d_b1, float* d_w2, float* d_b2,
                                        float* d_w3, float* d_b3, void* det_scratch, void* stream_)
 {
-    if (B <= 0 || K <= 0 || h <= 0 || w <= 0 || D <= 0) return FS_ERR_INVALID_ARG;
-    if (!cur_feats || !src_feats || !src_extrinsics || !src_Ks || !cur_invK || !planes || !w1 || !b1 || !w2 ||
-        !b2 || !w3 || !grad_out || !workspace || !d_cur_feats || !d_src_feats || !d_w1 || !d_b1 || !d_w2 || !d_b2 ||
-        !d_w3 || !d_b3 || !det_scratch)
-        return FS_ERR_INVALID_ARG;
-    if (K > 16 || plane_stride_pix != 0) return FS_ERR_UNSUPPORTED;   // (the scatter form has no deterministic variant)
-    if (C != 48 && C != 16) return FS_ERR_UNSUPPORTED;
-    if ((unsigned long long)h * w * (C + 2 * kCvU) * sizeof(float) >= (1ull << 32)) return FS_ERR_UNSUPPORTED;
+    // (own check: the scatter form, K > 16 or per-pixel planes, has no deterministic variant)
+    if (const int refused = cv_check_args(B, K, C, h, w, D, {cur_feats, src_feats, src_extrinsics, src_Ks, cur_invK, planes, w1, b1,
+                                                             w2, b2, w3, grad_out, workspace, d_cur_feats, d_src_feats, d_w1, d_b1,
+                                                             d_w2, d_b2, d_w3, d_b3, det_scratch}, true, K <= 16 && plane_stride_pix == 0))
+        return refused;
     CvDetLayout Ld;
     cv_det_layout(B, K, C, h, w, D, Ld);
     hipStream_t st = (hipStream_t)stream_;
     const int hw = h * w;
-    const size_t n_cur = (size_t)B * hw * C, n_src = n_cur * K;
-    // (the workspace layout of cv_backward_impl's two-pass form: fs_cost_volume_backward_workspace_bytes)
-    float* curT = (float*)workspace;
-    float* srcT = curT + n_cur;
-    float* d_curT = srcT + n_src;
-    float* Pmat = (float*)((char*)workspace + align_up((n_cur + n_src) * 2 * sizeof(float), 256));
-    float4* recS = (float4*)((char*)Pmat + align_up((size_t)B * K * 12 * 4, 256));
-    float2* recM = (float2*)((char*)recS + align_up((size_t)B * D * hw * C * sizeof(float), 256));
-    float* Ginv = (float*)((char*)recM + align_up((size_t)B * D * hw * 2 * sizeof(float), 256));
+    const CvBwdLayout L = cv_bwd_layout(B, K, C, h, w, D, true);
+    const CvBwdWorkspace W = cv_bwd_carve(workspace, L);
     float* wslab = (float*)det_scratch;
     float* part = (float*)((char*)det_scratch + Ld.o_part);
     float* dslab = (float*)((char*)det_scratch + Ld.o_dslab);
     float* sslab = (float*)((char*)det_scratch + Ld.o_sslab);
-    const int tiles_x = (w + kSgTW - 1) / kSgTW, tiles_y = (h + kSgTH - 1) / kSgTH, tiles = tiles_x * tiles_y;
+    const CvTiles tiles = cv_tiles(h, w);
     const int groups = (hw + 31) / 32;
     const int slices = Ld.slices, chunks = Ld.chunks;
     ScopedStage prof_(kStCostVolume, st);
-    {
-        const int n_thr = std::max(std::max(B * K * 12, 32 * (C + 1)), std::max(32 * 32, B * K * D));
-        hipLaunchKernelGGL(cv_bwd_prep_kernel, dim3((n_thr + 255) / 256), dim3(256), 0, st, B * K, K, D, C, 1, src_Ks,
-                           src_extrinsics, cur_invK, planes, (long long)plane_stride_b, (long long)plane_stride_d, Pmat, Ginv, d_w1, d_b1,
-                           d_w2, d_b2, d_w3, d_b3);
-    }
-    const uint32_t* xhdr = (const uint32_t*)saved;
-    const float4* xs = saved ? (const float4*)((const char*)saved + 256) : nullptr;
-    const float2* xm = saved ? (const float2*)((const char*)saved + 256 + cv_saved_xs_bytes(B, C, h, w, D)) : nullptr;
-    cv_relayout(false, false, cur_feats, curT, C, hw, B, st);
-    cv_relayout(false, false, src_feats, srcT, C, hw, B * K, st);
-    auto sweep16 = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(cv_grid(B, groups, slices)), dim3(256), 0, st, B, K, h, w, D, slices, curT, srcT,
-                           Pmat, cur_invK, planes, (long long)plane_stride_b, (long long)plane_stride_d, w1, b1, w2, b2, w3,
-                           grad_out, d_curT, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, recS, recM, xs, xm, xhdr,
-                           dslab, wslab);
-    };
-    auto tile_sweep = [&](auto kernel) {
-        const unsigned grid = 8u * (unsigned)B * (unsigned)((tiles + 7) >> 3) * (unsigned)K * (unsigned)chunks;
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), 0, st, B, K, h, w, D, chunks, tiles_x, tiles_y, curT,
-                           (const float4*)recS, (const float2*)recM, Pmat, Ginv, cur_invK, planes, (long long)plane_stride_b,
-                           (long long)plane_stride_d, d_src_feats, sslab);
-    };
+    cv_bwd_prep(st, B, K, C, D, true, src_Ks, src_extrinsics, cur_invK, planes, plane_stride_b, plane_stride_d, W.Pmat, W.Ginv,
+                d_w1, d_b1, d_w2, d_b2, d_w3, d_b3);
+    const CvSaved S = cv_saved_carve(saved, B, C, h, w, D);
+    cv_relayout(false, false, cur_feats, W.curT, C, hw, B, st);
+    cv_relayout(false, false, src_feats, W.srcT, C, hw, B * K, st);
     auto chunk_sum = [&](long long n, int nslabs, const float* slab, float* dst) {
         if (nslabs <= 0) return;
         const unsigned g = (unsigned)std::min<long long>((n + 255) / 256, 8192);
         hipLaunchKernelGGL(cv_det_slab_sum_kernel, dim3(g), dim3(256), 0, st, n, nslabs, slab, dst);
     };
     const dim3 gpart((unsigned)((Ld.nw + 255) / 256), (unsigned)Ld.nseg, (unsigned)B);
-    if (C == 48) {
-        if (saved) sweep16(cost_volume16_bwd_det_kernel<48, true>); else sweep16(cost_volume16_bwd_det_kernel<48, false>);
+    cv_dispatch(C, saved != nullptr, false, [&](auto c, auto kept, auto) {
+        constexpr int CC = decltype(c)::value;
+        hipLaunchKernelGGL((cost_volume16_bwd_det_kernel<CC, decltype(kept)::value>), dim3(cv_grid(B, groups, slices)), dim3(256), 0, st,
+                           B, K, h, w, D, slices, W.curT, W.srcT, W.Pmat, cur_invK, planes, (long long)plane_stride_b,
+                           (long long)plane_stride_d, w1, b1, w2, b2, w3, grad_out, W.d_curT, nullptr, nullptr, nullptr, nullptr, nullptr,
+                           nullptr, W.recS, W.recM, (const float4*)S.xs, (const float2*)S.xm, (const uint32_t*)S.hdr, dslab, wslab);
         hipLaunchKernelGGL(cv_det_wpart_kernel, gpart, dim3(256), 0, st, Ld.rows, Ld.nseg, Ld.nw, (const float*)wslab, part);
-        hipLaunchKernelGGL(cv_det_wfinal_kernel<48>, dim3((unsigned)((Ld.nw + 255) / 256)), dim3(256), 0, st, B, Ld.nseg,
+        hipLaunchKernelGGL(cv_det_wfinal_kernel<CC>, dim3((unsigned)((Ld.nw + 255) / 256)), dim3(256), 0, st, B, Ld.nseg,
                            (const float*)part, d_w1, d_b1, d_w2, d_b2, d_w3, d_b3);
-        tile_sweep(cv_src_grad_det_kernel<48>);
-    } else {
-        if (saved) sweep16(cost_volume16_bwd_det_kernel<16, true>); else sweep16(cost_volume16_bwd_det_kernel<16, false>);
-        hipLaunchKernelGGL(cv_det_wpart_kernel, gpart, dim3(256), 0, st, Ld.rows, Ld.nseg, Ld.nw, (const float*)wslab, part);
-        hipLaunchKernelGGL(cv_det_wfinal_kernel<16>, dim3((unsigned)((Ld.nw + 255) / 256)), dim3(256), 0, st, B, Ld.nseg,
-                           (const float*)part, d_w1, d_b1, d_w2, d_b2, d_w3, d_b3);
-        tile_sweep(cv_src_grad_det_kernel<16>);
-    }
-    chunk_sum((long long)n_cur, slices - 1, dslab, d_curT);
-    chunk_sum((long long)n_src, chunks - 1, sslab, d_src_feats);
-    cv_relayout(false, true, d_curT, d_cur_feats, C, hw, B, st);
+        hipLaunchKernelGGL(cv_src_grad_det_kernel<CC>, cv_tile_sweep_grid(B, K, tiles, chunks), dim3(64), 0, st, B, K, h, w, D, chunks,
+                           tiles.x, tiles.y, W.curT, (const float4*)W.recS, (const float2*)W.recM, W.Pmat, W.Ginv, cur_invK, planes,
+                           (long long)plane_stride_b, (long long)plane_stride_d, d_src_feats, sslab);
+    });
+    chunk_sum((long long)L.n_cur, slices - 1, dslab, W.d_curT);
+    chunk_sum((long long)L.n_src, chunks - 1, sslab, d_src_feats);
+    cv_relayout(false, true, W.d_curT, d_cur_feats, C, hw, B, st);
     FS_CHECK_LAUNCH("cost_volume_backward_det");
     return FS_OK;
 }

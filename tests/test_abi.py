@@ -94,9 +94,62 @@ def test_key_area_sizing_and_retry_capacity():
     assert L.fs_abi_version() == _lib.ABI_VERSION
 
 
-def test_cost_volume_rejects_maps_of_4GB_and_more():
+CV_FORWARDS = ("fs_cost_volume_forward", "fs_cost_volume_forward_layout", "fs_cost_volume_forward_train")
+CV_BACKWARDS = ("fs_cost_volume_backward", "fs_cost_volume_backward_train", "fs_cost_volume_backward_det")
+
+
+def _cv_call(name, B=1, K=1, C=48, h=8, w=8, D=8, strides=(0, 1, 0), null=None, saved=True, layout=0, det_scratch=True):
+    """One cost-volume entry point with fake non-NULL pointers; `null`: index of the required pointer to pass as NULL (forwards:
+    6 maps / cameras / planes, 6 MLP tensors, workspace, out; backwards: the same 6, 5 MLP tensors, grad_out, workspace, 8 gradients).
+    EVERY call of this helper must carry a defect the library refuses before it launches anything."""
+    import ctypes as C_
+    from freesplat_amd import _lib
+    p = C_.c_void_p(4096)
+    opt = lambda present: p if present else None
+    ptrs = [p] * (14 if name in CV_FORWARDS else 21)
+    if null is not None:
+        ptrs[null] = None
+    args = [B, K, C, h, w, D] + ptrs[:6] + list(strides)
+    if name in CV_FORWARDS:
+        args += ptrs[6:] + {"fs_cost_volume_forward": [], "fs_cost_volume_forward_layout": [layout],
+                            "fs_cost_volume_forward_train": [opt(saved)]}[name]
+    else:
+        args += ptrs[6:13] + ([] if name == "fs_cost_volume_backward" else [opt(saved)]) + ptrs[13:]
+        args += [opt(det_scratch)] if name == "fs_cost_volume_backward_det" else []
+    return getattr(_lib.lib(), name)(*args, None)
+
+
+def _cv_status_codes(name):
+    """Every FS_ERR_INVALID_ARG (-1) condition (a non-positive size, a NULL required pointer, a layout outside 0..3) is answered
+    before any FS_ERR_UNSUPPORTED (-3) one (a matching dimension other than 48 / 16, a map of 4 GB or more, K > 16 or per-pixel
+    planes for the deterministic backward)."""
+    for bad in (dict(h=0), dict(B=0), dict(D=0)):
+        assert _cv_call(name, **bad) == -1, bad
+    for C in (48, 32):
+        for i in range(14 if name in CV_FORWARDS else 21):
+            assert _cv_call(name, C=C, null=i) == -1, (C, i)
+    assert _cv_call(name, C=32) == -3
+    assert _cv_call(name, h=4096, w=4096) == -3
+    if name == "fs_cost_volume_forward_layout":
+        for C in (48, 32):
+            assert _cv_call(name, C=C, layout=4) == -1 and _cv_call(name, C=C, layout=-1) == -1
+    if name in ("fs_cost_volume_forward_train", "fs_cost_volume_backward_train"):
+        assert _cv_call(name, saved=False) == -1 and _cv_call(name, C=32, saved=False) == -1
+    if name == "fs_cost_volume_backward_det":
+        assert _cv_call(name, C=32, saved=False) == -3              # (`saved` is optional there)
+        for C in (48, 32):
+            assert _cv_call(name, C=C, det_scratch=False) == -1
+            assert _cv_call(name, C=C, K=17) == -3
+            assert _cv_call(name, C=C, strides=(512, 64, 1)) == -3
+        assert _cv_call(name, K=17, det_scratch=False) == -1 and _cv_call(name, K=17, null=0) == -1
+
+
+def test_cost_volume_rejects_maps_of_4GB_and_more(monkeypatch):
     """The sweeps address a tap as map base + 32-bit byte offset: a feature map of >= 4 GB is refused (FS_ERR_UNSUPPORTED, -3)
-    before anything is launched -- so fake non-NULL pointers are enough here, no device involved."""
+    before anything is launched -- so fake non-NULL pointers are enough here, no device involved.  All six entry points answer
+    the same arguments alike (_cv_status_codes), and the backward's size queries follow the form that will run: the
+    deterministic scratch is 0 for what that form refuses, the per-call workspace equals the upper bound for the two-pass form
+    and leaves out the record / inverse-homography regions for per-pixel planes."""
     import ctypes as C
     from freesplat_amd import _lib
     L = _lib.lib()
@@ -110,6 +163,13 @@ def test_cost_volume_rejects_maps_of_4GB_and_more():
     assert L.fs_cost_volume_forward(*fwd) == -3
     fwd[2], fwd[3] = 48, 0
     assert L.fs_cost_volume_forward(*fwd) == -1
+    for name in CV_FORWARDS + CV_BACKWARDS:
+        _cv_status_codes(name)
+    monkeypatch.delenv("FS_CV_BWD_ATOMIC", raising=False)
+    assert L.fs_cost_volume_backward_det_bytes(1, 17, 48, 8, 8, 8) == 0 and L.fs_cost_volume_backward_det_bytes(1, 1, 32, 8, 8, 8) == 0
+    assert L.fs_cost_volume_backward_workspace_bytes(2, 2, 48, 8, 8, 8) == 353792
+    assert L.fs_cost_volume_backward_workspace_bytes_for(2, 2, 48, 8, 8, 8, 0) == 353792
+    assert L.fs_cost_volume_backward_workspace_bytes_for(2, 2, 48, 8, 8, 8, 1) == 147712
 
 
 def test_every_entry_point_validates_its_arguments_before_touching_a_device():
