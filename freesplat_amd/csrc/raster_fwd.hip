@@ -1085,9 +1085,11 @@ __device__ __forceinline__ bool sort_tile_partitioned(
 // Blend loop of one wavefront = one 8x8 quadrant of the tile, fully independent of the other three (no workgroup
 // barrier): front-to-back alpha compositing over the tile's sorted list.
 //   * the list words carry a 4-bit quadrant mask (computed once at binning time): the wavefront ballots 64 entries at a
-//     time against its own bit and gathers the 48-byte records of the entries that have it one batch ahead, so the global
-//     latency of batch i+1 is covered by the blending of batch i; entries that cannot touch the quadrant cost 1/64 of a
-//     VALU test instead of a full per-pixel evaluation;
+//     time against its own bit and queues the list positions of the entries that have it (hits) in `qi` (64 slots, in
+//     LDS; `qw`: their words, when the list itself is in global memory).  Entries that cannot touch the quadrant cost
+//     1/64 of a VALU test instead of a full per-pixel evaluation;
+//   * when 64 hits wait (or the list ends) lane k takes hit k and gathers its 48-byte record, one hit batch ahead, so
+//     the global latency of batch i+1 is covered by the blending of batch i: gather and compaction are paid per 64 hits;
 //   * the survivors of a batch are COMPACTED into a wavefront-private LDS area, two per slot with their fields
 //     interleaved ([x_a x_b y_a y_b] ...), so that the walk reads register PAIRS straight from LDS
 //     (6 ds_read_b128 per two survivors) and the exponent, the exp and alpha of both run on packed fp32
@@ -1104,6 +1106,7 @@ constexpr int kPairQuads = 6;  // float4 per slot of two survivors
 constexpr int kPairArea = 34 * kPairQuads;  // float4 per wavefront: up to 3 carried + 64 new survivors = 67 entries, two per slot
 template <bool FAST_EXP, bool TRACK, bool LDS_LIST>
 __device__ __forceinline__ void blend_quadrant(const uint32_t* pl, int n, const float4* __restrict__ rec, float4* const cp,
+                                               uint32_t* const qi, uint32_t* const qw,
                                                int H, int W, int tx, int ty, int wave, const float* __restrict__ bg,
                                                float* __restrict__ out_color, float* __restrict__ out_depth,
                                                float* __restrict__ out_alpha, float* __restrict__ final_T,
@@ -1189,53 +1192,102 @@ __device__ __forceinline__ void blend_quadrant(const uint32_t* pl, int n, const 
         if constexpr (!PARTIAL) FS_BLEND_ONE(md & gd, av.y, mv.y, kd, e3.w)
     };
 
-    // software pipeline: list words two batches ahead, records one batch ahead
+    // Scan first, gather second: a chunk of 64 list words costs the wavefront one quadrant-bit test, a ballot and a rank;
+    // the list positions of the entries that carry the bit (hits) are queued in `qi`, and only when 64 of them wait (or
+    // the list ends) does lane k take hit k, gather its 48-byte record and, one batch later, compact it -- the gather and
+    // the compaction are issued once per 64 HITS, not once per 64 scanned entries.  A chunk's hits that do not fit the
+    // 64-slot queue stay in their lanes until the batch has been taken, then go to the queue's front.
+    // software pipeline: list words two chunks ahead; the records of hit batch i + 1 are in flight while batch i is blended
     uint32_t w_cur = lane < n ? pl[lane] : 0u;
     uint32_t w_nxt = 64 + lane < n ? pl[64 + lane] : 0u;
     float4 r0 = {}, r1 = {}, r2 = {};
-    if (w_cur & qbit) {
-        const float4* q = rec + 3 * (size_t)(w_cur >> 4);
-        r0 = q[0]; r1 = q[1]; r2 = q[2];
-    }
+    int r_pos = 0;   // TRACK: position of this lane's hit in the tile's FULL list, 1-based (n_contrib; the backward starts there)
+    int c = 0;       // list position of w_cur's chunk
+    int filled = 0;  // hits waiting in the queue (< 64 between two chunks)
+    auto take = [&](int cnt) __attribute__((always_inline)) {
+        wave_lds_sync();
+        if (lane < cnt) {
+            const uint32_t e = qi[lane];
+            uint32_t w;
+            if constexpr (LDS_LIST) w = pl[e]; else w = qw[lane];
+            const float4* q = rec + 3 * (size_t)(w >> 4);
+            r0 = q[0]; r1 = q[1]; r2 = q[2];
+            if constexpr (TRACK) r_pos = (int)e + 1;
+        }
+    };
+    // forms the next hit batch and issues its record gather; returns its size (0: the list is exhausted)
+    auto next_batch = [&]() __attribute__((always_inline)) -> int {
+        while (c < n) {
+            const bool hit = (w_cur & qbit) != 0;
+            const unsigned long long hits = __ballot(hit);
+            const uint32_t w_hit = w_cur;
+            const uint32_t e = (uint32_t)(c + lane);
+            w_cur = w_nxt;
+            w_nxt = c + 128 + lane < n ? pl[c + 128 + lane] : 0u;
+            c += 64;
+            if (!hits) continue;  // an empty chunk costs the test alone
+            const int slot = filled + __builtin_amdgcn_mbcnt_hi((uint32_t)(hits >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hits, 0));
+            if (hit && slot < 64) {
+                qi[slot] = e;
+                if constexpr (!LDS_LIST) qw[slot] = w_hit;
+            }
+            filled += __popcll(hits);
+            if (filled >= 64) {
+                take(64);
+                // (DS operations of one wavefront execute in order: the batch's reads precede these writes)
+                if (hit && slot >= 64) {
+                    qi[slot - 64] = e;
+                    if constexpr (!LDS_LIST) qw[slot - 64] = w_hit;
+                }
+                filled -= 64;
+                return 64;
+            }
+        }
+        const int cnt = filled;  // the list ended with the queue part full
+        if (cnt != 0) take(cnt);
+        filled = 0;
+        return cnt;
+    };
     // Survivors that do not fill a step of four are CARRIED into the next batch (they stay at the front of the
     // compaction area, the next batch's survivors are appended behind them): one partial step per quadrant instead of
-    // one per batch (~0.4 of a step per batch of ~9).
-    int rem = 0;
-    for (int c = 0; c < n; c += 64) {
+    // one per batch.
+    // One iteration: compact batch i (its records arrived while batch i - 1 was blended), form batch i + 1 and issue its
+    // gather, blend batch i.
+    int rem = 0, cur = 0;
+    for (;;) {
         if (done_m == ~0ull) break;  // every pixel of the quadrant is saturated (or outside the image)
-        const bool hit = (w_cur & qbit) != 0;
-        const unsigned long long hits = __ballot(hit);
-        const float4 a0 = r0, a1 = r1, a2 = r2;
-        w_cur = w_nxt;
-        w_nxt = c + 128 + lane < n ? pl[c + 128 + lane] : 0u;
-        if (w_cur & qbit) {
-            const float4* q = rec + 3 * (size_t)(w_cur >> 4);
-            r0 = q[0]; r1 = q[1]; r2 = q[2];
-        }
-        if (!hits) continue;
-        if (hit) {
-            const int k = rem + __builtin_amdgcn_mbcnt_hi((uint32_t)(hits >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hits, 0));
+        if (lane < cur) {
+            const int k = rem + lane;
             float* d = (float*)(cp + (k >> 1) * kPairQuads) + (k & 1);
             // (coefficients NEGATED: the walk evaluates q = -power >= 0, bit for bit the negation of the oracle's power,
             //  so that "0 >= power >= threshold" is one unsigned compare of q's bits against skip_bits)
-            d[0] = a0.x; d[2] = a0.y;                   // [x_a x_b y_a y_b]
-            d[4] = -a0.z; d[6] = -a0.w;                 // [A_a A_b C_a C_b]   (A = a/2, C = c/2)
-            d[8] = -a1.x; d[10] = skip_bits(a1.z);      // [B_a B_b thr_a thr_b] (B = b; thr = bits of -threshold)
-            d[12] = a1.y; d[14] = __int_as_float(c + lane + 1);  // [op_a op_b pos_a pos_b]
-            cp[(k >> 1) * kPairQuads + 4 + (k & 1)] = make_float4(a2.x, a2.y, a2.z, a1.w);  // [r g b depth]
+            d[0] = r0.x; d[2] = r0.y;                   // [x_a x_b y_a y_b]
+            d[4] = -r0.z; d[6] = -r0.w;                 // [A_a A_b C_a C_b]   (A = a/2, C = c/2)
+            d[8] = -r1.x; d[10] = skip_bits(r1.z);      // [B_a B_b thr_a thr_b] (B = b; thr = bits of -threshold)
+            d[12] = r1.y;                               // [op_a op_b pos_a pos_b]
+            if constexpr (TRACK) d[14] = __int_as_float(r_pos);
+            cp[(k >> 1) * kPairQuads + 4 + (k & 1)] = make_float4(r2.x, r2.y, r2.z, r1.w);  // [r g b depth]
         }
-        wave_lds_sync();
-        const int total = rem + __popcll(hits), nfull = total >> 2;
-        for (int p = 0; p < nfull; ++p) step(cp + 2 * p * kPairQuads, std::false_type{}, 4);
-        rem = total & 3;
-        if (rem != 0 && nfull != 0) {
-            // the leftover entries sit in the slot pair behind the last full step: move that pair to the front
-            // (DS operations of one wavefront execute in order: the steps' reads are done, the copy's read precedes its write)
-            float4 t = {};
-            if (lane < 2 * kPairQuads) t = cp[2 * nfull * kPairQuads + lane];
-            if (lane < 2 * kPairQuads) cp[lane] = t;
+        const int nxt = next_batch();
+        if (cur != 0) {
+            wave_lds_sync();
+            const int total = rem + cur, nfull = total >> 2;
+            for (int p = 0; p < nfull; ++p) {
+                if (done_m == ~0ull) break;
+                step(cp + 2 * p * kPairQuads, std::false_type{}, 4);
+            }
+            rem = total & 3;
+            if (rem != 0 && nfull != 0) {
+                // the leftover entries sit in the slot pair behind the last full step: move that pair to the front
+                // (DS operations of one wavefront execute in order: the steps' reads are done, the copy's read precedes its write)
+                float4 t = {};
+                if (lane < 2 * kPairQuads) t = cp[2 * nfull * kPairQuads + lane];
+                if (lane < 2 * kPairQuads) cp[lane] = t;
+            }
+            wave_lds_sync();   // (the next batch's compaction appends behind the carried entries)
         }
-        wave_lds_sync();   // (the next batch's compaction appends behind the carried entries)
+        cur = nxt;
+        if (cur == 0) break;
     }
     if (rem != 0 && done_m != ~0ull) {
         // the quadrant's last, partial step: its unused entries enter with weight 0, their colours must still be finite
@@ -1245,7 +1297,11 @@ __device__ __forceinline__ void blend_quadrant(const uint32_t* pl, int n, const 
     }
 #undef FS_BLEND_ONE
     if (inside) {
-        const size_t pix = (size_t)py * W + px, HW = (size_t)H * W;
+        // (the pixel's coordinates are formed again from a fresh lane id: kept alive across the walk they cost registers
+        //  the walk needs)
+        const int ln = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0));
+        const int ox = tx * kTile + (wave & 1) * 8 + (ln & 7), oy = ty * kTile + (wave >> 1) * 8 + (ln >> 3);
+        const size_t pix = (size_t)oy * W + ox, HW = (size_t)H * W;
         final_T[pix] = T_;
         if constexpr (TRACK) n_contrib[pix] = last;
         out_color[pix] = fmaf(T_, bg[0], C01.x);
@@ -1259,7 +1315,7 @@ __device__ __forceinline__ void blend_quadrant(const uint32_t* pl, int n, const 
 // ------------------------------------------------------------------------------------------
 // sort_blend: one workgroup per tile.  All four wavefronts sort the tile's keys in LDS (bucket sort above), the sorted
 // list words stay in LDS, then each wavefront blends its own quadrant from them without another workgroup barrier.
-// LDS: 14 KiB key staging for 1 792 keys (reused as the four wavefronts' compaction areas once the sort is done) + 7 KiB bucket
+// LDS: 14 KiB key staging for 1 792 keys (reused as the four wavefronts' compaction areas and hit queues once the sort is done) + 7 KiB bucket
 // offsets (reused as the sorted list) = 21.6 KiB -> 7 workgroups per CU, 7 wavefronts per SIMD at 68 - 72 registers (round 6;
 // rounds 3 - 5: 2 048 keys, 24.6 KiB, 6 wavefronts at 80 registers -- the longest tile list of config 3 is 1 338 entries.
 // Same-session A/B, profiles/r6_blend_waves_ab.txt: +1.3 % views/s at config 3, +7 % on the close-up workload).
@@ -1268,7 +1324,8 @@ __device__ __forceinline__ void blend_quadrant(const uint32_t* pl, int n, const 
 // groups of <= 2048 keys -> one LDS bucket sort per group) and blended from there; a tile it declines (thousands of equal
 // depths, > 64 groups, a group whose compacted count disagrees with the histogram) falls back to the in-place global network.
 // ------------------------------------------------------------------------------------------
-static_assert(4 * kPairArea * sizeof(float4) <= kSortLds * sizeof(unsigned long long), "compaction areas must fit the key staging");
+static_assert(4 * (kPairArea * sizeof(float4) + 64 * sizeof(uint32_t)) <= kSortLds * sizeof(unsigned long long),
+              "compaction areas and hit queues must fit the key staging");
 template <bool FAST_EXP, bool TRACK>
 #ifndef FS_BLEND_WAVES
 #define FS_BLEND_WAVES 7      // (A/B builds: make VARIANT=w6 EXTRA="-DFS_BLEND_WAVES=6 -DFS_SORT_LDS=2048")
@@ -1313,14 +1370,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FS_BLEND_WA
     FS_PT(2, 1);  // this wavefront's part of the sort done
     __syncthreads();  // list complete (LDS or global); the key staging is free for the compaction areas
     FS_PT(2, 2);  // list complete
-    const int wave = threadIdx.x >> 6;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform: a scalar
     float4* const cp = (float4*)sk + wave * kPairArea;
+    // hit queues: 64 list positions per wavefront in the staging's slack behind the compaction areas; a list blended from
+    // global memory queues its words too, in s_cnt (bucket offsets / LDS list: unused once such a list is sorted)
+    uint32_t* const qi = (uint32_t*)((float4*)sk + 4 * kPairArea) + wave * 64;
+    uint32_t* const qw = s_cnt + wave * 64;
     const int tx = tile % gx, ty = tile / gx;
     if (in_lds)
-        blend_quadrant<FAST_EXP, TRACK, true>(s_cnt, (int)n, rec, cp, H, W, tx, ty, wave, bg, out_color, out_depth, out_alpha,
+        blend_quadrant<FAST_EXP, TRACK, true>(s_cnt, (int)n, rec, cp, qi, nullptr, H, W, tx, ty, wave, bg, out_color, out_depth, out_alpha,
                                               final_T, n_contrib);
     else
-        blend_quadrant<FAST_EXP, TRACK, false>(gl, (int)n, rec, cp, H, W, tx, ty, wave, bg, out_color, out_depth, out_alpha,
+        blend_quadrant<FAST_EXP, TRACK, false>(gl, (int)n, rec, cp, qi, qw, H, W, tx, ty, wave, bg, out_color, out_depth, out_alpha,
                                                final_T, n_contrib);
     FS_PT(2, 3);  // quadrant 0 blended
 }
