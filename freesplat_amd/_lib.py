@@ -1,4 +1,4 @@
-"""ctypes binding of libfreesplat_hip.so (C ABI: include/freesplat_amd.h).
+"""ctypes binding of libfreesplat_hip.so (C ABI: include/freesplat_amd.h, include/freesplat_amd_loss.h).
 
 The product path has NO fallback: if the HIP library is missing or a call fails this module
 raises.  `build()` compiles the library in-tree with hipcc for gfx950.
@@ -26,6 +26,7 @@ class RasterDims(C.Structure):
 
 
 ABI_VERSION = 9          # include/freesplat_amd.h FS_ABI_VERSION
+LOSS_API_VERSION = 1     # include/freesplat_amd_loss.h FS_LOSS_API_VERSION
 
 RASTER_TILE_CULL = 1
 RASTER_SH_FP16 = 2
@@ -35,6 +36,9 @@ RASTER_FAST_EXP = 16
 RASTER_NO_BACKWARD_STATE = 32
 RASTER_DETERMINISTIC = 64
 RASTER_SCALE_ROT = 128
+
+SSIM_SKIMAGE = 1
+SSIM_3DGS = 2
 
 
 def build(force: bool = False) -> str:
@@ -155,6 +159,16 @@ SIGNATURES = {
     "fs_raster_n_contrib": (_VP, [_VP, C.c_int32, C.c_int32]),
 }
 
+# name -> (restype, argtypes); must list every symbol include/freesplat_amd_loss.h declares (a header and a table of its
+# own: the main header's symbol set and FS_ABI_VERSION stay as they are)
+LOSS_SIGNATURES = {
+    "fs_loss_api_version": (C.c_int, []),
+    "fs_ssim_loss_saved_bytes": (C.c_size_t, [C.c_int32] * 5),
+    "fs_ssim_loss_scratch_bytes": (C.c_size_t, [C.c_int32] * 5),
+    "fs_ssim_loss_forward": (C.c_int, [C.c_int32] * 5 + [_VP] * 7),
+    "fs_ssim_loss_backward": (C.c_int, [C.c_int32] * 5 + [_VP] * 8),
+}
+
 
 def lib():
     global _lib
@@ -169,13 +183,17 @@ def lib():
         # device is detected"
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)  # AttributeError if the library lacks a declared symbol
-            fn.restype = res
-            fn.argtypes = args
+        for table in (SIGNATURES, LOSS_SIGNATURES):
+            for name, (res, args) in table.items():
+                fn = getattr(L, name)  # AttributeError if the library lacks a declared symbol
+                fn.restype = res
+                fn.argtypes = args
         if L.fs_abi_version() != ABI_VERSION:
             raise FreeSplatHipError(f"{LIB_PATH} has ABI revision {L.fs_abi_version()}, this binding expects {ABI_VERSION} "
                                     "(include/freesplat_amd.h FS_ABI_VERSION): rebuild the library")
+        if L.fs_loss_api_version() != LOSS_API_VERSION:
+            raise FreeSplatHipError(f"{LIB_PATH} has loss API revision {L.fs_loss_api_version()}, this binding expects "
+                                    f"{LOSS_API_VERSION} (include/freesplat_amd_loss.h FS_LOSS_API_VERSION): rebuild the library")
         _lib = L
     return _lib
 
