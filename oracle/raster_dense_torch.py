@@ -2,7 +2,7 @@
 
 TEST INFRASTRUCTURE ONLY (see oracle/raster_oracle.c header).  Used to cross-check the
 hand-derived backward of the C oracle (and through it the HIP kernels) on tiny scenes
-(<= ~100 Gaussians, <= 48x48 px): every pixel evaluates every Gaussian, O(N*P) memory.
+(<= ~400 Gaussians, <= 48x64 px): every pixel evaluates every Gaussian, O(N*P) memory.
 
 The discrete parts (tile rectangles, draw order) are taken from the C oracle's forward so
 that both evaluate exactly the same (gaussian, pixel) pairs; everything differentiable is
@@ -40,9 +40,16 @@ def _sh_color(deg, dirs, shs):
 
 
 def render_dense(H, W, tanfovx, tanfovy, bg, viewmatrix, projmatrix, sh_degree, campos,
-                 means3D, cov6, opacities, shs=None, colors_precomp=None, *, rect, radii, order):
+                 means3D, cov6, opacities, shs=None, colors_precomp=None, *, rect, radii, order,
+                 sh_clamp_convention=True, jacobian_clamp=True, alpha_cap_convention=True):
     """All tensor args float64.  rect [N,4] int (tile rect), radii [N] int, order: LongTensor of
-    gaussian ids sorted by (depth bits, id) -- all from the C oracle.  Returns color[3,H,W], depth[H,W]."""
+    gaussian ids sorted by (depth bits, id) -- all from the C oracle.  Returns color[3,H,W], depth[H,W].
+
+    The three switches turn ONE emulated convention of the original off each (defaults: all on, the original's
+    behaviour); tests use them to show that a scene and a metric can see the branch, without ever running broken code:
+      sh_clamp_convention=False   same image, but the gradient passes through max(colour, 0) as if it were unclamped
+      jacobian_clamp=False        the projection Jacobian is taken at the unclamped view-space x, y
+      alpha_cap_convention=False  min(0.99, o * G) gets its true derivative (0 where capped)"""
     dt = torch.float64
     N = means3D.shape[0]
     V = viewmatrix.to(dt)
@@ -60,8 +67,8 @@ def render_dense(H, W, tanfovx, tanfovy, bg, viewmatrix, projmatrix, sh_degree, 
     cx_ = (txtz < -limx) | (txtz > limx)
     cy_ = (tytz < -limy) | (tytz > limy)
     # original: clamped coordinate gets zero gradient and its tz dependence is ignored
-    tx = torch.where(cx_, (txtz.clamp(-limx, limx) * tz).detach(), pv[:, 0])
-    ty = torch.where(cy_, (tytz.clamp(-limy, limy) * tz).detach(), pv[:, 1])
+    tx = torch.where(cx_, (txtz.clamp(-limx, limx) * tz).detach(), pv[:, 0]) if jacobian_clamp else pv[:, 0]
+    ty = torch.where(cy_, (tytz.clamp(-limy, limy) * tz).detach(), pv[:, 1]) if jacobian_clamp else pv[:, 1]
     zero = torch.zeros_like(tz)
     J = torch.stack([torch.stack([fx / tz, zero, -fx * tx / (tz * tz)], -1),
                      torch.stack([zero, fy / tz, -fy * ty / (tz * tz)], -1)], -2)  # [N,2,3]
@@ -84,7 +91,10 @@ def render_dense(H, W, tanfovx, tanfovy, bg, viewmatrix, projmatrix, sh_degree, 
         d = means3D - campos.to(dt)[None]
         d = d / d.norm(dim=-1, keepdim=True)
         col = _sh_color(sh_degree, d, shs)
-        col = torch.clamp_min(col, 0.0)  # zero grad where clamped, as the original
+        if sh_clamp_convention:
+            col = torch.clamp_min(col, 0.0)  # zero grad where clamped, as the original
+        else:
+            col = col + (torch.clamp_min(col, 0.0) - col).detach()
     else:
         col = colors_precomp
 
@@ -103,7 +113,7 @@ def render_dense(H, W, tanfovx, tanfovy, bg, viewmatrix, projmatrix, sh_degree, 
     G = torch.exp(power)
     raw = opacities[o][:, None] * G
     # original: alpha = min(0.99, o*G) but the backward ignores the clamp
-    alpha = raw + (torch.clamp_max(raw, 0.99) - raw).detach()
+    alpha = raw + (torch.clamp_max(raw, 0.99) - raw).detach() if alpha_cap_convention else torch.clamp_max(raw, 0.99)
     active = member & (power <= 0) & (alpha >= 1.0 / 255.0)
     a_eff = torch.where(active, alpha, torch.zeros_like(alpha))
     one_m = 1.0 - a_eff

@@ -3,7 +3,11 @@
 Bar (BASELINE.json north_star): <= 1e-4 abs per pixel with identical tile/depth ordering.
 What is asserted here is stronger for the forward: bit-exact images, radii, tile ranges and
 depth-sorted id lists (the oracle and the kernels share one arithmetic contract).  The backward
-accumulates with float atomics, so its bar is a tolerance: 2e-4 of the gradient's max-abs.
+accumulates with float atomics, so its bar is a tolerance: the largest error of a gradient tensor is
+at most 2e-4 of that tensor's max-abs.  That figure is tensor-wide: a Gaussian whose own gradient is
+small can be wrong without moving it, and the wall scene of these tests clamps no colour, never reaches
+the Jacobian's frustum clamp and stays 4 m behind the near cull.  tests/test_raster_branch_edges.py adds,
+beside it, a scene that takes those branches and an error scaled per Gaussian.
 """
 import numpy as np
 import pytest

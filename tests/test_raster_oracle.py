@@ -1,6 +1,11 @@
 """CPU tests that pin the rasterizer ORACLE itself (the reference has no golden vectors for this
 boundary -- SURVEY.md 8(c)): closed-form known answers, an independent float64 torch restatement,
-and autograd for the hand-derived backward."""
+and autograd for the hand-derived backward.
+
+The test_edge_* tests ask the oracle about the branches the wall scene never takes (util_raster.edge_scene: clamped SH
+colours, the Jacobian's frustum clamp, the near cull, zero covariances, opacities below 1/255 and above 0.99), judged per
+Gaussian (util_raster.per_gaussian_err) against float64 autograd of the dense restatement.  Bounds: twice the figures measured
+on the CPU (util_raster.EDGE_ORACLE_VS_F64)."""
 import math
 
 import numpy as np
@@ -10,7 +15,9 @@ import torch
 from oracle import raster_oracle as ro
 from oracle.raster_dense_torch import render_dense
 from util_framing import _frame
-from util_raster import oracle_forward, small_scene, view_inputs
+from util_raster import (EDGE_ORACLE_VS_F64, EDGE_TOL_CPU, assert_edge_cases_present, colour_key, dead_rows,
+                         chain_scale_rot, dense_reference, edge_dense_reference, edge_scale_rot, edge_oracle_backward, edge_view, max_abs_err, oracle_forward,
+                         per_gaussian_err, small_scene, view_inputs)
 
 C0 = 0.28209479177387814
 
@@ -258,3 +265,93 @@ def test_backward_matches_finite_differences_of_dense():
             fd[j] = (loss(*args_p) - loss(*args_m)) / (2 * h)
         scale = np.abs(ana).max() + 1e-12
         assert np.abs(fd - ana[idx]).max() / scale < 2e-3, (name, fd, ana[idx])
+
+
+EDGE_CASES = [(0, False), (1, False), (2, False), (3, False), (2, True)]
+
+
+@pytest.mark.parametrize("sh_degree,precomp", EDGE_CASES)
+def test_edge_backward_matches_float64_per_gaussian(sh_degree, precomp):
+    """The oracle's fp32 backward on the edge scene (colour and depth cotangents) against float64 autograd of the dense
+    restatement, per Gaussian.  Opacities in 0.05 - 0.9 so that fp32 and float64 take the same 1/255 and T < 1e-4
+    decisions; at this seed no pixel flips and no Gaussian is excluded."""
+    vi, st, g_color, g_depth = edge_view(sh_degree, precomp, "dense")
+    counts = assert_edge_cases_present(vi, st, colours_clamp=not precomp)
+    got, ref = edge_oracle_backward(sh_degree, precomp, "dense"), edge_dense_reference(sh_degree, precomp, "dense")
+    np.testing.assert_allclose(st["color"], ref["color"], atol=2e-5)
+    np.testing.assert_allclose(st["depth"], ref["depth"], atol=1e-4)
+    ck = colour_key(vi)
+    fig = {}
+    for name, key in (("means3D", "means3D"), ("cov3D", "cov3D"), ("opacities", "opacities"), ("colour", ck)):
+        assert np.isfinite(got[key]).all() and np.isfinite(ref[key]).all(), name
+        fig[name] = per_gaussian_err(got[key], ref[key]) + (max_abs_err(got[key], ref[key]),)
+    print(f"edge scene degree {sh_degree} precomp {precomp}: {counts}")
+    print("oracle vs float64 (per-Gaussian error, worst Gaussian, error / tensor max-abs):",
+          {k: f"{e:.2e} @{g} {m:.1e}" for k, (e, g, m) in fig.items()})
+    for name, (e, g, _) in fig.items():
+        assert e <= EDGE_TOL_CPU[name], f"{name}: per-Gaussian error {e:.3e} at Gaussian {g} (bound {EDGE_TOL_CPU[name]:.2e})"
+
+
+def test_edge_backward_scale_rot_form_matches_float64_per_gaussian():
+    """The (scales, rotations) form of the edge scene: covariances rebuilt from edge_scale_rot's rows (the zero rows stay
+    zero), the oracle's dL/dcov3D and the float64 restatement's both chained through float64 build_cov3d."""
+    from freesplat_amd.rasterizer import build_cov3d
+    vi, _, g_color, g_depth = edge_view(2, False, "dense")
+    sc, rq = edge_scale_rot(vi["cov3D"], vi["edge_rows"]["zero_cov"])
+    vi = dict(vi, cov3D=build_cov3d(sc.double(), rq.double(), 1.0).float())
+    st = oracle_forward(vi)
+    assert_edge_cases_present(vi, st)
+    got, ref = ro.backward(st, g_color, g_depth), dense_reference(vi, st, g_color, g_depth)
+    got.update(chain_scale_rot(sc, rq, got["cov3D"]))
+    ref.update(chain_scale_rot(sc, rq, ref["cov3D"]))
+    fig = {name: per_gaussian_err(got[key], ref[key]) for name, key in (("means3D", "means3D"), ("cov3D", "cov3D"),
+           ("opacities", "opacities"), ("colour", "shs"), ("scales", "scales"), ("rotations", "rotations"))}
+    print("oracle vs float64, (scales, rotations) form:", {k: f"{e:.2e} @{g}" for k, (e, g) in fig.items()})
+    for name, (e, g) in fig.items():
+        assert e <= EDGE_TOL_CPU[name], f"{name}: per-Gaussian error {e:.3e} at Gaussian {g} (bound {EDGE_TOL_CPU[name]:.2e})"
+
+
+@pytest.mark.parametrize("sh_degree,precomp", EDGE_CASES)
+def test_edge_exact_zero_gradients(sh_degree, precomp):
+    """No tolerance: a clamped colour channel gives every one of its SH coefficients gradient 0; a culled Gaussian and one
+    whose opacity is below 1/255 get gradient 0 in every tensor; everything is finite.  Full opacity range."""
+    vi, st, _, _ = edge_view(sh_degree, precomp, "full")
+    assert_edge_cases_present(vi, st, colours_clamp=not precomp, low_opacity_visible=2, high_opacity_visible=2)
+    got = edge_oracle_backward(sh_degree, precomp, "full")
+    dead = dead_rows(vi, st)
+    assert (st["radii"][dead] == 0).sum() >= 2 and (st["radii"][dead] > 0).sum() >= 2
+    for key in ("means3D", "cov3D", "opacities", colour_key(vi), "means2D"):
+        assert np.isfinite(got[key]).all(), key
+        assert not got[key][dead].any(), key
+        assert got[key][~dead].any(), key
+    if not precomp:
+        cl = st["clamped"].astype(bool)                                   # [N,3]
+        assert not got["shs"][np.broadcast_to(cl[:, None, :], got["shs"].shape)].any()
+        assert got["shs"][:, 0, :][~cl & ~dead[:, None]].any()
+
+
+@pytest.mark.parametrize("switch,opacity,seen_in", [("sh_clamp_convention", "dense", ("colour", "means3D")),
+                                                    ("jacobian_clamp", "dense", ("means3D", "cov3D", "opacities", "colour")),
+                                                    ("alpha_cap_convention", "capped", ("opacities", "means3D", "cov3D"))])
+def test_edge_scene_and_metric_see_each_convention(switch, opacity, seen_in):
+    """Sensitivity, on the reference side so that nothing broken ever runs: with ONE emulated convention of the original
+    switched off in the float64 restatement, the per-Gaussian error of the (unchanged) oracle exceeds the bound by 10x and
+    more in the tensors the convention reaches -- a kernel that took that branch wrongly would be as far off.  The alpha
+    cap needs o * G > 0.99, so its check runs on the "capped" scene (the dense one plus the three rows above 0.99), on
+    which the unaltered reference is checked first.  Prints the tensor-wide max-abs figure (the older tests' metric, bar
+    2e-4) of the same alteration beside it."""
+    vi, st, g_color, g_depth = edge_view(2, False, opacity)
+    assert_edge_cases_present(vi, st, high_opacity_visible=3 if opacity == "capped" else 0)
+    got = edge_oracle_backward(2, False, opacity)
+    plain = edge_dense_reference(2, False, opacity)
+    altered = dense_reference(vi, st, g_color, g_depth, **{switch: False})
+    for name in ("means3D", "cov3D", "opacities", "colour"):
+        key = "shs" if name == "colour" else name
+        base, _ = per_gaussian_err(got[key], plain[key])
+        assert base <= EDGE_TOL_CPU[name], f"{name}: {base:.3e} against the unaltered reference"
+        e, g = per_gaussian_err(got[key], altered[key])
+        m = max_abs_err(got[key], altered[key])
+        print(f"{switch} off, {name}: per-Gaussian {e:.2e} (Gaussian {g}) = {e / EDGE_TOL_CPU[name]:.0f}x the bound; "
+              f"tensor-wide max-abs {m:.1e} ({'seen' if m >= 2e-4 else 'NOT seen'} at the 2e-4 bar)")
+        if name in seen_in:
+            assert e >= 10.0 * EDGE_TOL_CPU[name], f"{switch} off is invisible in {name}: {e:.3e}"

@@ -62,3 +62,270 @@ def hip_forward(vi: dict, device, requires_grad=False):
                                 if leaves["opacities"].dim() == 1 else leaves["opacities"],
                                 cov3D_precomp=leaves["cov3D"])
     return out, leaves
+
+
+# ------------------------------------------------------------------------------------------------ branch-edge scenes
+EDGE_NEARS = (0.5, 1.0, 0.25)   # per-view near planes of the three-view variant: 1/near rescales of 2, 1 and 4, exact in fp32
+
+
+def edge_scene(N=320, H=40, W=56, seed=5, n_views=1, sh_degree=2, opacity="full"):
+    """small_scene with rows overwritten so that one render takes the branches the wall scene never reaches: clamped SH
+    colours, the Jacobian's frustum clamp (+-x, +-y, one pair either side of 1.3 tan_fov), the near cull (view-space z
+    exactly 0.2, one ulp above, below, behind the camera), zero covariances, opacities below 1/255 and above 0.99.
+
+    Every case is placed in the camera space of a view (the frame the rasterizer sees after the 1/near rescale) and
+    mapped to the world through that view's camera-to-world matrix.  View 0 is axis-aligned at z = 0 with near = 0.5, so
+    its view-space z is world z times 2 without rounding and "exactly 0.2" means exactly.  n_views = 3 adds the per-view
+    cases: nears EDGE_NEARS, one Gaussian drawn in view 0 / near-culled in view 1 / frustum-clamped in view 2, and one
+    whose red channel is clamped in view 0 only (sh_degree >= 1).
+
+    opacity: "full" keeps sigmoid(N(0,2)) plus the rows below 1/255 and above 0.99; "dense" clamps everything to
+    0.05 - 0.9 (fp32 and float64 then agree on the 1/255 and T < 1e-4 decisions); "capped" is "dense" with the rows above
+    0.99 put back.  Returns (scene, cams) as small_scene does; scene["edge_rows"] names the overwritten rows."""
+    assert N >= 300 and H % 16 and W % 16 and n_views in (1, 3) and opacity in ("full", "dense", "capped")
+    scene, cams = small_scene(N=N, H=H, W=W, seed=seed, n_views=n_views, sh_degree=sh_degree)
+    rng = np.random.default_rng(seed + 1000)
+    c2w = cams["extrinsics"].double().numpy().copy()
+    c2w[0, :3, :3] = np.eye(3)
+    c2w[0, 2, 3] = 0.0
+    cams["extrinsics"] = torch.from_numpy(c2w.astype(np.float32))
+    cams["near"] = torch.tensor(EDGE_NEARS[:n_views])
+    c2w = cams["extrinsics"].double().numpy()
+    scale = 1.0 / cams["near"].double().numpy()
+    tan = 0.5 / np.array([synthetic.FX_N, synthetic.FY_N])
+    fx_px = W / (2.0 * tan[0])
+
+    means, cov, sh, opac = (scene[k] for k in ("means", "covariances", "harmonics", "opacities"))
+    sh[:, :, 0] = torch.from_numpy(rng.uniform(-3.0, 3.0, (N, 3)).astype(np.float32))
+    if opacity != "full":
+        opac.clamp_(0.05, 0.9)
+    # rows to overwrite: both 256-row blocks of preprocess_bwd, their boundary and the last (ragged) row included
+    first = [0, 255, 256, N - 1]
+    pool = first + [int(i) for i in rng.permutation(N) if int(i) not in first]
+    rows = {}
+
+    def take(name):
+        i = pool.pop(0)
+        rows.setdefault(name, []).append(i)
+        return i
+
+    def put(i, view, p_cam, cov_cam, opacity_i=None):
+        """Row i at p_cam in the (rescaled) camera space of `view`; cov_cam = its covariance there (3x3)."""
+        s = scale[view]
+        R = c2w[view, :3, :3]
+        means[i] = torch.from_numpy((R @ (np.asarray(p_cam, np.float64) / s) + c2w[view, :3, 3]).astype(np.float32))
+        cov[i] = torch.from_numpy((R @ (np.asarray(cov_cam, np.float64) / (s * s)) @ R.T).astype(np.float32))
+        if opacity_i is not None:
+            opac[i] = opacity_i
+
+    def blob(sigma):
+        return np.eye(3) * sigma * sigma
+
+    on_screen = lambda fx_, fy_, z: (fx_ * tan[0] * z, fy_ * tan[1] * z, z)
+    # frustum clamp: large Gaussians centred beyond 1.3 tan_fov whose rectangles reach the image; (1.31, 1.29) is the pair
+    for f, ax in ((1.4, 0), (-1.5, 0), (1.45, 1), (-1.35, 1), (1.6, 0), (-1.4, 1), (1.31, 0), (1.29, 0), (-1.31, 1), (-1.29, 1)):
+        z = rng.uniform(4.0, 8.0)
+        p = np.zeros(3)
+        p[2], p[ax], p[1 - ax] = z, f * tan[ax] * z, rng.uniform(-0.5, 0.5) * tan[1 - ax] * z
+        s2 = (0.25 * z * tan[ax]) ** 2
+        put(take("frustum"), 0, p, s2 * np.array([[1, 0.1, 0], [0.1, 1, 0.05], [0, 0.05, 0.3]]), 0.6)
+    # near cull: z <= 0.2 is culled.  fp32 0.2 exactly, one ulp above it, 0.21, 0.25 (drawn); 0.19, behind the camera (culled)
+    z02 = np.float32(0.2)
+    for j, z in enumerate((z02, np.nextafter(z02, np.float32(1)), 0.21, 0.19, -1.0, 0.25)):
+        put(take("near"), 0, (-0.03 + 0.012 * j, 0.01, float(z)), blob(0.01), 0.6)
+    # zero covariances that land on screen: cov2D is the 0.3 low-pass term alone
+    for fx_, fy_ in ((-0.55, 0.5), (0.5, 0.55), (-0.2, -0.7), (0.75, -0.2)):
+        put(take("zero_cov"), 0, on_screen(fx_, fy_, rng.uniform(3.0, 5.0)), np.zeros((3, 3)), 0.7)
+    # exactly one, two and three clamped channels (C0 * -3 + 0.5 < 0 < C0 * 1 + 0.5; the higher bands are 0.025 and less)
+    for k, (fx_, fy_) in enumerate(((-0.7, -0.6), (0.1, -0.75), (0.7, 0.7))):
+        i = take("clamped_%d" % (k + 1))
+        put(i, 0, on_screen(fx_, fy_, 3.0), blob(0.12), 0.6)
+        sh[i, :, 0] = torch.tensor([-3.0 if c <= k else 1.0 for c in range(3)])
+    # opacities below 1/255 (never contribute) and above 0.99 (the alpha cap: o * G > 0.99 within 0.1 sigma of the mean, and
+    # sigma = 8 px puts a pixel centre there); in front of the wall, apart from each other and from the near-cull rows
+    for o, (fx_, fy_) in zip((0.003, 0.0039, 1e-4), ((-0.4, 0.75), (0.3, 0.3), (-0.75, 0.1))):
+        put(take("low_opacity"), 0, on_screen(fx_, fy_, 2.5), blob(0.1), o if opacity == "full" else None)
+    for o, (fx_, fy_) in zip((1.0, 0.999, 0.995), ((0.6, -0.55), (-0.6, -0.5), (0.05, 0.65))):
+        put(take("high_opacity"), 0, on_screen(fx_, fy_, 2.0), blob(8.0 * 2.0 / fx_px), o if opacity != "dense" else None)
+    if n_views == 3:
+        # 0.15 m in front of the cameras: view-space z = 0.3 (drawn) / 0.15 (near-culled) / 0.6 at 1.45 tan_fov_x (clamped)
+        zw = 0.15
+        put(take("per_view_cull"), 2, (-1.45 * tan[0] * zw * scale[2], 0.0, zw * scale[2]), blob(8.0 * zw * scale[2] / fx_px), 0.6)
+        # red is 0 + 0.5 from the DC term; the degree-1 x coefficient moves it by -+0.23 as the view direction's x changes
+        # sign between view 0 (camera to its left) and view 2 (camera to its right)
+        i = take("per_view_clamp")
+        mid = 0.5 * (c2w[0, :3, 3] + c2w[2, :3, 3])
+        put(i, 0, (mid - c2w[0, :3, 3] + np.array([0.0, 0.0, 0.4])) * scale[0], blob(0.02 * scale[0]), 0.5)
+        sh[i] = 0.0
+        sh[i, :, 0] = torch.tensor([-0.5 / 0.28209479177387814, 1.0, 1.0])
+        if sh_degree >= 1:
+            sh[i, 0, 3] = 2.0
+    scene["edge_rows"] = rows
+    return scene, cams
+
+
+def edge_counts(vi: dict, st: dict) -> dict:
+    """How often each branch-edge case occurs in one view, from the oracle's forward state and fp32 view-space coordinates."""
+    V, m = vi["viewmatrix"].numpy(), vi["means3D"].numpy()
+    pv = m[:, 0:1] * V[0, :3] + m[:, 1:2] * V[1, :3] + m[:, 2:3] * V[2, :3] + V[3, :3]       # fp32, as the oracle's xf43
+    vis = st["radii"] > 0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rx = pv[:, 0] / pv[:, 2] / np.float32(vi["tanfovx"])
+        ry = pv[:, 1] / pv[:, 2] / np.float32(vi["tanfovy"])
+    lim = np.float32(1.3)
+    z02 = np.float32(0.2)
+    ncl = st["clamped"].sum(1)
+    op = vi["opacities"].numpy()
+    return dict(
+        clamped_channels=int(st["clamped"].sum()), clamped_1=int((ncl == 1).sum()), clamped_2=int((ncl == 2).sum()),
+        clamped_3=int((ncl == 3).sum()),
+        jac_px=int((vis & (rx > lim)).sum()), jac_nx=int((vis & (rx < -lim)).sum()),
+        jac_py=int((vis & (ry > lim)).sum()), jac_ny=int((vis & (ry < -lim)).sum()),
+        just_inside=int((vis & (np.maximum(np.abs(rx), np.abs(ry)) > 1.25) & (np.abs(rx) <= lim) & (np.abs(ry) <= lim)).sum()),
+        just_outside=int((vis & (((np.abs(rx) > lim) & (np.abs(rx) < 1.35)) | ((np.abs(ry) > lim) & (np.abs(ry) < 1.35)))).sum()),
+        culled=int((~vis).sum()), behind=int((pv[:, 2] < 0).sum()),
+        z_exactly_02_culled=int(((pv[:, 2] == z02) & ~vis).sum()),
+        z_one_ulp_above_02_drawn=int(((pv[:, 2] == np.nextafter(z02, np.float32(1))) & vis).sum()),
+        z_below_02=int(((pv[:, 2] > 0) & (pv[:, 2] < z02)).sum()),
+        zero_cov_visible=int((vis & ~vi["cov3D"].numpy().any(1)).sum()),
+        low_opacity_visible=int((vis & (op < 1.0 / 255.0)).sum()), high_opacity_visible=int((vis & (op > 0.99)).sum()))
+
+
+EDGE_FLOORS = dict(clamped_channels=20, clamped_1=1, clamped_2=1, clamped_3=1, jac_px=1, jac_nx=1, jac_py=1, jac_ny=1,
+                   just_inside=1, just_outside=1, culled=2, behind=1, z_exactly_02_culled=1, z_one_ulp_above_02_drawn=1,
+                   z_below_02=1, zero_cov_visible=2)
+
+
+def assert_edge_cases_present(vi: dict, st: dict, colours_clamp=True, **more) -> dict:
+    """The conditions of every test on an edge scene: each case is there in at least EDGE_FLOORS' number (and `more`'s), so a
+    change of the generator fails the tests instead of emptying them.  Returns the counts."""
+    n = edge_counts(vi, st)
+    floors = dict(EDGE_FLOORS, **more)
+    if not colours_clamp:       # colors_precomp: no clamp exists
+        floors = {k: v for k, v in floors.items() if not k.startswith("clamped")}
+    short = {k: (n[k], v) for k, v in floors.items() if n[k] < v}
+    assert not short, f"edge scene lost its cases (have, need): {short}"
+    assert n["jac_px"] + n["jac_nx"] + n["jac_py"] + n["jac_ny"] >= 4
+    return n
+
+
+def per_gaussian_err(got, ref, rows=None, f=1e-4):
+    """max over Gaussians g of  max_j |got_gj - ref_gj| / max(max_j |ref_gj|, f * max|ref|)  for gradients [N, ...], and
+    the index of the worst Gaussian.  A Gaussian whose gradient is below f of the tensor's largest is judged absolutely at
+    that floor.  `rows`: boolean mask of the Gaussians judged (the floor still comes from the whole tensor)."""
+    t = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    b = t(ref).astype(np.float64)
+    b = b.reshape(b.shape[0], -1)
+    a = t(got).astype(np.float64).reshape(b.shape)
+    scale = np.maximum(np.abs(b).max(1), max(f * np.abs(b).max(), 1e-300))
+    e = np.abs(a - b).max(1) / scale
+    if rows is not None:
+        e = np.where(rows, e, 0.0)
+    g = int(np.argmax(e))
+    return float(e[g]), g
+
+
+def max_abs_err(got, ref):
+    """The tensor-wide figure of the older tests: largest error over the largest magnitude of the whole tensor."""
+    t = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    b = t(ref).astype(np.float64)
+    return float(np.abs(t(got).astype(np.float64).reshape(b.shape) - b).max() / (np.abs(b).max() + 1e-300))
+
+
+def dense_reference(vi: dict, st: dict, g_color, g_depth=None, **switches) -> dict:
+    """float64 autograd of the dense restatement (oracle/raster_dense_torch.py) for the cotangents g_color [3,H,W] and
+    g_depth [H,W] | None, on the discrete decisions (rects, radii, draw order) of the oracle's forward state `st`.
+    Returns the gradients keyed as raster_oracle.backward keys them, plus the float64 images "color" and "depth"."""
+    from oracle.raster_dense_torch import render_dense
+    leaf = lambda t: None if t is None else t.double().clone().requires_grad_(True)
+    m, c, o = leaf(vi["means3D"]), leaf(vi["cov3D"]), leaf(vi["opacities"])
+    s, cp = leaf(vi.get("shs")), leaf(vi.get("colors_precomp"))
+    order = torch.from_numpy(np.lexsort((np.arange(st["N"]), st["depths"].view(np.uint32))).astype(np.int64))
+    color, depth, _ = render_dense(vi["H"], vi["W"], vi["tanfovx"], vi["tanfovy"], vi["bg"], vi["viewmatrix"],
+                                   vi["projmatrix"], vi["sh_degree"], vi["campos"], m, c, o, shs=s, colors_precomp=cp,
+                                   rect=torch.from_numpy(st["rect"]), radii=torch.from_numpy(st["radii"]), order=order,
+                                   **switches)
+    loss = (color * torch.from_numpy(np.asarray(g_color)).double()).sum()
+    if g_depth is not None:
+        loss = loss + (depth * torch.from_numpy(np.asarray(g_depth)).double()).sum()
+    loss.backward()
+    n = lambda t: None if t is None else t.grad.numpy()
+    return dict(means3D=n(m), cov3D=n(c), opacities=n(o), shs=n(s), colors_precomp=n(cp),
+                color=color.detach().numpy(), depth=depth.detach().numpy())
+
+
+# The edge scene every branch-edge test uses, and what the C oracle's fp32 backward measures against float64 autograd of
+# the dense restatement on it (per_gaussian_err; the worst of SH degree 0-3 and colors_precomp at opacity="dense", colour
+# and depth cotangents; CPU, x86-64 glibc).  The seed is the one of 1-8 with the smallest opacities figure, picked from this
+# oracle-vs-float64 measurement alone; no single-pixel decision flips between fp32 and float64 at it, so no Gaussian is
+# excluded.  means3D's worst case, and the scales / rotations figures, are those of the (scales, rotations) form of the
+# scene (edge_scale_rot; dL/dcov3D chained through float64 build_cov3d on both sides); without it means3D is 2.74e-5.  The worst Gaussians all have gradients of 1e-4 - 2e-3 of their tensor's largest: the figure is the fp32
+# rounding of sums of signed per-pixel terms, seen from the metric's floor.
+EDGE_H, EDGE_W, EDGE_N, EDGE_SEED = 40, 56, 320, 1
+EDGE_ORACLE_VS_F64 = dict(means3D=5.64e-5, cov3D=2.29e-5, opacities=4.00e-4, colour=1.08e-4, scales=1.64e-5, rotations=2.57e-5)
+EDGE_TOL_CPU = {k: 2.0 * v for k, v in EDGE_ORACLE_VS_F64.items()}      # platform libm differences
+EDGE_TOL_GPU = {k: 4.0 * v for k, v in EDGE_ORACLE_VS_F64.items()}      # + the order of the kernels' fp32 sums
+_edge_cache = {}
+
+
+def colour_key(vi: dict) -> str:
+    return "shs" if vi.get("shs") is not None else "colors_precomp"
+
+
+def edge_view(sh_degree=2, precomp=False, opacity="dense", view=0, n_views=1):
+    """(vi, st, g_color, g_depth) of one view of the edge scene: framed inputs, the oracle's forward state and the
+    cotangents.  Computed once per argument set and shared: treat all four as read-only."""
+    key = ("view", sh_degree, precomp, opacity, view, n_views)
+    if key not in _edge_cache:
+        scene, cams = edge_scene(EDGE_N, EDGE_H, EDGE_W, EDGE_SEED, n_views, sh_degree, opacity)
+        vi = view_inputs(scene, cams, view, EDGE_H, EDGE_W, bg=(0.3, 0.5, 0.1))
+        if precomp:
+            vi["colors_precomp"] = (vi["shs"][:, 0, :] * 0.5 + 0.5).contiguous()
+            vi["shs"] = None
+        vi["edge_rows"] = scene["edge_rows"]
+        rng = np.random.default_rng(EDGE_SEED + 10 * view)
+        g_color = rng.normal(size=(3, EDGE_H, EDGE_W)).astype(np.float32)
+        g_depth = rng.normal(size=(EDGE_H, EDGE_W)).astype(np.float32)
+        _edge_cache[key] = (vi, oracle_forward(vi), g_color, g_depth)
+    return _edge_cache[key]
+
+
+def edge_oracle_backward(*args):
+    """raster_oracle.backward of edge_view(*args), computed once."""
+    from oracle import raster_oracle as ro
+    key = ("oracle",) + args
+    if key not in _edge_cache:
+        vi, st, g_color, g_depth = edge_view(*args)
+        _edge_cache[key] = ro.backward(st, g_color, g_depth)
+    return _edge_cache[key]
+
+
+def edge_dense_reference(*args):
+    """dense_reference of edge_view(*args) with every convention of the original on, computed once."""
+    key = ("dense",) + args
+    if key not in _edge_cache:
+        vi, st, g_color, g_depth = edge_view(*args)
+        _edge_cache[key] = dense_reference(vi, st, g_color, g_depth)
+    return _edge_cache[key]
+
+
+def dead_rows(vi: dict, st: dict):
+    """Gaussians that cannot contribute: culled (radius 0) or opacity below 1/255."""
+    return (st["radii"] == 0) | (vi["opacities"].numpy() < 1.0 / 255.0)
+
+
+def edge_scale_rot(cov6: torch.Tensor, zero_rows):
+    """(scales [N,3], rotations [N,4]) of the size of the covariances cov6 (test_raster_scale_rot_alpha._scale_rot_for:
+    quaternion norms in 0.5 - 2, random signs); the zero-covariance rows get scales of exactly 0, i.e. stay zero."""
+    import test_raster_scale_rot_alpha as sra
+    sc, rq = sra._scale_rot_for(dict(cov3D=cov6), EDGE_SEED)
+    sc[list(zero_rows)] = 0.0
+    return sc, rq
+
+
+def chain_scale_rot(sc: torch.Tensor, rq: torch.Tensor, g_cov6) -> dict:
+    """dL/dscales, dL/drotations from dL/dcov3D [N,6] through float64 autograd of rasterizer.build_cov3d."""
+    from freesplat_amd.rasterizer import build_cov3d
+    s64, r64 = sc.double().requires_grad_(True), rq.double().requires_grad_(True)
+    (build_cov3d(s64, r64, 1.0) * torch.from_numpy(np.asarray(g_cov6, np.float64))).sum().backward()
+    return dict(scales=s64.grad.numpy(), rotations=r64.grad.numpy())
