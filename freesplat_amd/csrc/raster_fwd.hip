@@ -1127,19 +1127,26 @@ __device__ __forceinline__ void blend_quadrant(const uint32_t* pl, int n, const 
     // v_cmp + s_xor per survivor, v_cndmask + v_or to update it: ~4 of ~30 VALU per survivor in round 2's loop).
     unsigned long long done_m = __builtin_amdgcn_ballot_w64(!inside);
 
-    // VM: mask of the pixels this survivor can reach (power in range, alpha >= 1/255, pixel not yet saturated)
+    // VM: mask of the pixels this survivor can reach (power in range, alpha >= 1/255, pixel not yet saturated).
+    // The test (T (1 - alpha) >= 1e-4) and the done mask are wave-wide; the COMMIT runs under the execution mask of the
+    // lanes that take the survivor and is skipped when none does (s_and_saveexec + s_cbranch_execz): ~11 % of config 3's
+    // evaluated survivors reach only saturated pixels (profiles/r11_blend_commit_count.txt).  A lane that does not commit
+    // keeps C, T and `last` -- what fma(K, 0, C) and the selects of the predicated form gave it.
+    // (the empty asm makes T_ opaque inside the branch: without it the compiler turns the branch back into selects)
 #define FS_BLEND_ONE(VM, AL, OM, KR, POS)                                                           \
     {                                                                                               \
         const float test_T = T_ * (OM);                                                             \
         const unsigned long long vis = (VM) & ~done_m;                                              \
         const unsigned long long okc = __builtin_amdgcn_ballot_w64(test_T >= 0.0001f);              \
         done_m |= vis & ~okc;                     /* T would fall below 1e-4: the pixel is done, this one not applied */ \
-        const bool ok = __builtin_amdgcn_inverse_ballot_w64(vis & okc);                             \
-        const f32x2 wgt = splat2(ok ? (AL) * T_ : 0.0f); /* weight 0: sums unchanged (finite colours) */ \
-        C01 = fma2((f32x2){(KR).x, (KR).y}, wgt, C01);                                              \
-        C2D = fma2((f32x2){(KR).z, (KR).w}, wgt, C2D);                                              \
-        T_ = ok ? test_T : T_;                                                                      \
-        if constexpr (TRACK) last = ok ? __float_as_int(POS) : last;                                \
+        if (__builtin_amdgcn_inverse_ballot_w64(vis & okc)) {                                       \
+            const f32x2 wgt = splat2((AL) * T_);                                                    \
+            T_ = test_T;                                                                            \
+            asm volatile("" : "+v"(T_));                                                            \
+            C01 = fma2((f32x2){(KR).x, (KR).y}, wgt, C01);                                          \
+            C2D = fma2((f32x2){(KR).z, (KR).w}, wgt, C2D);                                          \
+            if constexpr (TRACK) last = __float_as_int(POS);                                        \
+        }                                                                                           \
     }
     // One step = two slots = four survivors a, b | c, d, blended strictly in list order.  PARTIAL: the quadrant's very
     // last step, `left` (1..3) entries; full steps carry no "does this entry exist" logic.
@@ -1186,6 +1193,11 @@ __device__ __forceinline__ void blend_quadrant(const uint32_t* pl, int n, const 
             gc = __builtin_amdgcn_ballot_w64(av.x >= 1.0f / 255.0f); gd = __builtin_amdgcn_ballot_w64(av.y >= 1.0f / 255.0f);
         }
         const f32x2 mw = splat2(1.0f) - aw, mv = splat2(1.0f) - av;
+        // the four colour / depth rows are in registers BEFORE the first commit branch (requested above, behind the exp
+        // chains): left alone, the compiler sinks ka's read into the first branch and waits for the whole LDS queue there
+        asm volatile("" :: "v"(ka.x), "v"(ka.y), "v"(ka.z), "v"(ka.w), "v"(kb.x), "v"(kb.y), "v"(kb.z), "v"(kb.w),
+                           "v"(kc.x), "v"(kc.y), "v"(kc.z), "v"(kc.w), "v"(mw.x), "v"(mw.y), "v"(mv.x), "v"(mv.y));
+        if constexpr (!PARTIAL) asm volatile("" :: "v"(kd.x), "v"(kd.y), "v"(kd.z), "v"(kd.w), "v"(mv.y));
         FS_BLEND_ONE(ma & ga, aw.x, mw.x, ka, c3.z)
         FS_BLEND_ONE(mb & gb, aw.y, mw.y, kb, c3.w)
         FS_BLEND_ONE(mc & gc, av.x, mv.x, kc, e3.z)
