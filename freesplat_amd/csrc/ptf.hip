@@ -17,6 +17,8 @@
 // projection uses plain IEEE mul/add/div in a fixed order, rounding is round-half-to-even.
 #include "fs_common.h"
 
+#include <cassert>
+
 namespace fs {
 
 constexpr uint32_t kZInit = 0x461C4000u;  // bits of 10000.0f (encoder_freesplat.py:464)
@@ -619,20 +621,6 @@ __global__ __launch_bounds__(256) void ptf_gru_inputs_bwd_kernel(int n_fuse, con
     }
 }
 
-__host__ __device__ inline size_t ptf_scratch_layout(int M, int P, size_t off[7])
-{
-    const int nbM = (M + kScanBlock - 1) / kScanBlock, nbP = (P + kScanBlock - 1) / kScanBlock;
-    size_t o = 0;
-    off[0] = o; o += align_up((size_t)P * 4, 256);            // zbuf
-    off[1] = o; o += align_up((size_t)M * 4, 256);            // pix_of
-    off[2] = o; o += align_up((size_t)M * 4, 256);            // zbits_of
-    off[3] = o; o += align_up((size_t)M, 256);                // win
-    off[4] = o; o += align_up((size_t)P, 256);                // app
-    off[5] = o; o += align_up((size_t)(nbM + nbP) * 4, 256);  // block counts / offsets
-    off[6] = o;
-    return o;
-}
-
 // ---- deterministic backward (fs_ptf_*_backward_det) ----
 // Several fused rows can share a pixel p of view i (exact z-buffer ties), and the default kernels add their terms into the view's
 // per-pixel gradients with float atomics: arrival order.  Here the adds happen in ascending fuse-row order.  An inverted index
@@ -640,19 +628,8 @@ __host__ __device__ inline size_t ptf_scratch_layout(int M, int P, size_t off[7]
 // rank in its segment is the number of rows of the segment before it.  A row whose pixel has no other row adds its terms
 // directly (a plain read-modify-write: no other thread of the launch touches that pixel); a tied row stores its terms at
 // (segment + rank), and ptf_det_tie_sum_kernel adds them to the pixel in rank order.
-// scratch: cnt[P], fill[P], total (zeroed together), seg[P], slot[n], list[n], terms[n][kPtfDetTerms]
+// scratch: det_layout below (cnt[P], fill[P], total -- zeroed together --, seg[P], slot[n], list[n], terms[n][kPtfDetTerms])
 constexpr int kPtfDetTerms = 66;          // the most terms a fused row adds: 64 latent floats + rho + om (gru inputs)
-__host__ __device__ inline size_t ptf_det_layout(int n, int P, size_t off[6])
-{
-    size_t o = 0;
-    off[0] = o; o += align_up(((size_t)2 * P + 1) * 4, 256);     // cnt, fill, total
-    off[1] = o; o += align_up((size_t)P * 4, 256);               // seg
-    off[2] = o; o += align_up((size_t)n * 4, 256);               // slot
-    off[3] = o; o += align_up((size_t)n * 4, 256);               // list
-    off[4] = o; o += align_up((size_t)n * kPtfDetTerms * 4, 256);   // terms
-    off[5] = o;
-    return o;
-}
 struct PtfDetIndex { int* cnt; int* fill; int* total; int* seg; int* slot; int* list; float* terms; };
 
 __global__ __launch_bounds__(256) void ptf_det_count_kernel(int n, const long long* __restrict__ fuse_pix, int* __restrict__ cnt)
@@ -812,16 +789,102 @@ __global__ __launch_bounds__(256) void ptf_gru_inputs_bwd_det_kernel(int n_fuse,
 
 using namespace fs;
 
+// ---- host layer ---------------------------------------------------------------------------------------------
+// Every scratch buffer is a run of 256-byte aligned regions.  Each carve-up is written ONCE, as a struct of byte offsets: the
+// size query returns its `total`, the launchers take their pointers from the same offsets.
+namespace {
+struct Carve {
+    size_t o = 0;
+    size_t take(size_t bytes) { const size_t at = o; o += align_up(bytes, 256); return at; }
+};
+template <class T> T* at(void* base, size_t off) { return (T*)((char*)base + off); }
+
+// one match (fs_ptf_scratch_bytes): M state rows (sized for at least one), P pixels
+struct MatchLayout { size_t zbuf, pix_of, zbits_of, win, app, blocks, total; };
+MatchLayout match_layout(int M, int P)
+{
+    if (M < 1) M = 1;
+    const int nbM = (M + kScanBlock - 1) / kScanBlock, nbP = (P + kScanBlock - 1) / kScanBlock;
+    Carve c;
+    MatchLayout L;
+    L.zbuf = c.take((size_t)P * 4);
+    L.pix_of = c.take((size_t)M * 4);
+    L.zbits_of = c.take((size_t)M * 4);
+    L.win = c.take((size_t)M);
+    L.app = c.take((size_t)P);
+    L.blocks = c.take((size_t)(nbM + nbP) * 4);        // block counts / offsets
+    L.total = c.o;
+    return L;
+}
+
+// one fold step (fs_ptf_fold_scratch_bytes): the match scratch, then the step's four index lists (fs_ptf_fold_step_lists)
+struct FoldLayout { size_t match, keep, fuse, fpix, app, reserved0, reserved1, total; };
+FoldLayout fold_layout(int M_max, int P)
+{
+    const size_t M1 = (size_t)(M_max > 0 ? M_max : 1), nf = (size_t)(M_max < P ? M_max : P), nf1 = nf > 0 ? nf : 1;
+    Carve c;
+    FoldLayout L;
+    L.match = c.take(match_layout(M_max, P).total);
+    L.keep = c.take(M1 * 8);
+    L.fuse = c.take(nf1 * 8);
+    L.fpix = c.take(nf1 * 8);
+    L.app = c.take((size_t)P * 8);
+    // reserved: nothing reads or writes these two since the GRU gathers and encodes its input rows itself and writes its rows
+    // into the out state (they held the pairs' [176] input rows and [64] output rows); they stay part of `total`
+    L.reserved0 = c.take(nf1 * 176 * 4);
+    L.reserved1 = c.take(nf1 * 64 * 4);
+    L.total = c.o;
+    return L;
+}
+
+size_t fold_zbuf_at(int M_max, int P) { return fold_layout(M_max, P).match + match_layout(M_max, P).zbuf; }
+
+// the camera block fs_ptf_fold keeps behind its largest step's FoldLayout
+struct CameraLayout { size_t kpix, E0, w2c, total; };
+CameraLayout camera_layout(int V, size_t P)
+{
+    Carve c;
+    CameraLayout L;
+    L.kpix = c.take((size_t)V * 4 * 4);
+    L.E0 = c.take(P * 64);
+    L.w2c = c.take((size_t)V * 64);
+    L.total = c.o;
+    return L;
+}
+
+// the deterministic backward's pixel -> rows index (fs_ptf_backward_det_bytes): n fused rows, P pixels
+struct DetLayout { size_t cnt, seg, slot, list, terms, total; };
+DetLayout det_layout(int n, int P)
+{
+    Carve c;
+    DetLayout L;
+    L.cnt = c.take(((size_t)2 * P + 1) * 4);           // cnt[P], fill[P], total
+    L.seg = c.take((size_t)P * 4);
+    L.slot = c.take((size_t)n * 4);
+    L.list = c.take((size_t)n * 4);
+    L.terms = c.take((size_t)n * kPtfDetTerms * 4);
+    L.total = c.o;
+    return L;
+}
+
+// the six state arrays of a caller, which the kernels only read
+PtfState ptf_state(const float* G, const float* X, const float* R, const float* O, const float* E, const float* D)
+{
+    return PtfState{const_cast<float*>(G), const_cast<float*>(X), const_cast<float*>(R), const_cast<float*>(O),
+                    const_cast<float*>(E), const_cast<float*>(D)};
+}
+bool all_set(const PtfState& s) { return s.G && s.X && s.R && s.O && s.E && s.D; }
+}  // namespace
+
 FS_API size_t fs_ptf_scratch_bytes(int32_t M, int32_t h, int32_t w)
 {
     if (M < 0 || h <= 0 || w <= 0) return 0;
-    size_t off[7];
-    return ptf_scratch_layout(M > 0 ? M : 1, h * w, off);
+    return match_layout(M, h * w).total;
 }
 
 // M: number of state rows, or (Mp != NULL) an upper bound of *Mp used for sizing grids and the scratch layout
-// zbuf_clean: the z-buffer (the first P words of the scratch) already holds 0xFFFFFFFF -- the previous step's emit kernel
-// leaves it so -- and the fill launch is skipped
+// zbuf_clean: the z-buffer already holds 0xFFFFFFFF -- the previous step's emit kernel leaves it so -- and the fill launch
+// is skipped
 static int ptf_match_impl(int32_t M, const int32_t* Mp, int32_t h, int32_t w, const float* xyz, const float* w2c,
                           const float* kpix, const float* depth_i, float depth_thres, void* scratch,
                           int64_t* keep_idx, int64_t* fuse_idx, int64_t* fuse_pix, int64_t* append_pix,
@@ -832,15 +895,13 @@ static int ptf_match_impl(int32_t M, const int32_t* Mp, int32_t h, int32_t w, co
     if (M > 0 && (!xyz || !keep_idx || !fuse_idx || !fuse_pix)) return FS_ERR_INVALID_ARG;
     hipStream_t st = (hipStream_t)stream_;
     const int P = h * w;
-    size_t off[7];
-    ptf_scratch_layout(M > 0 ? M : 1, P, off);
-    char* s = (char*)scratch;
-    uint32_t* zbuf = (uint32_t*)(s + off[0]);
-    int32_t* pix_of = (int32_t*)(s + off[1]);
-    uint32_t* zbits_of = (uint32_t*)(s + off[2]);
-    uint8_t* win = (uint8_t*)(s + off[3]);
-    uint8_t* app = (uint8_t*)(s + off[4]);
-    uint32_t* blocks = (uint32_t*)(s + off[5]);
+    const MatchLayout L = match_layout(M, P);
+    uint32_t* zbuf = at<uint32_t>(scratch, L.zbuf);
+    int32_t* pix_of = at<int32_t>(scratch, L.pix_of);
+    uint32_t* zbits_of = at<uint32_t>(scratch, L.zbits_of);
+    uint8_t* win = at<uint8_t>(scratch, L.win);
+    uint8_t* app = at<uint8_t>(scratch, L.app);
+    uint32_t* blocks = at<uint32_t>(scratch, L.blocks);
     const int nbM = (M + kScanBlock - 1) / kScanBlock, nbP = (P + kScanBlock - 1) / kScanBlock;
     ScopedStage prof_(kStPtf, st);
     if (!zbuf_clean) hipLaunchKernelGGL(ptf_fill_kernel, dim3((P + 255) / 256), dim3(256), 0, st, zbuf, P);
@@ -890,15 +951,12 @@ FS_API int fs_ptf_write_state(int32_t n_keep, int32_t n_fuse, int32_t n_app, con
     if (n_keep < 0 || n_fuse < 0 || n_app < 0) return FS_ERR_INVALID_ARG;
     const long long n_out = (long long)n_keep + n_fuse + n_app;
     if (n_out == 0) return FS_OK;
-    if (!g_i || !x_i || !rho_i || !om_i || !d_i || !E_i || !oG || !oX || !oR || !oO || !oE || !oD)
-        return FS_ERR_INVALID_ARG;
-    if ((n_keep || n_fuse) && (!G || !X || !R || !O || !E || !D)) return FS_ERR_INVALID_ARG;
+    const PtfState s = ptf_state(G, X, R, O, E, D), o{oG, oX, oR, oO, oE, oD};
+    if (!g_i || !x_i || !rho_i || !om_i || !d_i || !E_i || !all_set(o)) return FS_ERR_INVALID_ARG;
+    if ((n_keep || n_fuse) && !all_set(s)) return FS_ERR_INVALID_ARG;
     if (n_fuse && (!fused || !fuse_idx || !fuse_pix)) return FS_ERR_INVALID_ARG;
     hipStream_t st = (hipStream_t)stream_;
     ScopedStage prof_(kStPtf, st);
-    PtfState s{const_cast<float*>(G), const_cast<float*>(X), const_cast<float*>(R), const_cast<float*>(O),
-               const_cast<float*>(E), const_cast<float*>(D)};
-    PtfState o{oG, oX, oR, oO, oE, oD};
     hipLaunchKernelGGL(ptf_write_state_kernel<false>, dim3((unsigned)((n_out + 15) / 16)), dim3(256), 0, st, n_keep, n_fuse,
                        n_app, (const int32_t*)nullptr, (const long long*)keep_idx, (const long long*)fuse_idx, (const long long*)fuse_pix,
                        (const long long*)append_pix, s, g_i, x_i, rho_i, om_i, d_i, E_i, fused, o);
@@ -907,70 +965,45 @@ FS_API int fs_ptf_write_state(int32_t n_keep, int32_t n_fuse, int32_t n_app, con
 }
 
 // ---- one whole fold step without host involvement -----------------------------------------------------------
-namespace {
-struct FoldLayout { size_t match, keep, fuse, fpix, app, cat, fused, total; };
-FoldLayout fold_layout(int M_max, int P)
-{
-    FoldLayout L;
-    size_t off[7];
-    const size_t nf = (size_t)(M_max < P ? M_max : P);
-    size_t o = 0;
-    L.match = o; o += align_up(ptf_scratch_layout(M_max > 0 ? M_max : 1, P, off), 256);
-    L.keep = o;  o += align_up((size_t)(M_max > 0 ? M_max : 1) * 8, 256);
-    L.fuse = o;  o += align_up((nf > 0 ? nf : 1) * 8, 256);
-    L.fpix = o;  o += align_up((nf > 0 ? nf : 1) * 8, 256);
-    L.app = o;   o += align_up((size_t)P * 8, 256);
-    L.cat = o;   o += align_up((nf > 0 ? nf : 1) * 176 * 4, 256);
-    L.fused = o; o += align_up((nf > 0 ? nf : 1) * 64 * 4, 256);
-    L.total = o;
-    return L;
-}
-}  // namespace
-
 FS_API size_t fs_ptf_fold_scratch_bytes(int32_t M_max, int32_t h, int32_t w)
 {
     if (M_max < 0 || h <= 0 || w <= 0) return 0;
     return fold_layout(M_max, h * w).total;
 }
 
-static int fold_step_impl(int32_t M_max, const int32_t* M_dev, int32_t h, int32_t w, const float* G, const float* X,
-                          const float* R, const float* O, const float* E, const float* D, const float* g_i,
-                          const float* x_i, const float* rho_i, const float* om_i, const float* d_i, const float* E_i,
-                          const float* w2c, const float* kpix, float depth_thres, const float* gru_tables,
-                          void* scratch, float* oG, float* oX, float* oR, float* oO, float* oE, float* oD,
-                          int32_t* counts, void* stream_, bool zbuf_clean, float* save_side = nullptr, float* save_act = nullptr,
-                          float* save_cat = nullptr)
+namespace {
+struct FoldView { const float *g, *x, *rho, *om, *d, *E, *w2c, *kpix; };   // the view folded in: its arrays and its camera
+struct FoldSave { float *side, *act, *cat; };                             // all NULL: the GRU keeps nothing for a backward
+}  // namespace
+
+static int fold_step_impl(int32_t M_max, const int32_t* M_dev, int32_t h, int32_t w, const PtfState& in, const FoldView& v,
+                          float depth_thres, const float* gru_tables, void* scratch, const PtfState& out, int32_t* counts,
+                          void* stream_, bool zbuf_clean, const FoldSave& save = FoldSave{nullptr, nullptr, nullptr})
 {
-    if (M_max <= 0 || h <= 0 || w <= 0 || !G || !X || !R || !O || !E || !D || !g_i || !x_i || !rho_i || !om_i || !d_i ||
-        !E_i || !w2c || !kpix || !gru_tables || !scratch || !oG || !oX || !oR || !oO || !oE || !oD || !counts)
+    if (M_max <= 0 || h <= 0 || w <= 0 || !all_set(in) || !v.g || !v.x || !v.rho || !v.om || !v.d || !v.E || !v.w2c ||
+        !v.kpix || !gru_tables || !scratch || !all_set(out) || !counts)
         return FS_ERR_INVALID_ARG;
     hipStream_t st = (hipStream_t)stream_;
     const int P = h * w;
     const FoldLayout L = fold_layout(M_max, P);
-    char* s = (char*)scratch;
-    long long *keep = (long long*)(s + L.keep), *fuse = (long long*)(s + L.fuse), *fpix = (long long*)(s + L.fpix),
-              *app = (long long*)(s + L.app);
-    float *cat = (float*)(s + L.cat), *fused = (float*)(s + L.fused);
-    int rc = ptf_match_impl(M_max, M_dev, h, w, X, w2c, kpix, d_i, depth_thres, s + L.match, (int64_t*)keep,
-                            (int64_t*)fuse, (int64_t*)fpix, (int64_t*)app, counts, stream_, zbuf_clean);
+    long long *keep = at<long long>(scratch, L.keep), *fuse = at<long long>(scratch, L.fuse),
+              *fpix = at<long long>(scratch, L.fpix), *app = at<long long>(scratch, L.app);
+    int rc = ptf_match_impl(M_max, M_dev, h, w, in.X, v.w2c, v.kpix, v.d, depth_thres, at<char>(scratch, L.match),
+                            (int64_t*)keep, (int64_t*)fuse, (int64_t*)fpix, (int64_t*)app, counts, stream_, zbuf_clean);
     if (rc != FS_OK) return rc;
     const int nf_max = M_max < P ? M_max : P;
     ScopedStage prof_(kStPtf, st);
-    (void)cat; (void)fused;  // (the GRU gathers and encodes its input rows itself and writes its rows into the out state)
-    rc = launch_ptf_gru_gather(nf_max, counts, (const long long*)fuse, (const long long*)fpix, G, R, O, g_i, rho_i, om_i,
-                               gru_tables, oG, true, st, save_side, save_act, save_cat);
+    rc = launch_ptf_gru_gather(nf_max, counts, fuse, fpix, in.G, in.R, in.O, v.g, v.rho, v.om, gru_tables, out.G, true, st,
+                               save.side, save.act, save.cat);
     if (rc != FS_OK) return rc;
-    PtfState si{const_cast<float*>(G), const_cast<float*>(X), const_cast<float*>(R), const_cast<float*>(O),
-                const_cast<float*>(E), const_cast<float*>(D)};
-    PtfState so{oG, oX, oR, oO, oE, oD};
     const long long n_out_max = (long long)M_max + P;
     // (the counts are on the device: both grids cover their worst case, workgroups past the rows that exist leave at once)
     const unsigned cap = 256 * 8 * 4;        // 8 workgroups per CU resident, four rounds of them: enough to balance, few enough to be cheap when empty
     hipLaunchKernelGGL(ptf_write_state_kernel<true>, dim3(std::min<unsigned>((unsigned)((n_out_max + 15) / 16), cap)), dim3(256), 0, st, 0, 0, 0,
                        (const int32_t*)counts, (const long long*)keep, (const long long*)fuse, (const long long*)fpix,
-                       (const long long*)app, si, g_i, x_i, rho_i, om_i, d_i, E_i, (const float*)nullptr, so);
+                       (const long long*)app, in, v.g, v.x, v.rho, v.om, v.d, v.E, (const float*)nullptr, out);
     hipLaunchKernelGGL(ptf_write_state_fused_kernel, dim3(std::min<unsigned>((unsigned)((nf_max + 63) / 64), cap)), dim3(256), 0, st, 0, 0,
-                       (const int32_t*)counts, (const long long*)fuse, (const long long*)fpix, si, x_i, rho_i, om_i, d_i, E_i, so);
+                       (const int32_t*)counts, (const long long*)fuse, (const long long*)fpix, in, v.x, v.rho, v.om, v.d, v.E, out);
     FS_CHECK_LAUNCH("ptf_write_state");
     return FS_OK;
 }
@@ -982,8 +1015,8 @@ FS_API int fs_ptf_fold_step(int32_t M_max, const int32_t* M_dev, int32_t h, int3
                             void* scratch, float* oG, float* oX, float* oR, float* oO, float* oE, float* oD,
                             int32_t* counts, void* stream_)
 {
-    return fold_step_impl(M_max, M_dev, h, w, G, X, R, O, E, D, g_i, x_i, rho_i, om_i, d_i, E_i, w2c, kpix, depth_thres,
-                          gru_tables, scratch, oG, oX, oR, oO, oE, oD, counts, stream_, false);
+    return fold_step_impl(M_max, M_dev, h, w, ptf_state(G, X, R, O, E, D), FoldView{g_i, x_i, rho_i, om_i, d_i, E_i, w2c, kpix},
+                          depth_thres, gru_tables, scratch, PtfState{oG, oX, oR, oO, oE, oD}, counts, stream_, false);
 }
 
 // fs_ptf_fold_step for a TRAINING fold (round 6): the GRU additionally leaves, for fused pair t (the order of the step's fuse list),
@@ -998,8 +1031,9 @@ FS_API int fs_ptf_fold_step_save(int32_t M_max, const int32_t* M_dev, int32_t h,
                                  int32_t* counts, float* side, float* act, float* cat, void* stream_)
 {
     if (!side || !act || !cat) return FS_ERR_INVALID_ARG;
-    return fold_step_impl(M_max, M_dev, h, w, G, X, R, O, E, D, g_i, x_i, rho_i, om_i, d_i, E_i, w2c, kpix, depth_thres,
-                          gru_tables, scratch, oG, oX, oR, oO, oE, oD, counts, stream_, false, side, act, cat);
+    return fold_step_impl(M_max, M_dev, h, w, ptf_state(G, X, R, O, E, D), FoldView{g_i, x_i, rho_i, om_i, d_i, E_i, w2c, kpix},
+                          depth_thres, gru_tables, scratch, PtfState{oG, oX, oR, oO, oE, oD}, counts, stream_, false,
+                          FoldSave{side, act, cat});
 }
 
 // Camera constants of the fold in one launch: thread i scales the normalised intrinsics of view i to pixels
@@ -1020,8 +1054,16 @@ __global__ __launch_bounds__(256) void ptf_cameras_kernel(int V, int P, int h, i
     kpix[4 * t + 2] = K[2] * (float)w; kpix[4 * t + 3] = K[5] * (float)h;
 }
 
-namespace {
-size_t fold_camera_bytes(int V, int P) { return align_up((size_t)V * 4 * 4, 256) + align_up((size_t)P * 64, 256) + align_up((size_t)V * 64, 256); }
+// zbuf: NULL, or P words to fill with 0xFFFFFFFF in the same launch
+static int launch_ptf_cameras(int32_t V, int32_t h, int32_t w, const float* Es, const float* Kn, float* kpix, float* E0,
+                              uint32_t* zbuf, hipStream_t st)
+{
+    const long long P = (long long)h * w;
+    const long long nt = P * 4 > V ? P * 4 : V;
+    hipLaunchKernelGGL(ptf_cameras_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, V, (int)P, h, w, Es, Kn,
+                       kpix, E0, zbuf);
+    FS_CHECK_LAUNCH("ptf_cameras");
+    return FS_OK;
 }
 
 // The per-view pixel intrinsics kpix [V,4] = (fx w, fy h, cx w, cy h) and the initial per-Gaussian extrinsics E0 [P,16]
@@ -1031,18 +1073,14 @@ FS_API int fs_ptf_cameras(int32_t V, int32_t h, int32_t w, const float* Es, cons
                           void* stream_)
 {
     if (V < 1 || h <= 0 || w <= 0 || !Es || !Kn || !kpix || !E0) return FS_ERR_INVALID_ARG;
-    const long long P = (long long)h * w;
-    const long long nt = P * 4 > V ? P * 4 : V;
-    hipLaunchKernelGGL(ptf_cameras_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, V, (int)P,
-                       h, w, Es, Kn, kpix, E0, (uint32_t*)nullptr);
-    FS_CHECK_LAUNCH("ptf_cameras");
-    return FS_OK;
+    return launch_ptf_cameras(V, h, w, Es, Kn, kpix, E0, nullptr, (hipStream_t)stream_);
 }
 
+// scratch of fs_ptf_fold: the FoldLayout of its last (largest) step, then the CameraLayout
 FS_API size_t fs_ptf_fold_bytes(int32_t V, int32_t h, int32_t w)
 {
     if (V < 2 || h <= 0 || w <= 0) return 0;
-    return fold_layout((V - 1) * h * w, h * w).total + fold_camera_bytes(V, h * w);
+    return fold_layout((V - 1) * h * w, h * w).total + camera_layout(V, (size_t)(h * w)).total;
 }
 
 // All fold steps of one scene in one host call: views 1 .. V-1 are folded into the state that starts as view 0.
@@ -1060,34 +1098,31 @@ FS_API int fs_ptf_fold(int32_t V, int32_t h, int32_t w, const float* lat, const 
         !bufA || !bufB || !counts)
         return FS_ERR_INVALID_ARG;
     const size_t P = (size_t)h * w;
-    hipStream_t st = (hipStream_t)stream_;
-    char* cam = (char*)scratch + fold_layout((int)((V - 1) * P), (int)P).total;
-    float* kpix = (float*)cam;
-    float* E0 = (float*)(cam + align_up((size_t)V * 4 * 4, 256));
+    const CameraLayout C = camera_layout(V, P);
+    char* cam = at<char>(scratch, fold_layout((int)((V - 1) * P), (int)P).total);
+    float *kpix = at<float>(cam, C.kpix), *E0 = at<float>(cam, C.E0);
     if (!w2c) {     // the world-to-camera matrices are formed here (fs_invert_4x4, into the scratch): one launch, no extra call
-        float* inv = (float*)(cam + align_up((size_t)V * 4 * 4, 256) + align_up(P * 64, 256));
+        float* inv = at<float>(cam, C.w2c);
         const int rc = fs_invert_4x4(V, Es, inv, stream_);
         if (rc != FS_OK) return rc;
         w2c = inv;
     }
-    {
-        const long long nt = (long long)P * 4 > V ? (long long)P * 4 : V;
-        // (the z-buffer is the first P words of the scratch for every step's layout; cleared here for step 1, by each
-        //  step's emit kernel for the next)
-        hipLaunchKernelGGL(ptf_cameras_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, V, (int)P, h, w, Es,
-                           Kn, kpix, E0, (uint32_t*)scratch);
-        FS_CHECK_LAUNCH("ptf_cameras");
-    }
-    const float* cur[6] = {lat, xs, rho, om, E0, dep};
+    // The z-buffer is cleared here for step 1 and by each step's emit kernel for the next: the steps' layouts differ (M_max
+    // grows), their z-buffers must not.
+    const size_t zbuf_at = fold_zbuf_at((int)P, (int)P);
+    for (int i = 2; i < V; ++i) assert(fold_zbuf_at((int)(i * P), (int)P) == zbuf_at);
+    int rc = launch_ptf_cameras(V, h, w, Es, Kn, kpix, E0, at<uint32_t>(scratch, zbuf_at), (hipStream_t)stream_);
+    if (rc != FS_OK) return rc;
+    PtfState cur = ptf_state(lat, xs, rho, om, E0, dep);
     for (int i = 1; i < V; ++i) {
-        float* const* out = (i & 1) ? bufA : bufB;
-        const int rc = fold_step_impl((int32_t)(i * P), i == 1 ? nullptr : counts + 4 * (i - 1) + 3, h, w, cur[0], cur[1],
-                                        cur[2], cur[3], cur[4], cur[5], lat + i * P * 64, xs + i * P * 3, rho + i * P,
-                                        om + i * P, dep + i * P, Es + 16 * (size_t)i, w2c + 16 * (size_t)i,
-                                        kpix + 4 * (size_t)i, depth_thres, gru_tables, scratch, out[0], out[1], out[2],
-                                        out[3], out[4], out[5], counts + 4 * i, stream_, true);
+        float* const* o = (i & 1) ? bufA : bufB;
+        const PtfState out{o[0], o[1], o[2], o[3], o[4], o[5]};
+        const FoldView v{lat + i * P * 64, xs + i * P * 3, rho + i * P, om + i * P, dep + i * P, Es + 16 * (size_t)i,
+                         w2c + 16 * (size_t)i, kpix + 4 * (size_t)i};
+        rc = fold_step_impl((int32_t)(i * P), i == 1 ? nullptr : counts + 4 * (i - 1) + 3, h, w, cur, v, depth_thres,
+                            gru_tables, scratch, out, counts + 4 * i, stream_, true);
         if (rc != FS_OK) return rc;
-        for (int k = 0; k < 6; ++k) cur[k] = out[k];
+        cur = out;
     }
     return FS_OK;
 }
@@ -1100,9 +1135,79 @@ FS_API int fs_ptf_fold_step_lists(int32_t M_max, int32_t h, int32_t w, void* scr
 {
     if (M_max <= 0 || h <= 0 || w <= 0 || !scratch || !lists) return FS_ERR_INVALID_ARG;
     const FoldLayout L = fold_layout(M_max, h * w);
-    char* s = (char*)scratch;
-    lists[0] = (int64_t*)(s + L.keep); lists[1] = (int64_t*)(s + L.fuse);
-    lists[2] = (int64_t*)(s + L.fpix); lists[3] = (int64_t*)(s + L.app);
+    lists[0] = at<int64_t>(scratch, L.keep); lists[1] = at<int64_t>(scratch, L.fuse);
+    lists[2] = at<int64_t>(scratch, L.fpix); lists[3] = at<int64_t>(scratch, L.app);
+    return FS_OK;
+}
+
+FS_API size_t fs_ptf_backward_det_bytes(int32_t n_fuse, int32_t P)
+{
+    if (n_fuse < 0 || P <= 0) return 0;
+    return det_layout(n_fuse, P).total;
+}
+
+// builds the pixel -> rows index of the fuse list (integer atomics only); false: a launch failed
+static bool ptf_det_index(int n, int P, const long long* fuse_pix, void* scratch, PtfDetIndex& ix, hipStream_t st)
+{
+    const DetLayout L = det_layout(n, P);
+    ix.cnt = at<int>(scratch, L.cnt); ix.fill = ix.cnt + P; ix.total = ix.fill + P;
+    ix.seg = at<int>(scratch, L.seg); ix.slot = at<int>(scratch, L.slot); ix.list = at<int>(scratch, L.list);
+    ix.terms = at<float>(scratch, L.terms);
+    if (hipMemsetAsync(ix.cnt, 0, ((size_t)2 * P + 1) * 4, st) != hipSuccess) {
+        set_last_error("ptf det index memset", hipGetLastError());
+        return false;
+    }
+    const dim3 g((unsigned)((n + 255) / 256));
+    hipLaunchKernelGGL(ptf_det_count_kernel, g, dim3(256), 0, st, n, fuse_pix, ix.cnt);
+    hipLaunchKernelGGL(ptf_det_segment_kernel, g, dim3(256), 0, st, n, fuse_pix, ix);
+    hipLaunchKernelGGL(ptf_det_fill_kernel, g, dim3(256), 0, st, n, fuse_pix, ix);
+    return true;
+}
+
+// Both backward drivers come in two forms.  The default form adds the fused rows' terms into the view's per-pixel gradients
+// with float atomics.  The deterministic form (ABI 9, `det`) adds them in ascending row order and is bitwise repeatable: it
+// also takes P = the view's pixel count (every fuse_pix < P) and a scratch of fs_ptf_backward_det_bytes(n_fuse, P) bytes.
+static int write_state_backward_impl(bool det, int32_t n_keep, int32_t n_fuse, int32_t n_app, const int64_t* keep_idx,
+                                     const int64_t* fuse_idx, const int64_t* fuse_pix, const int64_t* append_pix,
+                                     const float* X, const float* R, const float* E, const float* D, const float* x_i,
+                                     const float* rho_i, const float* d_i, const float* E_i, float* const* g_out,
+                                     float* const* g_in, float* g_lat_i, float* g_x_i, float* g_rho_i, float* g_om_i,
+                                     float* g_d_i, int32_t P, void* scratch, void* stream_)
+{
+    if (n_keep < 0 || n_fuse < 0 || n_app < 0 || (det && P < 0) || !g_out || !g_in) return FS_ERR_INVALID_ARG;
+    const long long n_out = (long long)n_keep + n_fuse + n_app;
+    if (n_out == 0) return FS_OK;
+    if (!g_lat_i || !g_x_i || !g_rho_i || !g_om_i || !g_d_i || !x_i || !rho_i || !d_i || !E_i) return FS_ERR_INVALID_ARG;
+    if (n_keep || n_fuse) {
+        if (!X || !R || !E || !D) return FS_ERR_INVALID_ARG;
+        for (int k = 0; k < 6; ++k)
+            if (!g_in[k]) return FS_ERR_INVALID_ARG;
+    }
+    if (det && n_fuse > 0 && (!fuse_idx || !fuse_pix || !scratch || P <= 0)) return FS_ERR_INVALID_ARG;
+    hipStream_t st = (hipStream_t)stream_;
+    ScopedStage prof_(kStPtf, st);
+    const PtfState s = ptf_state(nullptr, X, R, nullptr, E, D);
+    PtfGrad go{g_out[0], g_out[1], g_out[2], g_out[3], g_out[4], g_out[5]};
+    PtfGrad gs{g_in[0], g_in[1], g_in[2], g_in[3], g_in[4], g_in[5]};
+    const long long *fidx = (const long long*)fuse_idx, *fpix = (const long long*)fuse_pix;
+    const long long n_ka = (long long)n_keep + n_app;
+    if (n_ka > 0)   // (kept and appended rows: stores and read-modify-writes of pixels no fused row has, no atomics)
+        hipLaunchKernelGGL(ptf_write_state_bwd_kernel, dim3((unsigned)((n_ka + 63) / 64)), dim3(256), 0, st, n_keep, n_fuse,
+                           n_app, (const long long*)keep_idx, fidx, fpix, (const long long*)append_pix, s, x_i, rho_i, d_i, E_i,
+                           go, gs, g_lat_i, g_x_i, g_rho_i, g_om_i, g_d_i);
+    const dim3 grid((unsigned)((n_fuse + 63) / 64));
+    if (n_fuse > 0 && !det)
+        hipLaunchKernelGGL(ptf_write_state_bwd_fused_kernel, grid, dim3(256), 0, st, n_keep, n_fuse, fidx, fpix, s, x_i, rho_i,
+                           d_i, E_i, go, gs, g_x_i, g_rho_i, g_om_i, g_d_i);
+    if (n_fuse > 0 && det) {
+        PtfDetIndex ix;
+        if (!ptf_det_index(n_fuse, P, fpix, scratch, ix, st)) return FS_ERR_LAUNCH;
+        hipLaunchKernelGGL(ptf_write_state_bwd_fused_det_kernel, grid, dim3(256), 0, st, n_keep, n_fuse, fidx, fpix, s, x_i,
+                           rho_i, d_i, E_i, go, gs, g_x_i, g_rho_i, g_om_i, g_d_i, ix);
+        hipLaunchKernelGGL(ptf_det_tie_sum_kernel<0>, dim3((unsigned)(((long long)n_fuse * 6 + 255) / 256)), dim3(256), 0, st, n_fuse,
+                           fpix, ix, g_lat_i, g_x_i, g_rho_i, g_om_i, g_d_i);
+    }
+    FS_CHECK_LAUNCH(det ? "ptf_write_state_bwd_det" : "ptf_write_state_bwd");
     return FS_OK;
 }
 
@@ -1118,84 +1223,10 @@ FS_API int fs_ptf_write_state_backward(int32_t n_keep, int32_t n_fuse, int32_t n
                                        float* const* g_out, float* const* g_in, float* g_lat_i, float* g_x_i,
                                        float* g_rho_i, float* g_om_i, float* g_d_i, void* stream_)
 {
-    if (n_keep < 0 || n_fuse < 0 || n_app < 0 || !g_out || !g_in) return FS_ERR_INVALID_ARG;
-    const long long n_out = (long long)n_keep + n_fuse + n_app;
-    if (n_out == 0) return FS_OK;
-    if (!g_lat_i || !g_x_i || !g_rho_i || !g_om_i || !g_d_i || !x_i || !rho_i || !d_i || !E_i) return FS_ERR_INVALID_ARG;
-    if (n_keep || n_fuse) {
-        if (!X || !R || !E || !D) return FS_ERR_INVALID_ARG;
-        for (int k = 0; k < 6; ++k)
-            if (!g_in[k]) return FS_ERR_INVALID_ARG;
-    }
-    hipStream_t st = (hipStream_t)stream_;
-    ScopedStage prof_(kStPtf, st);
-    PtfState s{nullptr, const_cast<float*>(X), const_cast<float*>(R), nullptr, const_cast<float*>(E), const_cast<float*>(D)};
-    PtfGrad go{g_out[0], g_out[1], g_out[2], g_out[3], g_out[4], g_out[5]};
-    PtfGrad gs{g_in[0], g_in[1], g_in[2], g_in[3], g_in[4], g_in[5]};
-    const long long n_ka = (long long)n_keep + n_app;
-    if (n_ka > 0)
-        hipLaunchKernelGGL(ptf_write_state_bwd_kernel, dim3((unsigned)((n_ka + 63) / 64)), dim3(256), 0, st, n_keep, n_fuse,
-                           n_app, (const long long*)keep_idx, (const long long*)fuse_idx, (const long long*)fuse_pix,
-                           (const long long*)append_pix, s, x_i, rho_i, d_i, E_i, go, gs, g_lat_i, g_x_i, g_rho_i, g_om_i, g_d_i);
-    if (n_fuse > 0)
-        hipLaunchKernelGGL(ptf_write_state_bwd_fused_kernel, dim3((unsigned)((n_fuse + 63) / 64)), dim3(256), 0, st, n_keep, n_fuse,
-                           (const long long*)fuse_idx, (const long long*)fuse_pix, s, x_i, rho_i, d_i, E_i, go, gs, g_x_i, g_rho_i,
-                           g_om_i, g_d_i);
-    FS_CHECK_LAUNCH("ptf_write_state_bwd");
-    return FS_OK;
+    return write_state_backward_impl(false, n_keep, n_fuse, n_app, keep_idx, fuse_idx, fuse_pix, append_pix, X, R, E, D, x_i,
+                                     rho_i, d_i, E_i, g_out, g_in, g_lat_i, g_x_i, g_rho_i, g_om_i, g_d_i, 0, nullptr, stream_);
 }
 
-// Backward of fs_ptf_gru_inputs: dcat [n_fuse,176] -> g_G [M,64] rows fuse_idx (stored), g_R / g_O [M] (added to what
-// fs_ptf_write_state_backward stored), g_lat_i / g_rho_i / g_om_i of the view (accumulated, atomics).
-FS_API int fs_ptf_gru_inputs_backward(int32_t n_fuse, const int64_t* fuse_idx, const int64_t* fuse_pix, const float* R,
-                                      const float* O, const float* rho_i, const float* om_i, const float* dcat,
-                                      float* g_G, float* g_R, float* g_O, float* g_lat_i, float* g_rho_i, float* g_om_i,
-                                      void* stream_)
-{
-    if (n_fuse < 0) return FS_ERR_INVALID_ARG;
-    if (n_fuse == 0) return FS_OK;
-    if (!fuse_idx || !fuse_pix || !R || !O || !rho_i || !om_i || !dcat || !g_G || !g_R || !g_O || !g_lat_i || !g_rho_i ||
-        !g_om_i)
-        return FS_ERR_INVALID_ARG;
-    hipStream_t st = (hipStream_t)stream_;
-    ScopedStage prof_(kStPtf, st);
-    hipLaunchKernelGGL(ptf_gru_inputs_bwd_kernel, dim3((n_fuse + 15) / 16), dim3(256), 0, st, n_fuse,
-                       (const long long*)fuse_idx, (const long long*)fuse_pix, R, O, rho_i, om_i, dcat, g_G, g_R, g_O,
-                       g_lat_i, g_rho_i, g_om_i);
-    FS_CHECK_LAUNCH("ptf_gru_inputs_bwd");
-    return FS_OK;
-}
-
-// ---- deterministic backward (ABI 9) ----
-FS_API size_t fs_ptf_backward_det_bytes(int32_t n_fuse, int32_t P)
-{
-    if (n_fuse < 0 || P <= 0) return 0;
-    size_t off[6];
-    return ptf_det_layout(n_fuse, P, off);
-}
-
-// builds the pixel -> rows index of the fuse list (integer atomics only); false: a launch failed
-static bool ptf_det_index(int n, int P, const long long* fuse_pix, void* scratch, PtfDetIndex& ix, hipStream_t st)
-{
-    size_t off[6];
-    ptf_det_layout(n, P, off);
-    char* base = (char*)scratch;
-    ix.cnt = (int*)(base + off[0]); ix.fill = ix.cnt + P; ix.total = ix.fill + P;
-    ix.seg = (int*)(base + off[1]); ix.slot = (int*)(base + off[2]); ix.list = (int*)(base + off[3]);
-    ix.terms = (float*)(base + off[4]);
-    if (hipMemsetAsync(ix.cnt, 0, ((size_t)2 * P + 1) * 4, st) != hipSuccess) {
-        set_last_error("ptf det index memset", hipGetLastError());
-        return false;
-    }
-    const dim3 g((unsigned)((n + 255) / 256));
-    hipLaunchKernelGGL(ptf_det_count_kernel, g, dim3(256), 0, st, n, fuse_pix, ix.cnt);
-    hipLaunchKernelGGL(ptf_det_segment_kernel, g, dim3(256), 0, st, n, fuse_pix, ix);
-    hipLaunchKernelGGL(ptf_det_fill_kernel, g, dim3(256), 0, st, n, fuse_pix, ix);
-    return true;
-}
-
-// fs_ptf_write_state_backward, bitwise repeatable: the fused rows add into the view's per-pixel gradients in ascending row
-// order.  P = the view's pixel count (every fuse_pix < P); scratch = fs_ptf_backward_det_bytes(n_fuse, P) bytes.
 FS_API int fs_ptf_write_state_backward_det(int32_t n_keep, int32_t n_fuse, int32_t n_app, const int64_t* keep_idx,
                                            const int64_t* fuse_idx, const int64_t* fuse_pix, const int64_t* append_pix,
                                            const float* X, const float* R, const float* E, const float* D,
@@ -1203,59 +1234,55 @@ FS_API int fs_ptf_write_state_backward_det(int32_t n_keep, int32_t n_fuse, int32
                                            float* const* g_out, float* const* g_in, float* g_lat_i, float* g_x_i,
                                            float* g_rho_i, float* g_om_i, float* g_d_i, int32_t P, void* scratch, void* stream_)
 {
-    if (n_keep < 0 || n_fuse < 0 || n_app < 0 || P < 0 || !g_out || !g_in) return FS_ERR_INVALID_ARG;
-    const long long n_out = (long long)n_keep + n_fuse + n_app;
-    if (n_out == 0) return FS_OK;
-    if (!g_lat_i || !g_x_i || !g_rho_i || !g_om_i || !g_d_i || !x_i || !rho_i || !d_i || !E_i) return FS_ERR_INVALID_ARG;
-    if (n_keep || n_fuse) {
-        if (!X || !R || !E || !D) return FS_ERR_INVALID_ARG;
-        for (int k = 0; k < 6; ++k)
-            if (!g_in[k]) return FS_ERR_INVALID_ARG;
-    }
-    if (n_fuse > 0 && (!fuse_idx || !fuse_pix || !scratch || P <= 0)) return FS_ERR_INVALID_ARG;
+    return write_state_backward_impl(true, n_keep, n_fuse, n_app, keep_idx, fuse_idx, fuse_pix, append_pix, X, R, E, D, x_i,
+                                     rho_i, d_i, E_i, g_out, g_in, g_lat_i, g_x_i, g_rho_i, g_om_i, g_d_i, P, scratch, stream_);
+}
+
+static int gru_inputs_backward_impl(bool det, int32_t n_fuse, const int64_t* fuse_idx, const int64_t* fuse_pix, const float* R,
+                                    const float* O, const float* rho_i, const float* om_i, const float* dcat, float* g_G,
+                                    float* g_R, float* g_O, float* g_lat_i, float* g_rho_i, float* g_om_i, int32_t P,
+                                    void* scratch, void* stream_)
+{
+    if (n_fuse < 0 || (det && P < 0)) return FS_ERR_INVALID_ARG;
+    if (n_fuse == 0) return FS_OK;
+    if (!fuse_idx || !fuse_pix || !R || !O || !rho_i || !om_i || !dcat || !g_G || !g_R || !g_O || !g_lat_i || !g_rho_i ||
+        !g_om_i || (det && (!scratch || P <= 0)))
+        return FS_ERR_INVALID_ARG;
     hipStream_t st = (hipStream_t)stream_;
     ScopedStage prof_(kStPtf, st);
-    PtfState s{nullptr, const_cast<float*>(X), const_cast<float*>(R), nullptr, const_cast<float*>(E), const_cast<float*>(D)};
-    PtfGrad go{g_out[0], g_out[1], g_out[2], g_out[3], g_out[4], g_out[5]};
-    PtfGrad gs{g_in[0], g_in[1], g_in[2], g_in[3], g_in[4], g_in[5]};
-    const long long n_ka = (long long)n_keep + n_app;
-    if (n_ka > 0)   // (kept and appended rows: stores and read-modify-writes of pixels no fused row has, no atomics)
-        hipLaunchKernelGGL(ptf_write_state_bwd_kernel, dim3((unsigned)((n_ka + 63) / 64)), dim3(256), 0, st, n_keep, n_fuse,
-                           n_app, (const long long*)keep_idx, (const long long*)fuse_idx, (const long long*)fuse_pix,
-                           (const long long*)append_pix, s, x_i, rho_i, d_i, E_i, go, gs, g_lat_i, g_x_i, g_rho_i, g_om_i, g_d_i);
-    if (n_fuse > 0) {
+    const long long *fidx = (const long long*)fuse_idx, *fpix = (const long long*)fuse_pix;
+    const dim3 grid((n_fuse + 15) / 16);
+    if (!det) {
+        hipLaunchKernelGGL(ptf_gru_inputs_bwd_kernel, grid, dim3(256), 0, st, n_fuse, fidx, fpix, R, O, rho_i, om_i, dcat, g_G,
+                           g_R, g_O, g_lat_i, g_rho_i, g_om_i);
+    } else {
         PtfDetIndex ix;
-        if (!ptf_det_index(n_fuse, P, (const long long*)fuse_pix, scratch, ix, st)) return FS_ERR_LAUNCH;
-        hipLaunchKernelGGL(ptf_write_state_bwd_fused_det_kernel, dim3((unsigned)((n_fuse + 63) / 64)), dim3(256), 0, st, n_keep,
-                           n_fuse, (const long long*)fuse_idx, (const long long*)fuse_pix, s, x_i, rho_i, d_i, E_i, go, gs, g_x_i,
-                           g_rho_i, g_om_i, g_d_i, ix);
-        hipLaunchKernelGGL(ptf_det_tie_sum_kernel<0>, dim3((unsigned)(((long long)n_fuse * 6 + 255) / 256)), dim3(256), 0, st, n_fuse,
-                           (const long long*)fuse_pix, ix, g_lat_i, g_x_i, g_rho_i, g_om_i, g_d_i);
+        if (!ptf_det_index(n_fuse, P, fpix, scratch, ix, st)) return FS_ERR_LAUNCH;
+        hipLaunchKernelGGL(ptf_gru_inputs_bwd_det_kernel, grid, dim3(256), 0, st, n_fuse, fidx, fpix, R, O, rho_i, om_i, dcat,
+                           g_G, g_R, g_O, g_lat_i, g_rho_i, g_om_i, ix);
+        hipLaunchKernelGGL(ptf_det_tie_sum_kernel<1>, dim3((unsigned)(((long long)n_fuse * 66 + 255) / 256)), dim3(256), 0, st, n_fuse,
+                           fpix, ix, g_lat_i, (float*)nullptr, g_rho_i, g_om_i, (float*)nullptr);
     }
-    FS_CHECK_LAUNCH("ptf_write_state_bwd_det");
+    FS_CHECK_LAUNCH(det ? "ptf_gru_inputs_bwd_det" : "ptf_gru_inputs_bwd");
     return FS_OK;
 }
 
-// fs_ptf_gru_inputs_backward, bitwise repeatable (as fs_ptf_write_state_backward_det; same P and scratch size)
+// Backward of fs_ptf_gru_inputs: dcat [n_fuse,176] -> g_G [M,64] rows fuse_idx (stored), g_R / g_O [M] (added to what
+// fs_ptf_write_state_backward stored), g_lat_i / g_rho_i / g_om_i of the view (accumulated).
+FS_API int fs_ptf_gru_inputs_backward(int32_t n_fuse, const int64_t* fuse_idx, const int64_t* fuse_pix, const float* R,
+                                      const float* O, const float* rho_i, const float* om_i, const float* dcat,
+                                      float* g_G, float* g_R, float* g_O, float* g_lat_i, float* g_rho_i, float* g_om_i,
+                                      void* stream_)
+{
+    return gru_inputs_backward_impl(false, n_fuse, fuse_idx, fuse_pix, R, O, rho_i, om_i, dcat, g_G, g_R, g_O, g_lat_i, g_rho_i,
+                                    g_om_i, 0, nullptr, stream_);
+}
+
 FS_API int fs_ptf_gru_inputs_backward_det(int32_t n_fuse, const int64_t* fuse_idx, const int64_t* fuse_pix, const float* R,
                                           const float* O, const float* rho_i, const float* om_i, const float* dcat,
                                           float* g_G, float* g_R, float* g_O, float* g_lat_i, float* g_rho_i, float* g_om_i,
                                           int32_t P, void* scratch, void* stream_)
 {
-    if (n_fuse < 0 || P < 0) return FS_ERR_INVALID_ARG;
-    if (n_fuse == 0) return FS_OK;
-    if (!fuse_idx || !fuse_pix || !R || !O || !rho_i || !om_i || !dcat || !g_G || !g_R || !g_O || !g_lat_i || !g_rho_i ||
-        !g_om_i || !scratch || P <= 0)
-        return FS_ERR_INVALID_ARG;
-    hipStream_t st = (hipStream_t)stream_;
-    ScopedStage prof_(kStPtf, st);
-    PtfDetIndex ix;
-    if (!ptf_det_index(n_fuse, P, (const long long*)fuse_pix, scratch, ix, st)) return FS_ERR_LAUNCH;
-    hipLaunchKernelGGL(ptf_gru_inputs_bwd_det_kernel, dim3((n_fuse + 15) / 16), dim3(256), 0, st, n_fuse,
-                       (const long long*)fuse_idx, (const long long*)fuse_pix, R, O, rho_i, om_i, dcat, g_G, g_R, g_O,
-                       g_lat_i, g_rho_i, g_om_i, ix);
-    hipLaunchKernelGGL(ptf_det_tie_sum_kernel<1>, dim3((unsigned)(((long long)n_fuse * 66 + 255) / 256)), dim3(256), 0, st, n_fuse,
-                       (const long long*)fuse_pix, ix, g_lat_i, (float*)nullptr, g_rho_i, g_om_i, (float*)nullptr);
-    FS_CHECK_LAUNCH("ptf_gru_inputs_bwd_det");
-    return FS_OK;
+    return gru_inputs_backward_impl(true, n_fuse, fuse_idx, fuse_pix, R, O, rho_i, om_i, dcat, g_G, g_R, g_O, g_lat_i, g_rho_i,
+                                    g_om_i, P, scratch, stream_);
 }

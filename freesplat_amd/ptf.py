@@ -1,6 +1,6 @@
 """Pixel-wise Triplet Fusion: drop-in for EncoderFreeSplat.fuse_gaussians.
 
-Mirrors /root/reference/src/model/encoder/encoder_freesplat.py:431-522 (same signature, same four
+Mirrors the reference's src/model/encoder/encoder_freesplat.py:431-522 (same signature, same four
 outputs in the same ORDER) together with the modules it needs: `GRU`
 (src/model/encoder/modules/networks.py:188-214, parameter names mlp_{z,r,n}.{0,2}.{weight,bias} and
 construction order kept so checkpoints and seeded inits carry over); the positional encodings
@@ -22,6 +22,7 @@ The fold is HIP in both modes (b = 1, the only shape the reference's indexing su
 from __future__ import annotations
 
 import ctypes as C
+import itertools
 import math
 import os
 import weakref
@@ -33,117 +34,55 @@ from . import _lib
 from .rasterizer import deterministic
 
 
-class _GruRows(torch.autograd.Function):
-    """The GRU on materialised rows [hid(64) | he(24) | x(64) | xe(24)]: fs_ptf_gru_forward, and for the backward
-    fs_ptf_gru_backward + fs_ptf_gru_weight_grads (gru_backward below).  What GRU.forward runs when the module is called on
-    its own; the fold uses the gathering variants of the same kernels."""
+# ---- constants, the GRU's parameters, the library call --------------------------------------------------------------
+GRU_PARAM_SHAPES = [(64, 176), (64,), (64, 64), (64,), (64, 176), (64,), (64, 64), (64,), (64, 152), (64,), (64, 64), (64,)]
 
-    @staticmethod
-    def forward(ctx, cat, gru, *params):
-        n = cat.shape[0]
-        tab = gru_tables(gru)
-        out = torch.empty(n, 64, device=cat.device)
-        if n:
-            _lib.check(_lib.lib().fs_ptf_gru_forward(n, _lib.ptr(cat), _lib.ptr(tab), _lib.ptr(out), _lib.current_stream()),
-                       "fs_ptf_gru_forward")
-        ctx.gru = gru
-        ctx.save_for_backward(cat)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        (cat,) = ctx.saved_tensors
-        gru = ctx.gru
-        dcat, grads = gru_backward(_gru_params(gru), gru_tables(gru), gru_operand_stream(gru), cat, g.float().contiguous())
-        return (dcat, None) + tuple(grads)
+# The fold's state is six arrays G, X, R, O, E, D (latent, position, density, weight, extrinsics, depth) with these floats per row.
+# In a flat buffer of `rows` rows the arrays lie one after the other: array k starts at float rows * _STATE_OFF[k].
+STATE_WIDTHS = (64, 3, 1, 1, 16, 1)
+_STATE_OFF = (0,) + tuple(itertools.accumulate(STATE_WIDTHS))
+STATE_FLOATS = _STATE_OFF[-1]                                     # 86 floats per row
+_RETURNED_FLOATS = sum(STATE_WIDTHS[k] for k in (0, 1, 4, 5))     # of G, X, E, D: what fuse_gaussians returns
+_Ptr6 = C.c_void_p * 6
 
 
-class GRU(nn.Module):
-    """networks.py:188-214: same constructor, parameter names and call signature.  `forward` runs on the HIP kernels (rows
-    through fs_ptf_gru_forward / fs_ptf_gru_backward on the fp32 matrix cores); there is no CPU path (the
-    reference-pinned restatement the tests compare against lives with the test infrastructure, not in this package)."""
-
-    def __init__(self, input_channel=64, hidden_channel=64, weights_dim=24):
-        super().__init__()
-        if (input_channel, hidden_channel, weights_dim) != (64, 64, 24):
-            raise ValueError("freesplat_amd GRU: the kernels are built for 64 / 64 / 24 channels (the reference's only use, "
-                             "encoder_freesplat.py:163)")
-        mk = lambda d: nn.Sequential(nn.Linear(d, hidden_channel), nn.ReLU(), nn.Linear(hidden_channel, hidden_channel))
-        self.mlp_z = mk(hidden_channel + input_channel + 2 * weights_dim)
-        self.mlp_r = mk(hidden_channel + input_channel + 2 * weights_dim)
-        self.mlp_n = mk(hidden_channel + input_channel + 1 * weights_dim)
-
-    def forward(self, input_feat, hidden_feat, input_weights_emb, hidden_weights_emb):
-        if input_feat.device.type != "cuda":
-            raise RuntimeError(f"freesplat_amd GRU: tensors must live on a HIP device (got {input_feat.device}); no CPU path")
-        if hidden_feat is None:
-            hidden_feat = torch.zeros_like(input_feat)
-        lead = input_feat.shape[:-1]
-        rows = [t.reshape(-1, t.shape[-1]).float() for t in (hidden_feat, hidden_weights_emb, input_feat, input_weights_emb)]
-        cat = torch.cat(rows, dim=-1).contiguous()                 # [n, 176] = [hid | he | x | xe]
-        return _GruRows.apply(cat, self, *_gru_params(self)).reshape(lead + (64,))
+def _state_arrays(rows: int, device=None, base: int = None):
+    """The six arrays of a state of `rows` rows: new tensors on `device`, or (base: the address of a flat buffer of
+    rows * STATE_FLOATS floats) the array of six pointers into that buffer, which the library takes."""
+    if base is None:
+        return tuple(torch.empty(rows, n, dtype=torch.float32, device=device) for n in STATE_WIDTHS)
+    return _Ptr6(*[base + 4 * rows * o for o in _STATE_OFF[:6]])
 
 
-def match_view(xyz: Tensor, w2c: Tensor, kpix: Tensor, depth_i: Tensor, h: int, w: int, depth_thres: float = 0.1):
-    """fs_ptf_match on device tensors: xyz [M,3], w2c [4,4], kpix [4], depth_i [h*w] -> ascending int64
-    index tensors (keep_idx, fuse_idx, fuse_pix, append_pix).  One host sync (the three counts)."""
-    if xyz.device.type != "cuda":
-        raise RuntimeError(f"freesplat_amd PTF: tensors must live on a HIP device (got {xyz.device}); no CPU path")
-    dev = xyz.device
-    M, P = xyz.shape[0], h * w
-    L = _lib.lib()
-    xyz = xyz.detach().float().contiguous()
-    scratch = torch.empty(L.fs_ptf_scratch_bytes(M, h, w), dtype=torch.uint8, device=dev)
-    keep = torch.empty(max(M, 1), dtype=torch.int64, device=dev)
-    fuse = torch.empty(max(M, 1), dtype=torch.int64, device=dev)
-    fpix = torch.empty(max(M, 1), dtype=torch.int64, device=dev)
-    app = torch.empty(P, dtype=torch.int64, device=dev)
-    counts = torch.empty(4, dtype=torch.int32, device=dev)
-    p = _lib.ptr
-    w2c_, kpix_, depth_ = (t.detach().float().contiguous() for t in (w2c, kpix, depth_i))  # alive until the launch is queued
-    _lib.check(L.fs_ptf_match(M, h, w, p(xyz), p(w2c_), p(kpix_), p(depth_),
-                              C.c_float(depth_thres), p(scratch), p(keep), p(fuse), p(fpix), p(app), p(counts),
-                              _lib.current_stream()), "fs_ptf_match")
-    nk, nf, na, _ = counts.tolist()
-    return keep[:nk], fuse[:nf], fpix[:nf], app[:na]
+def _gru_params(gru: "GRU") -> list:
+    """[mlp_r[0].weight, .bias, mlp_r[2].weight, .bias, mlp_z .., mlp_n ..] -- through the modules' dicts: as attribute
+    chains (gru.mlp_r[0].weight: Module.__getattr__ + Sequential.__getitem__) the twelve look-ups cost 24 us of a 2-view
+    call that is host-bound."""
+    out = []
+    for name in ("mlp_r", "mlp_z", "mlp_n"):
+        layers = gru._modules[name]._modules
+        for k in ("0", "2"):
+            pr = layers[k]._parameters
+            out.append(pr["weight"])
+            out.append(pr["bias"])
+    return out
 
 
-# operand tables per GRU module, valid while the parameters keep their storage and version; weak keys: a table must not
-# outlive its module (a new module may get the same id(), the same parameter addresses and the same version counters)
-_KEEP_BYTES_ENV = os.environ.get("FREESPLAT_PTF_KEEP_BYTES")   # see _PtfFold.forward
+def _call(name: str, *args) -> None:
+    """The library's `name` on the current stream (its last argument), checked."""
+    _lib.check(getattr(_lib.lib(), name)(*args, _lib.current_stream()), name)
 
 
-def _keep_bytes(device) -> int:
-    """How many bytes of worst-case fold state a training fold may keep untrimmed until its backward: FREESPLAT_PTF_KEEP_BYTES if
-    set, else 1/16 of the memory currently free on the device, capped at 8 GiB (18 GB on an idle MI355X -> 8 GiB; a card with
-    16 GB free keeps 1 GB and trims above it -- ADVICE r5: a fixed 8 GiB could run smaller devices out of memory)."""
-    if _KEEP_BYTES_ENV is not None:
-        return int(_KEEP_BYTES_ENV)
-    try:
-        free, _total = torch.cuda.mem_get_info(device)
-    except Exception:
-        return 1 << 30
-    return int(min(8 << 30, free // 16))
-_table_cache: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
-LAST_FOLD_COUNTS = None   # device tensor [V,4] (kept, fused, appended, state rows) of the last fused fold: bench accounting
+def _call_backward(name: str, args: tuple, P: int, det_scratch) -> None:
+    """`name`, or with a scratch (the deterministic mode) `name`_det, which takes the view's pixel count and that scratch too:
+    tied fused rows then add into the view's pixels in row order."""
+    if det_scratch is None:
+        _call(name, *args)
+    else:
+        _call(name + "_det", *args, P, _lib.ptr(det_scratch))
 
 
-def gru_tables(gru: "GRU") -> Tensor:
-    """The GRU's weights and biases as MFMA operands of csrc/ptf_gru.hip:ptf_gru16_kernel (fs_ptf_gru_table_layout() = 1): the
-    forward's operand rows of _gru_stream16_index, then the six bias vectors.  Cached per parameter version."""
-    params = _gru_params(gru)
-    key = tuple((q.data_ptr(), q._version) for q in params)
-    hit = _table_cache.get(gru)
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    assert _lib.lib().fs_ptf_gru_table_layout() == 1
-    tab = _gru_operand_stream16(gru, forward_only=True)
-    assert tab.shape[0] == _lib.lib().fs_ptf_gru_table_rows()
-    _table_cache[gru] = (key, tab)
-    return tab
-
-
-_stream_cache: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
+# ---- the GRU and its operands ------------------------------------------------------------------------------------------
 _stream16_index_cache: dict = {}
 
 
@@ -204,6 +143,7 @@ def _gru_stream16_index(forward_only: bool, transposed_only: bool = False) -> "n
         for s in range(16):
             rows += [tr(R1, ob, s) for ob in range(11)] + [tr(Z1, ob, s) for ob in range(11)]
         assert len(rows) == 1400
+    assert _lib.lib().fs_ptf_gru_table_layout() == 1 and _lib.lib().fs_ptf_gru_stream_layout() == 2
     c = _lib.lib().fs_ptf_gru_stream_chunk_rows()
     n_rows = (_lib.lib().fs_ptf_gru_table_rows() if forward_only else _lib.lib().fs_ptf_gru_stream_rows()) - 6
     if transposed_only:
@@ -233,60 +173,37 @@ def _gru_operand_stream16(gru: "GRU", forward_only: bool = False, transposed_onl
         return flat[idx]
 
 
+# operands per GRU module, valid while the parameters keep their storage and version; weak keys: an entry must not outlive its
+# module (a new module may get the same id(), the same parameter addresses and the same version counters)
+_operand_cache: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
+
+
+def _operand(gru: "GRU", form: str, **which) -> Tensor:
+    """Form `form` of the module's cached operands: _gru_operand_stream16(gru, **which), built on first request."""
+    key = tuple((q.data_ptr(), q._version) for q in _gru_params(gru))
+    ops = _operand_cache.get(gru)
+    if ops is None or ops["key"] != key:
+        ops = _operand_cache[gru] = {"key": key}
+    if form not in ops:
+        ops[form] = _gru_operand_stream16(gru, **which)
+    return ops[form]
+
+
+def gru_tables(gru: "GRU") -> Tensor:
+    """The GRU's weights and biases as MFMA operands of csrc/ptf_gru.hip:ptf_gru16_kernel (fs_ptf_gru_table_layout() = 1): the
+    forward's operand rows of _gru_stream16_index, then the six bias vectors.  Cached per parameter version, as the two below."""
+    return _operand(gru, "tables", forward_only=True)
+
+
 def gru_operand_stream(gru: "GRU") -> Tensor:
     """The operand stream of csrc/ptf_gru.hip:ptf_gru_bwd16_kernel (fs_ptf_gru_stream_layout() = 2), built from the parameters:
     the 696 rows of the forward (re-run), then the transposed layers' rows, then the six bias vectors."""
-    assert _lib.lib().fs_ptf_gru_stream_layout() == 2
-    tab = gru_tables(gru)                                   # (cached per parameter version: a new table = new parameters)
-    hit = _stream_cache.get(gru)
-    if hit is not None and hit[0] is tab:
-        return hit[1]
-    stream = _gru_operand_stream16(gru)
-    _stream_cache[gru] = (tab, stream)
-    return stream
-
-
-_stream_t_cache: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
-
-
-def save_gru_activations(V: int = 2, P: int = 0, device=None) -> bool:
-    """Training folds keep the GRU's hidden activations, gates and gathered input rows (fs_ptf_fold_step_save) so that the
-    backward runs the transposed layers only (fs_ptf_gru_backward_saved: 704 instead of 1 400 MFMAs per 16 pairs) -- 4 KB per
-    possible fused pair and step held until the backward: (V - 1) * P * 4 KB, 10 GB for config 3's three views at 968x1296.
-    FREESPLAT_GRU_SAVE=1 / 0 forces it on / off (A/B); otherwise it is on when that fits a quarter of the memory currently free
-    on the device (a 288 GB MI355X: always; a small card falls back to the re-running backward instead of running out of memory).
-    In the deterministic mode (rasterizer.deterministic()) it is a quarter of the device's TOTAL memory instead: the two GRU
-    backwards round differently, so the choice must not follow the memory that happens to be free."""
-    e = os.environ.get("FREESPLAT_GRU_SAVE")
-    if e is not None:
-        return e != "0"
-    if P <= 0 or device is None:
-        return True
-    need = (V - 1) * P * 4 * (_lib.lib().fs_ptf_gru_side_cols() + _lib.lib().fs_ptf_gru_act_cols() + 176)
-    if deterministic():
-        # (the two GRU backwards round differently: in the deterministic mode the choice must not follow the memory that happens
-        #  to be free, so it follows the device's total memory)
-        return need <= torch.cuda.get_device_properties(device).total_memory // 4
-    try:
-        free, _total = torch.cuda.mem_get_info(device)
-    except Exception:
-        return False
-    return need <= free // 4
+    return _operand(gru, "stream")
 
 
 def gru_operand_stream_t(gru: "GRU") -> Tensor:
     """The transposed layers' operand rows alone (fs_ptf_gru_stream_t_rows() rows): the stream of fs_ptf_gru_backward_saved."""
-    tab = gru_tables(gru)                                   # (cached per parameter version: a new table = new parameters)
-    hit = _stream_t_cache.get(gru)
-    if hit is not None and hit[0] is tab:
-        return hit[1]
-    stream = _gru_operand_stream16(gru, transposed_only=True)
-    assert stream.shape[0] == _lib.lib().fs_ptf_gru_stream_t_rows()
-    _stream_t_cache[gru] = (tab, stream)
-    return stream
-
-
-GRU_PARAM_SHAPES = [(64, 176), (64,), (64, 64), (64,), (64, 176), (64,), (64, 64), (64,), (64, 152), (64,), (64, 64), (64,)]
+    return _operand(gru, "stream_t", transposed_only=True)
 
 
 def gru_grad_views(flat: Tensor) -> list:
@@ -317,22 +234,134 @@ def gru_backward(params: list, tables: Tensor, operand_stream: Tensor, cat: Tens
         grads = torch.zeros(L.fs_ptf_gru_grad_floats(), dtype=torch.float32, device=dev)
     dcat = torch.empty(n, 176, dtype=torch.float32, device=dev)
     g_fused = g_fused.contiguous()
-    st = _lib.current_stream()
     if saved is not None:
         side, act, stream_t = saved
-        _lib.check(L.fs_ptf_gru_backward_saved(n, p(cat), p(stream_t), p(act), p(g_fused), p(dcat), p(side), st),
-                   "fs_ptf_gru_backward_saved")
+        _call("fs_ptf_gru_backward_saved", n, p(cat), p(stream_t), p(act), p(g_fused), p(dcat), p(side))
     else:
         side = torch.empty(n, L.fs_ptf_gru_side_cols(), dtype=torch.float32, device=dev)
-        _lib.check(L.fs_ptf_gru_backward(n, p(cat), p(tables), p(operand_stream), p(g_fused), p(dcat), p(side), st),
-                   "fs_ptf_gru_backward")
+        _call("fs_ptf_gru_backward", n, p(cat), p(tables), p(operand_stream), p(g_fused), p(dcat), p(side))
     ws = torch.empty(L.fs_ptf_gru_weight_grads_bytes(n), dtype=torch.uint8, device=dev)
-    _lib.check(L.fs_ptf_gru_weight_grads(n, p(cat), p(side), p(grads), p(ws), st), "fs_ptf_gru_weight_grads")
+    _call("fs_ptf_gru_weight_grads", n, p(cat), p(side), p(grads), p(ws))
     return dcat, gru_grad_views(grads)
 
 
+class _GruRows(torch.autograd.Function):
+    """The GRU on materialised rows [hid(64) | he(24) | x(64) | xe(24)]: fs_ptf_gru_forward, and for the backward
+    fs_ptf_gru_backward + fs_ptf_gru_weight_grads (gru_backward).  What GRU.forward runs when the module is called on
+    its own; the fold uses the gathering variants of the same kernels."""
+
+    @staticmethod
+    def forward(ctx, cat, gru, *params):
+        n = cat.shape[0]
+        tab = gru_tables(gru)
+        out = torch.empty(n, 64, device=cat.device)
+        if n:
+            _call("fs_ptf_gru_forward", n, _lib.ptr(cat), _lib.ptr(tab), _lib.ptr(out))
+        ctx.gru = gru
+        ctx.save_for_backward(cat)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (cat,) = ctx.saved_tensors
+        gru = ctx.gru
+        dcat, grads = gru_backward(_gru_params(gru), gru_tables(gru), gru_operand_stream(gru), cat, g.float().contiguous())
+        return (dcat, None) + tuple(grads)
+
+
+class GRU(nn.Module):
+    """networks.py:188-214: same constructor, parameter names and call signature.  `forward` runs on the HIP kernels (rows
+    through fs_ptf_gru_forward / fs_ptf_gru_backward on the fp32 matrix cores); there is no CPU path (the
+    reference-pinned restatement the tests compare against lives with the test infrastructure, not in this package)."""
+
+    def __init__(self, input_channel=64, hidden_channel=64, weights_dim=24):
+        super().__init__()
+        if (input_channel, hidden_channel, weights_dim) != (64, 64, 24):
+            raise ValueError("freesplat_amd GRU: the kernels are built for 64 / 64 / 24 channels (the reference's only use, "
+                             "encoder_freesplat.py:163)")
+        mk = lambda d: nn.Sequential(nn.Linear(d, hidden_channel), nn.ReLU(), nn.Linear(hidden_channel, hidden_channel))
+        self.mlp_z = mk(hidden_channel + input_channel + 2 * weights_dim)
+        self.mlp_r = mk(hidden_channel + input_channel + 2 * weights_dim)
+        self.mlp_n = mk(hidden_channel + input_channel + 1 * weights_dim)
+
+    def forward(self, input_feat, hidden_feat, input_weights_emb, hidden_weights_emb):
+        if input_feat.device.type != "cuda":
+            raise RuntimeError(f"freesplat_amd GRU: tensors must live on a HIP device (got {input_feat.device}); no CPU path")
+        if hidden_feat is None:
+            hidden_feat = torch.zeros_like(input_feat)
+        lead = input_feat.shape[:-1]
+        rows = [t.reshape(-1, t.shape[-1]).float() for t in (hidden_feat, hidden_weights_emb, input_feat, input_weights_emb)]
+        cat = torch.cat(rows, dim=-1).contiguous()                 # [n, 176] = [hid | he | x | xe]
+        return _GruRows.apply(cat, self, *_gru_params(self)).reshape(lead + (64,))
+
+
+# ---- memory policy of a training fold ----------------------------------------------------------------------------------
+_KEEP_BYTES_ENV = os.environ.get("FREESPLAT_PTF_KEEP_BYTES")
+
+
+def _keep_bytes(device) -> int:
+    """How many bytes of worst-case fold state a training fold may keep untrimmed until its backward (_PtfFold.forward):
+    FREESPLAT_PTF_KEEP_BYTES if set, else 1/16 of the memory currently free on the device, capped at 8 GiB (18 GB on an idle
+    MI355X -> 8 GiB; a card with 16 GB free keeps 1 GB and trims above it -- ADVICE r5: a fixed 8 GiB could run smaller devices
+    out of memory)."""
+    if _KEEP_BYTES_ENV is not None:
+        return int(_KEEP_BYTES_ENV)
+    try:
+        free, _total = torch.cuda.mem_get_info(device)
+    except Exception:
+        return 1 << 30
+    return int(min(8 << 30, free // 16))
+
+
+def save_gru_activations(V: int = 2, P: int = 0, device=None) -> bool:
+    """Training folds keep the GRU's hidden activations, gates and gathered input rows (fs_ptf_fold_step_save) so that the
+    backward runs the transposed layers only (fs_ptf_gru_backward_saved: 704 instead of 1 400 MFMAs per 16 pairs) -- 4 KB per
+    possible fused pair and step held until the backward: (V - 1) * P * 4 KB, 10 GB for config 3's three views at 968x1296.
+    FREESPLAT_GRU_SAVE=1 / 0 forces it on / off (A/B); otherwise it is on when that fits a quarter of the memory currently free
+    on the device (a 288 GB MI355X: always; a small card falls back to the re-running backward instead of running out of memory).
+    In the deterministic mode (rasterizer.deterministic()) it is a quarter of the device's TOTAL memory instead: the two GRU
+    backwards round differently, so the choice must not follow the memory that happens to be free."""
+    e = os.environ.get("FREESPLAT_GRU_SAVE")
+    if e is not None:
+        return e != "0"
+    if P <= 0 or device is None:
+        return True
+    need = (V - 1) * P * 4 * (_lib.lib().fs_ptf_gru_side_cols() + _lib.lib().fs_ptf_gru_act_cols() + 176)
+    if deterministic():
+        return need <= torch.cuda.get_device_properties(device).total_memory // 4
+    try:
+        free, _total = torch.cuda.mem_get_info(device)
+    except Exception:
+        return False
+    return need <= free // 4
+
+
+# ---- the fold's pieces and its inference path ----------------------------------------------------------------------------
+LAST_FOLD_COUNTS = None   # device tensor [V,4] (kept, fused, appended, state rows) of the last fused fold: bench accounting
 _fold_scratch: dict = {}       # (device, stream, V, h, w) -> the inference fold's internal scratch (reuse is ordered by the
                                # stream; two folds in flight on different streams must not share it; at most 8 shapes are kept)
+
+
+def match_view(xyz: Tensor, w2c: Tensor, kpix: Tensor, depth_i: Tensor, h: int, w: int, depth_thres: float = 0.1):
+    """fs_ptf_match on device tensors: xyz [M,3], w2c [4,4], kpix [4], depth_i [h*w] -> ascending int64
+    index tensors (keep_idx, fuse_idx, fuse_pix, append_pix).  One host sync (the three counts)."""
+    if xyz.device.type != "cuda":
+        raise RuntimeError(f"freesplat_amd PTF: tensors must live on a HIP device (got {xyz.device}); no CPU path")
+    dev = xyz.device
+    M, P = xyz.shape[0], h * w
+    xyz = xyz.detach().float().contiguous()
+    scratch = torch.empty(_lib.lib().fs_ptf_scratch_bytes(M, h, w), dtype=torch.uint8, device=dev)
+    keep = torch.empty(max(M, 1), dtype=torch.int64, device=dev)
+    fuse = torch.empty(max(M, 1), dtype=torch.int64, device=dev)
+    fpix = torch.empty(max(M, 1), dtype=torch.int64, device=dev)
+    app = torch.empty(P, dtype=torch.int64, device=dev)
+    counts = torch.empty(4, dtype=torch.int32, device=dev)
+    p = _lib.ptr
+    w2c_, kpix_, depth_ = (t.detach().float().contiguous() for t in (w2c, kpix, depth_i))  # alive until the launch is queued
+    _call("fs_ptf_match", M, h, w, p(xyz), p(w2c_), p(kpix_), p(depth_), C.c_float(depth_thres), p(scratch), p(keep), p(fuse),
+          p(fpix), p(app), p(counts))
+    nk, nf, na, _ = counts.tolist()
+    return keep[:nk], fuse[:nf], fpix[:nf], app[:na]
 
 
 def world_to_camera(Es: Tensor) -> Tensor:
@@ -345,7 +374,7 @@ def world_to_camera(Es: Tensor) -> Tensor:
     V = Es.shape[0]
     src = Es.reshape(V, 16).contiguous()
     out = torch.empty_like(src)
-    _lib.check(_lib.lib().fs_invert_4x4(V, _lib.ptr(src), _lib.ptr(out), _lib.current_stream()), "fs_invert_4x4")
+    _call("fs_invert_4x4", V, _lib.ptr(src), _lib.ptr(out))
     return out
 
 
@@ -397,17 +426,10 @@ def _fuse_gaussians_fused(gru, gaussians, coords, densities, weight_emb, depths,
     # arithmetic for the call -- the tensor views of the final state are made AFTER the launches, while the GPU works --
     # and the fold's internal scratch is kept per (device, stream, V, h, w): it is dead when the call returns (the count
     # read-back below waits for the fold).
-    widths = (64, 3, 1, 1, 16, 1)
     n_sets = 1 if V == 2 else 2
-    big = torch.empty(n_sets * rows * 86, device=dev)
+    big = torch.empty(n_sets * rows * STATE_FLOATS, device=dev)
     base = big.data_ptr()
-    ptrs = []
-    for k in range(n_sets):
-        arr, off = (C.c_void_p * 6)(), k * rows * 86
-        for q, n_ in enumerate(widths):
-            arr[q] = base + 4 * off
-            off += rows * n_
-        ptrs.append(arr)
+    ptrs = [_state_arrays(rows, base=base + 4 * k * rows * STATE_FLOATS) for k in range(n_sets)]
     counts = torch.empty(V, 4, dtype=torch.int32, device=dev)
     stream = torch.cuda.current_stream(dev).cuda_stream
     key = (dev, stream, V, h, w)
@@ -422,27 +444,14 @@ def _fuse_gaussians_fused(gru, gaussians, coords, densities, weight_emb, depths,
     global LAST_FOLD_COUNTS
     LAST_FOLD_COUNTS = counts
     last = counts[V - 1, 3]
-    off = 0 if ((V - 1) & 1 or V == 2) else rows * 86        # the set that holds the final state
-    G = big[off: off + rows * 64].view(rows, 64)
-    X = big[off + rows * 64: off + rows * 67].view(rows, 3)
-    E = big[off + rows * 69: off + rows * 85].view(rows, 4, 4)
-    D = big[off + rows * 85: off + rows * 86]
+    off = 0 if ((V - 1) & 1 or V == 2) else rows * STATE_FLOATS        # the set that holds the final state
+    oG, oX, oR, _, oE, oD, end = [off + rows * o for o in _STATE_OFF]
+    G = big[oG: oX].view(rows, -1)
+    X = big[oX: oR].view(rows, -1)
+    E = big[oE: oD].view(rows, 4, 4)
+    D = big[oD: end]
     n = int(last.item())                           # the only host sync of the fold
     return G[None, :n], X[None, :n], E[None, :n], D[None, :n]
-
-
-def _gru_params(gru: "GRU") -> list:
-    """[mlp_r[0].weight, .bias, mlp_r[2].weight, .bias, mlp_z .., mlp_n ..] -- through the modules' dicts: as attribute
-    chains (gru.mlp_r[0].weight: Module.__getattr__ + Sequential.__getitem__) the twelve look-ups cost 24 us of a 2-view
-    call that is host-bound."""
-    out = []
-    for name in ("mlp_r", "mlp_z", "mlp_n"):
-        layers = gru._modules[name]._modules
-        for k in ("0", "2"):
-            pr = layers[k]._parameters
-            out.append(pr["weight"])
-            out.append(pr["bias"])
-    return out
 
 
 class _PtfFold(torch.autograd.Function):
@@ -459,14 +468,13 @@ class _PtfFold(torch.autograd.Function):
         w2c = world_to_camera(Es)
         kpix = torch.empty(V, 4, dtype=torch.float32, device=dev)
         E0 = torch.empty(P, 16, dtype=torch.float32, device=dev)
-        _lib.check(L.fs_ptf_cameras(V, h, w, p(Es), p(Kn), p(kpix), p(E0), _lib.current_stream()), "fs_ptf_cameras")
+        _call("fs_ptf_cameras", V, h, w, p(Es), p(Kn), p(kpix), p(E0))
         counts = torch.empty(V, 4, dtype=torch.int32, device=dev)
         state = (lat[0], xs[0], rho[0], om[0], E0, dep[0])         # G, X, R, O, E, D of the state after view 0
         states, scratches, saves = [state], [None], [None]
         for i in range(1, V):
             M_max = i * P
-            rows = M_max + P
-            out = tuple(torch.empty(rows, n, device=dev) for n in (64, 3, 1, 1, 16, 1))
+            out = _state_arrays(M_max + P, dev)
             scratch = torch.empty(L.fs_ptf_fold_scratch_bytes(M_max, h, w), dtype=torch.uint8, device=dev)
             G, X, R, O, E, D = state
             args = (M_max, None if i == 1 else p(counts[i - 1, 3:]), h, w, p(G), p(X), p(R), p(O), p(E), p(D),
@@ -479,10 +487,10 @@ class _PtfFold(torch.autograd.Function):
                 side = torch.empty(nf_max, L.fs_ptf_gru_side_cols(), dtype=torch.float32, device=dev)
                 act = torch.empty(-(-nf_max // 16) * 16, L.fs_ptf_gru_act_cols(), dtype=torch.float32, device=dev)   # (whole 16-pair groups)
                 cat = torch.empty(nf_max, 176, dtype=torch.float32, device=dev)
-                _lib.check(L.fs_ptf_fold_step_save(*args, p(side), p(act), p(cat), _lib.current_stream()), "fs_ptf_fold_step_save")
+                _call("fs_ptf_fold_step_save", *args, p(side), p(act), p(cat))
                 saves.append((side, act, cat))
             else:
-                _lib.check(L.fs_ptf_fold_step(*args, _lib.current_stream()), "fs_ptf_fold_step")
+                _call("fs_ptf_fold_step", *args)
                 saves.append(None)
             state = out
             states.append(out)
@@ -492,20 +500,20 @@ class _PtfFold(torch.autograd.Function):
         cnt = counts.tolist()                          # the only host sync of the fold
         cnt[0] = [P, 0, 0, P]
         n = cnt[V - 1][3]
-        # The steps were queued into WORST-CASE buffers ((i + 1) P rows of 86 floats each: O(V^2 P) in total, 2.4 GB at
-        # V = 8 and 384x512) because their sizes were still on the device.  Now that the counts are known, keep only the
-        # rows that exist (one copy of sum_i n_i rows, ~0.3 ms at 10 views): what the backward holds on to is O(V n).
-        # The LAST state is only returned (the backward reads states 0 .. V-2): its G, X, E, D stay views of the worst-case
-        # buffer unless that would pin more than 256 MB of rows that do not exist.
-        # ... unless the worst-case buffers are small next to the device's memory (_keep_bytes: FREESPLAT_PTF_KEEP_BYTES, default 1/16 of the free device memory up to 8 GiB: config 3's
-        # three views at 968x1296 queue 2.2 GB): then nothing is copied -- the trims were 0.8 ms of rocclr copies per config-3
-        # training step (profiles/r5_c3_step_glue.json) for memory a 288 GB device does not miss.
-        worst = sum((i + 1) * P for i in range(1, V)) * 86 * 4
+        # The steps were queued into WORST-CASE buffers ((i + 1) P rows of STATE_FLOATS floats each: O(V^2 P) in total, 2.4 GB
+        # at V = 8 and 384x512) because their sizes were still on the device.  Where those buffers are small next to the
+        # device's memory (_keep_bytes; config 3's three views at 968x1296 queue 2.2 GB) nothing is copied: trimming them was
+        # 0.8 ms of rocclr copies per config-3 training step (profiles/r5_c3_step_glue.json) for memory a 288 GB device does
+        # not miss.  Otherwise, now that the counts are known, only the rows that exist are kept (one copy of sum_i n_i rows,
+        # ~0.3 ms at 10 views): what the backward holds on to is O(V n).  The LAST state is only returned (the backward reads
+        # states 0 .. V-2): its G, X, E, D stay views of the worst-case buffer unless that would pin more than 256 MB of rows
+        # that do not exist.
+        worst = sum((i + 1) * P for i in range(1, V)) * STATE_FLOATS * 4
         trim = worst > _keep_bytes(lat.device)
         for i in range(1, V - 1):
             states[i] = tuple((t[: cnt[i][3]].clone() if trim else t[: cnt[i][3]]) for t in states[i])
         G, X, R, O, E, D = states[V - 1]
-        if trim and (V * P - n) * 84 * 4 > (256 << 20):
+        if trim and (V * P - n) * _RETURNED_FLOATS * 4 > (256 << 20):
             G, X, E, D = (t[:n].clone() for t in (G, X, E, D))
         states[V - 1] = None
         ctx.cnt, ctx.hw, ctx.states, ctx.scratches = cnt, (h, w), states, scratches
@@ -533,10 +541,10 @@ class _PtfFold(torch.autograd.Function):
         # gradient of the current out state: G, X, R, O, E, D (None = zero)
         c = lambda t: None if t is None else t.contiguous()
         g_out = [c(gG), c(gX), None, None, c(gE), None if gD is None else gD.contiguous().view(n, 1)]
-        vp = lambda ts: (C.c_void_p * 6)(*[None if t is None else t.data_ptr() for t in ts])
+        vp = lambda ts: _Ptr6(*[None if t is None else t.data_ptr() for t in ts])
         det_scratch = None
         if deterministic():
-            # tied fused rows add into the view's pixels in row order (fs_ptf_*_backward_det): one scratch for every step
+            # one scratch of the deterministic backward for every step
             nf_max = max(cnt[i][1] for i in range(1, V))
             det_scratch = torch.empty(max(L.fs_ptf_backward_det_bytes(nf_max, P), 1), dtype=torch.uint8, device=dev)
         for i in range(V - 1, 0, -1):
@@ -550,16 +558,12 @@ class _PtfFold(torch.autograd.Function):
                 # the state before view 1 IS view 0 (every row of it kept or fused): its gradient is written straight
                 # into view 0's slices (the extrinsics' gradient goes nowhere)
                 g_in = [g_lat[0], g_xs[0], g_rho[0].view(P, 1), g_om[0].view(P, 1),
-                        torch.empty(M_in, 16, dtype=torch.float32, device=dev), g_dep[0].view(P, 1)]
+                        torch.empty(M_in, STATE_WIDTHS[4], dtype=torch.float32, device=dev), g_dep[0].view(P, 1)]
             else:
-                g_in = [torch.empty(M_in, k, dtype=torch.float32, device=dev) for k in (64, 3, 1, 1, 16, 1)]
-            ws_args = (nk, nf, na, keep, fuse, fpix, app, p(X), p(R), p(E), p(D), p(xs[i]), p(rho[i]), p(dep[i]), p(Es[i]),
-                       vp(g_out), vp(g_in), p(g_lat[i]), p(g_xs[i]), p(g_rho[i]), p(g_om[i]), p(g_dep[i]))
-            if det_scratch is not None:
-                _lib.check(L.fs_ptf_write_state_backward_det(*ws_args, P, p(det_scratch), _lib.current_stream()),
-                           "fs_ptf_write_state_backward_det")
-            else:
-                _lib.check(L.fs_ptf_write_state_backward(*ws_args, _lib.current_stream()), "fs_ptf_write_state_backward")
+                g_in = list(_state_arrays(M_in, dev))
+            _call_backward("fs_ptf_write_state_backward",
+                           (nk, nf, na, keep, fuse, fpix, app, p(X), p(R), p(E), p(D), p(xs[i]), p(rho[i]), p(dep[i]), p(Es[i]),
+                            vp(g_out), vp(g_in), p(g_lat[i]), p(g_xs[i]), p(g_rho[i]), p(g_om[i]), p(g_dep[i])), P, det_scratch)
             if nf > 0:
                 # the GRU rows: re-gather their inputs (HIP), GRU backward on the matrix cores (+ the weight-gradient GEMMs)
                 sv = ctx.saves[i]
@@ -567,21 +571,16 @@ class _PtfFold(torch.autograd.Function):
                     cat = sv[2][:nf]                       # (the forward kept the gathered + encoded rows)
                 else:
                     cat = torch.empty(nf, 176, dtype=torch.float32, device=dev)
-                    _lib.check(L.fs_ptf_gru_inputs(nf, fuse, fpix, p(G), p(R), p(O), p(lat[i]), p(rho[i]), p(om[i]), p(cat),
-                                                   _lib.current_stream()), "fs_ptf_gru_inputs")
+                    _call("fs_ptf_gru_inputs", nf, fuse, fpix, p(G), p(R), p(O), p(lat[i]), p(rho[i]), p(om[i]), p(cat))
                 g_fused = g_out[0][nk: nk + nf] if g_out[0] is not None else z(nf, 64)
                 if g_flat is None:
                     g_flat = z(L.fs_ptf_gru_grad_floats())
                 dcat, g_params = gru_backward(params, ctx.tables, ctx.operand_stream, cat, g_fused, g_flat,
                                               saved=None if sv is None else (sv[0], sv[1], ctx.stream_t))
                 ctx.saves[i] = None
-                gi_args = (nf, fuse, fpix, p(R), p(O), p(rho[i]), p(om[i]), p(dcat), p(g_in[0]), p(g_in[2]), p(g_in[3]),
-                           p(g_lat[i]), p(g_rho[i]), p(g_om[i]))
-                if det_scratch is not None:
-                    _lib.check(L.fs_ptf_gru_inputs_backward_det(*gi_args, P, p(det_scratch), _lib.current_stream()),
-                               "fs_ptf_gru_inputs_backward_det")
-                else:
-                    _lib.check(L.fs_ptf_gru_inputs_backward(*gi_args, _lib.current_stream()), "fs_ptf_gru_inputs_backward")
+                _call_backward("fs_ptf_gru_inputs_backward",
+                               (nf, fuse, fpix, p(R), p(O), p(rho[i]), p(om[i]), p(dcat), p(g_in[0]), p(g_in[2]), p(g_in[3]),
+                                p(g_lat[i]), p(g_rho[i]), p(g_om[i])), P, det_scratch)
             g_out = g_in
         need = ctx.needs_input_grad
         pick = lambda k, t: t if need[k] else None
@@ -594,12 +593,11 @@ def _fuse_gaussians_train(gru, gaussians, coords, densities, weight_emb, depths,
     """Training path (autograd): the same HIP fold as inference, with a HIP backward (_PtfFold)."""
     h, w = image_shape
     V = gaussians[0].shape[1]
-    f32 = _f32c
     P = h * w
     lat, xs, rho, om, dep, Es = _fold_inputs(gaussians, coords, densities, weight_emb, depths, extrinsics, V, P, detach=False)
     if V == 1:
         return lat[:1], xs[:1], Es[0].reshape(1, 1, 4, 4).repeat(1, P, 1, 1), dep[:1]
-    Kn = f32(intrinsics[0].detach()).reshape(V, 9)
+    Kn = _f32c(intrinsics[0].detach()).reshape(V, 9)
     G, X, E, D = _PtfFold.apply(lat, xs, rho, om, dep, Es, Kn, h, w, float(depth_thres), gru_tables(gru),
                                 gru_operand_stream(gru), gru_operand_stream_t(gru) if save_gru_activations(V, P, lat.device) else None,
                                 *_gru_params(gru))

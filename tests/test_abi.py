@@ -172,6 +172,114 @@ def test_cost_volume_rejects_maps_of_4GB_and_more(monkeypatch):
     assert L.fs_cost_volume_backward_workspace_bytes_for(2, 2, 48, 8, 8, 8, 1) == 147712
 
 
+# (entry point, {argument index: value}, pointer arguments set to NULL, expected status).  Every other int32 argument is 1, every
+# other pointer a non-NULL dummy, the two `float* const*` arguments (A6) a host array of six dummies; A5 is such an array with
+# its last entry NULL.  The third column is a tuple of argument indices, each NULLed IN TURN (one call per index), "all"
+# (every pointer not named in the second column, at once) or None (one call).  Only combinations that return before the first
+# launch are listed: a dummy pointer is never dereferenced.
+A5, A6 = "five dummies + NULL", "six dummies"
+PTF_STATUS_TABLE = [
+    # M, h, w, xyz, w2c, kpix, depth_i, thres, scratch, keep, fuse, fpix, app, counts
+    ("fs_ptf_match", {0: -1}, None, -1), ("fs_ptf_match", {1: 0}, None, -1), ("fs_ptf_match", {1: -1}, None, -1),
+    ("fs_ptf_match", {2: 0}, None, -1), ("fs_ptf_match", {2: -1}, None, -1),
+    ("fs_ptf_match", {}, (3, 4, 5, 6, 8, 9, 10, 11, 12, 13), -1),
+    ("fs_ptf_match", {0: 0}, (4, 5, 6, 8, 12, 13), -1),              # (no state rows: xyz and the three state lists may be NULL)
+    # n_fuse, fuse_idx, fuse_pix, G, R, O, g_i, rho_i, om_i, cat
+    ("fs_ptf_gru_inputs", {0: -1}, None, -1), ("fs_ptf_gru_inputs", {0: 0}, None, 0), ("fs_ptf_gru_inputs", {0: 0}, "all", 0),
+    ("fs_ptf_gru_inputs", {}, tuple(range(1, 10)), -1),
+    # n_keep, n_fuse, n_app, keep, fuse, fpix, app, G X R O E D (7-12), g_i x_i rho_i om_i d_i E_i (13-18), fused, out (20-25)
+    ("fs_ptf_write_state", {0: -1}, None, -1), ("fs_ptf_write_state", {1: -1}, None, -1), ("fs_ptf_write_state", {2: -1}, None, -1),
+    ("fs_ptf_write_state", {0: 0, 1: 0, 2: 0}, None, 0), ("fs_ptf_write_state", {0: 0, 1: 0, 2: 0}, "all", 0),
+    ("fs_ptf_write_state", {}, (4, 5) + tuple(range(7, 26)), -1),
+    ("fs_ptf_write_state", {0: 0, 1: 0}, tuple(range(13, 19)) + tuple(range(20, 26)), -1),
+    ("fs_ptf_write_state", {1: 0, 2: 0}, tuple(range(7, 13)), -1), ("fs_ptf_write_state", {0: 0, 2: 0}, tuple(range(7, 13)), -1),
+    # M_max, M_dev, h, w, state (4-9), view (10-15), w2c, kpix, thres, tables, scratch, out (21-26), counts[, side, act, cat]
+    ("fs_ptf_fold_step", {0: 0}, None, -1), ("fs_ptf_fold_step", {0: -1}, None, -1), ("fs_ptf_fold_step", {2: 0}, None, -1),
+    ("fs_ptf_fold_step", {2: -1}, None, -1), ("fs_ptf_fold_step", {3: 0}, None, -1), ("fs_ptf_fold_step", {3: -1}, None, -1),
+    ("fs_ptf_fold_step", {}, tuple(range(4, 18)) + tuple(range(19, 28)), -1),
+    ("fs_ptf_fold_step_save", {0: 0}, None, -1), ("fs_ptf_fold_step_save", {0: -1}, None, -1), ("fs_ptf_fold_step_save", {2: 0}, None, -1),
+    ("fs_ptf_fold_step_save", {2: -1}, None, -1), ("fs_ptf_fold_step_save", {3: 0}, None, -1), ("fs_ptf_fold_step_save", {3: -1}, None, -1),
+    ("fs_ptf_fold_step_save", {}, tuple(range(4, 18)) + tuple(range(19, 31)), -1),
+    ("fs_ptf_fold_step_save", {0: 0}, (28, 29, 30), -1),
+    # V, h, w, lat, xs, rho, om, dep, Es, w2c (optional), Kn, thres, tables, scratch, bufA, bufB, counts
+    ("fs_ptf_fold", {0: 1}, None, -1), ("fs_ptf_fold", {0: 0}, None, -1), ("fs_ptf_fold", {0: -1}, None, -1),
+    ("fs_ptf_fold", {0: 2, 1: 0}, None, -1), ("fs_ptf_fold", {0: 2, 1: -1}, None, -1), ("fs_ptf_fold", {0: 2, 2: 0}, None, -1),
+    ("fs_ptf_fold", {0: 2, 2: -1}, None, -1), ("fs_ptf_fold", {0: 2}, (3, 4, 5, 6, 7, 8, 10, 12, 13, 14, 15, 16), -1),
+    ("fs_ptf_fold", {0: 1, 14: A5, 15: A5}, None, -1), ("fs_ptf_fold", {0: 2, 14: A5}, (3, 15), -1),
+    # V, h, w, Es, Kn, kpix, E0
+    ("fs_ptf_cameras", {0: 0}, None, -1), ("fs_ptf_cameras", {0: -1}, None, -1), ("fs_ptf_cameras", {1: 0}, None, -1),
+    ("fs_ptf_cameras", {1: -1}, None, -1), ("fs_ptf_cameras", {2: 0}, None, -1), ("fs_ptf_cameras", {2: -1}, None, -1),
+    ("fs_ptf_cameras", {}, (3, 4, 5, 6), -1),
+    # M_max, h, w, scratch, lists: pointer arithmetic only, never a launch
+    ("fs_ptf_fold_step_lists", {}, None, 0), ("fs_ptf_fold_step_lists", {0: 0}, None, -1), ("fs_ptf_fold_step_lists", {0: -1}, None, -1),
+    ("fs_ptf_fold_step_lists", {1: 0}, None, -1), ("fs_ptf_fold_step_lists", {1: -1}, None, -1), ("fs_ptf_fold_step_lists", {2: 0}, None, -1),
+    ("fs_ptf_fold_step_lists", {2: -1}, None, -1), ("fs_ptf_fold_step_lists", {}, (3, 4), -1),
+]
+# n_keep, n_fuse, n_app, keep, fuse, fpix, app, X R E D (7-10), x_i rho_i d_i E_i (11-14), g_out, g_in, g_lat_i .. g_d_i (17-21)
+# [, P, scratch]: both forms answer these alike
+for _name in ("fs_ptf_write_state_backward", "fs_ptf_write_state_backward_det"):
+    PTF_STATUS_TABLE += [
+        (_name, {0: -1}, None, -1), (_name, {1: -1}, None, -1), (_name, {2: -1}, None, -1), (_name, {}, (15, 16), -1),
+        (_name, {0: 0, 1: 0, 2: 0}, (15, 16), -1),                       # (the two arrays are required even of an empty job)
+        (_name, {0: 0, 1: 0, 2: 0}, None, 0), (_name, {0: 0, 1: 0, 2: 0, 15: A6, 16: A6}, "all", 0),
+        (_name, {0: 0, 1: 0, 2: 0, 15: A5, 16: A5}, None, 0),
+        (_name, {}, tuple(range(7, 15)) + tuple(range(17, 22)), -1),
+        (_name, {0: 0, 1: 0}, tuple(range(11, 15)) + tuple(range(17, 22)), -1),
+        (_name, {1: 0, 2: 0}, (7, 8, 9, 10), -1), (_name, {0: 0, 2: 0}, (7, 8, 9, 10), -1),
+        (_name, {16: A5}, None, -1), (_name, {1: 0, 2: 0, 16: A5}, None, -1), (_name, {0: 0, 2: 0, 16: A5}, None, -1),
+        (_name, {15: A5}, (11, 17), -1),                                 # (entries of g_out may be NULL; something else is wrong here)
+    ]
+# n_fuse, fuse_idx, fuse_pix, R, O, rho_i, om_i, dcat, g_G, g_R, g_O, g_lat_i, g_rho_i, g_om_i[, P, scratch]
+for _name in ("fs_ptf_gru_inputs_backward", "fs_ptf_gru_inputs_backward_det"):
+    PTF_STATUS_TABLE += [(_name, {0: -1}, None, -1), (_name, {0: 0}, None, 0), (_name, {0: 0}, "all", 0),
+                         (_name, {}, tuple(range(1, 14)), -1)]
+# the deterministic forms' own arguments: P (22 / 14) negative is refused before the empty job is answered, P = 0 and a NULL
+# scratch (23 / 15) only where there are fused rows
+PTF_STATUS_TABLE += [
+    ("fs_ptf_write_state_backward_det", {0: 0, 1: 0, 2: 0, 22: -1}, None, -1), ("fs_ptf_write_state_backward_det", {22: -1}, None, -1),
+    ("fs_ptf_write_state_backward_det", {1: 0, 22: -1}, None, -1),
+    ("fs_ptf_write_state_backward_det", {0: 0, 1: 0, 2: 0, 22: 0}, None, 0), ("fs_ptf_write_state_backward_det", {22: 0}, None, -1),
+    ("fs_ptf_write_state_backward_det", {0: 0, 2: 0, 22: 0}, None, -1),
+    ("fs_ptf_write_state_backward_det", {0: 0, 1: 0, 2: 0}, (23,), 0), ("fs_ptf_write_state_backward_det", {}, (4, 5, 23), -1),
+    ("fs_ptf_write_state_backward_det", {0: 0, 2: 0}, (4, 5, 23), -1),
+    ("fs_ptf_gru_inputs_backward_det", {0: 0, 14: -1}, None, -1), ("fs_ptf_gru_inputs_backward_det", {14: -1}, None, -1),
+    ("fs_ptf_gru_inputs_backward_det", {0: 0, 14: 0}, None, 0), ("fs_ptf_gru_inputs_backward_det", {14: 0}, None, -1),
+    ("fs_ptf_gru_inputs_backward_det", {0: 0}, (15,), 0), ("fs_ptf_gru_inputs_backward_det", {}, (15,), -1),
+    ("fs_ptf_gru_inputs_backward_det", {0: 0, 14: 0}, (15,), 0), ("fs_ptf_gru_inputs_backward_det", {0: 0, 14: -1}, "all", -1),
+]
+
+
+def test_ptf_entry_points_answer_the_recorded_statuses():
+    """The PTF fold's twelve int-returning entry points over PTF_STATUS_TABLE: sizes negative / zero / positive, each required
+    pointer NULL in turn, the empty jobs, and for the deterministic backwards P of -1 / 0 and a NULL scratch with and without
+    fused rows.  The table was recorded from the revision before the host layer got one backward driver per pair and holds
+    for both; no row reaches a launch, so no device is involved."""
+    import ctypes as C
+    from freesplat_amd import _lib
+    L = _lib.lib()
+    dummy = 4096
+    arrays = {A6: [dummy] * 6, A5: [dummy] * 5 + [None]}
+    n_calls = 0
+    for name, over, nulls, want in PTF_STATUS_TABLE:
+        _, at = _lib.SIGNATURES[name]
+        is_ptr = [a is C.c_void_p or a is C.POINTER(C.c_void_p) for a in at]
+        base = [A6 if a is C.POINTER(C.c_void_p) else dummy if a is C.c_void_p else 0.1 if a is C.c_float else 1 for a in at]
+        if at[-1] is C.c_void_p:
+            base[-1] = None                                              # the stream
+        for i, v in over.items():
+            base[i] = v
+        if nulls == "all":
+            variants = [[None if (is_ptr[i] and i not in over) else v for i, v in enumerate(base)]]
+        else:
+            variants = [base] if nulls is None else [base[:i] + [None] + base[i + 1:] for i in nulls]
+            assert all(is_ptr[i] for i in (nulls or ()))
+        for args in variants:
+            keep = [(C.c_void_p * 6)(*arrays[v]) if isinstance(v, str) else v for v in args]     # (alive over the call)
+            assert getattr(L, name)(*keep) == want, (name, over, nulls, args)
+            n_calls += 1
+    assert n_calls == 331
+
+
 def test_every_entry_point_validates_its_arguments_before_touching_a_device():
     """Error behaviour of the boundary, checked without a GPU: every int-returning entry point called with NULL pointers
     answers FS_ERR_INVALID_ARG (-1) when its sizes are positive, and -1 or FS_OK (an empty job) when they are zero --

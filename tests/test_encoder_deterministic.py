@@ -62,6 +62,18 @@ def test_existing_size_queries_unchanged():
         assert L.fs_cost_volume_backward_workspace_bytes_for(*a, 0) == full
         assert L.fs_cost_volume_backward_workspace_bytes_for(*a, 1) == scatter
     assert L.fs_ptf_fold_scratch_bytes(5000, 48, 64) == 3124224
+    # the PTF fold's four queries over M x (h, w), V x (h, w) and n_fuse x P, recorded before their layouts became named structs
+    match = {(0, 7, 9): 1536, (0, 48, 64): 16384, (1, 7, 9): 1536, (1, 48, 64): 16384, (1000, 7, 9): 9984,
+             (1000, 48, 64): 24832, (5000, 7, 9): 46336, (5000, 48, 64): 61184}
+    step = {(0, 7, 9): 3840, (0, 48, 64): 42752, (1, 7, 9): 3840, (1, 48, 64): 42752, (1000, 7, 9): 80384,
+            (1000, 48, 64): 1033984, (5000, 7, 9): 148736, (5000, 48, 64): 3124224}
+    fold = {(2, 7, 9): 68864, (2, 48, 64): 3287808, (3, 7, 9): 69888, (3, 48, 64): 3340032, (5, 7, 9): 72192,
+            (5, 48, 64): 3444736}
+    det = {(0, 63): 768, (0, 3072): 37120, (10, 63): 4096, (10, 3072): 40448, (3072, 63): 836352, (3072, 3072): 872704}
+    for fn, table in ((L.fs_ptf_scratch_bytes, match), (L.fs_ptf_fold_scratch_bytes, step), (L.fs_ptf_fold_bytes, fold),
+                      (L.fs_ptf_backward_det_bytes, det)):
+        for a, want_bytes in table.items():
+            assert fn(*a) == want_bytes, (a, want_bytes)
 
 
 def _call(name, size, ptr=None, **over):

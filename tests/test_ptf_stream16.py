@@ -100,3 +100,28 @@ def test_stream16_is_one_gather_of_the_parameters():
     ops = [e.key for e in prof.key_averages() if e.key in ("aten::index", "aten::cat")]
     n_index = sum(e.count for e in prof.key_averages() if e.key == "aten::index")
     assert n_index == 1 and "aten::cat" in ops
+
+
+def test_operand_cache_follows_the_parameters_and_dies_with_the_module():
+    """One cache entry per GRU module holds the tables and both streams: the same tensor objects until a parameter changes
+    (storage or version counter), all three rebuilt after that, no entry left once the module is gone."""
+    import gc
+    import weakref
+    gc.collect()
+    n_before = len(P._operand_cache)
+    gru = P.GRU()
+    forms = ((P.gru_tables, dict(forward_only=True)), (P.gru_operand_stream, {}), (P.gru_operand_stream_t, dict(transposed_only=True)))
+    first = [fn(gru) for fn, _ in forms]
+    assert len(P._operand_cache) == n_before + 1
+    for (fn, kw), t in zip(forms, first):
+        assert fn(gru) is t and torch.equal(t, P._gru_operand_stream16(gru, **kw))
+    with torch.no_grad():
+        gru.mlp_n[2].weight.mul_(2.0)
+    for (fn, kw), old in zip(forms, first):
+        new = fn(gru)
+        fresh = P._gru_operand_stream16(gru, **kw)
+        assert new is not old and not torch.equal(new, old) and torch.equal(new, fresh) and fn(gru) is new
+    ref = weakref.ref(gru)
+    del gru
+    gc.collect()
+    assert ref() is None and len(P._operand_cache) == n_before
