@@ -1,4 +1,5 @@
-"""ctypes binding of libfreesplat_hip.so (C ABI: include/freesplat_amd.h, include/freesplat_amd_loss.h).
+"""ctypes binding of libfreesplat_hip.so (C ABI: include/freesplat_amd.h, include/freesplat_amd_loss.h,
+include/freesplat_amd_optim.h).
 
 The product path has NO fallback: if the HIP library is missing or a call fails this module
 raises.  `build()` compiles the library in-tree with hipcc for gfx950.
@@ -27,6 +28,7 @@ class RasterDims(C.Structure):
 
 ABI_VERSION = 9          # include/freesplat_amd.h FS_ABI_VERSION
 LOSS_API_VERSION = 1     # include/freesplat_amd_loss.h FS_LOSS_API_VERSION
+OPTIM_API_VERSION = 1    # include/freesplat_amd_optim.h FS_OPTIM_API_VERSION
 
 RASTER_TILE_CULL = 1
 RASTER_SH_FP16 = 2
@@ -170,6 +172,16 @@ LOSS_SIGNATURES = {
 }
 
 
+# name -> (restype, argtypes); must list every symbol include/freesplat_amd_optim.h declares (again a header and a table of
+# its own)
+_PP = C.POINTER(C.c_void_p)
+OPTIM_SIGNATURES = {
+    "fs_optim_api_version": (C.c_int, []),
+    "fs_gaussian_activate": (C.c_int, [C.c_int32] + [_VP] * 5),
+    "fs_gaussian_adam_step": (C.c_int, [C.c_int32, C.c_int32] + [_PP] * 4 + [_VP] * 3 + [C.c_double] * 3 + [_VP] * 3),
+}
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -183,7 +195,7 @@ def lib():
         # device is detected"
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
-        for table in (SIGNATURES, LOSS_SIGNATURES):
+        for table in (SIGNATURES, LOSS_SIGNATURES, OPTIM_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)  # AttributeError if the library lacks a declared symbol
                 fn.restype = res
@@ -194,6 +206,9 @@ def lib():
         if L.fs_loss_api_version() != LOSS_API_VERSION:
             raise FreeSplatHipError(f"{LIB_PATH} has loss API revision {L.fs_loss_api_version()}, this binding expects "
                                     f"{LOSS_API_VERSION} (include/freesplat_amd_loss.h FS_LOSS_API_VERSION): rebuild the library")
+        if L.fs_optim_api_version() != OPTIM_API_VERSION:
+            raise FreeSplatHipError(f"{LIB_PATH} has optimizer API revision {L.fs_optim_api_version()}, this binding expects "
+                                    f"{OPTIM_API_VERSION} (include/freesplat_amd_optim.h FS_OPTIM_API_VERSION): rebuild the library")
         _lib = L
     return _lib
 
