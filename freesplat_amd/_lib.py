@@ -29,6 +29,7 @@ class RasterDims(C.Structure):
 ABI_VERSION = 9          # include/freesplat_amd.h FS_ABI_VERSION
 LOSS_API_VERSION = 1     # include/freesplat_amd_loss.h FS_LOSS_API_VERSION
 OPTIM_API_VERSION = 1    # include/freesplat_amd_optim.h FS_OPTIM_API_VERSION
+DENSITY_API_VERSION = 1  # include/freesplat_amd_density.h FS_DENSITY_API_VERSION
 
 RASTER_TILE_CULL = 1
 RASTER_SH_FP16 = 2
@@ -181,6 +182,16 @@ OPTIM_SIGNATURES = {
     "fs_gaussian_adam_step": (C.c_int, [C.c_int32, C.c_int32] + [_PP] * 4 + [_VP] * 3 + [C.c_double] * 3 + [_VP] * 3),
 }
 
+# name -> (restype, argtypes); must list every symbol include/freesplat_amd_density.h declares (a fourth header, a fourth table)
+DENSITY_SIGNATURES = {
+    "fs_density_api_version": (C.c_int, []),
+    "fs_density_accumulate": (C.c_int, [C.c_int32] + [_VP] * 6),
+    "fs_density_plan_scratch_bytes": (C.c_size_t, [C.c_int32]),
+    "fs_density_plan": (C.c_int, [C.c_int32] + [_VP] * 5 + [C.c_float] * 6 + [_VP] * 6),
+    "fs_density_apply": (C.c_int, [C.c_int32] * 3 + [_VP] + [_PP] * 6 + [_VP] * 2 + [C.c_uint32, _VP]),
+    "fs_density_reset_opacity": (C.c_int, [C.c_int32, C.c_double] + [_VP] * 5),
+}
+
 
 def lib():
     global _lib
@@ -195,7 +206,7 @@ def lib():
         # device is detected"
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
-        for table in (SIGNATURES, LOSS_SIGNATURES, OPTIM_SIGNATURES):
+        for table in (SIGNATURES, LOSS_SIGNATURES, OPTIM_SIGNATURES, DENSITY_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)  # AttributeError if the library lacks a declared symbol
                 fn.restype = res
@@ -209,6 +220,9 @@ def lib():
         if L.fs_optim_api_version() != OPTIM_API_VERSION:
             raise FreeSplatHipError(f"{LIB_PATH} has optimizer API revision {L.fs_optim_api_version()}, this binding expects "
                                     f"{OPTIM_API_VERSION} (include/freesplat_amd_optim.h FS_OPTIM_API_VERSION): rebuild the library")
+        if L.fs_density_api_version() != DENSITY_API_VERSION:
+            raise FreeSplatHipError(f"{LIB_PATH} has density API revision {L.fs_density_api_version()}, this binding expects "
+                                    f"{DENSITY_API_VERSION} (include/freesplat_amd_density.h FS_DENSITY_API_VERSION): rebuild the library")
         _lib = L
     return _lib
 

@@ -21,6 +21,7 @@
 #include <math.h>
 
 #include "../../include/freesplat_amd_optim.h"
+#include "gaussian_act.h"
 
 namespace fs {
 
@@ -31,10 +32,8 @@ constexpr int kVec = 4;                                      // floats per lane 
 constexpr uint32_t kChunk = kAdamThreads * kVec;             // floats of one array a workgroup handles per iteration
 constexpr uint32_t kMaxGrid = 2048;                          // 8 workgroups per CU; the rest is grid-strided
 
-// The activations: the step (before the update, for the chain rule; after it, for the outputs) and fs_gaussian_activate call
-// these two, so one raw value gives one bit pattern everywhere.
-__device__ __forceinline__ float act_scale(float x) { return expf(x); }
-__device__ __forceinline__ float act_opacity(float x) { return 1.0f / (1.0f + expf(-x)); }
+// The activations act_scale / act_opacity (gaussian_act.h): the step (before the update, for the chain rule; after it, for
+// the outputs) and fs_gaussian_activate call these two, so one raw value gives one bit pattern everywhere.
 
 struct Segment {
     float* p;
@@ -74,31 +73,7 @@ __device__ __forceinline__ double ipow(double base, uint32_t e)
     return r;
 }
 
-template <int KIND>
-__device__ __forceinline__ uint32_t row_width(int M)
-{
-    return KIND == FS_OPTIM_OPACITIES ? 1u : KIND == FS_OPTIM_ROTATIONS ? 4u : KIND == FS_OPTIM_SHS ? 3u * (uint32_t)M : 3u;
-}
-
-// i = q * width + r, with the division by a constant in every branch
-template <int KIND>
-__device__ __forceinline__ void row_of(uint32_t i, int M, uint32_t& q, uint32_t& r)
-{
-    if constexpr (KIND == FS_OPTIM_OPACITIES) {
-        q = i; r = 0;
-    } else if constexpr (KIND == FS_OPTIM_ROTATIONS) {
-        q = i >> 2; r = i & 3u;
-    } else if constexpr (KIND != FS_OPTIM_SHS) {
-        q = i / 3u; r = i - 3u * q;
-    } else {
-        switch (M) {
-            case 1: q = i / 3u; r = i - 3u * q; break;
-            case 4: q = i / 12u; r = i - 12u * q; break;
-            case 9: q = i / 27u; r = i - 27u * q; break;
-            default: q = i / 48u; r = i - 48u * q; break;
-        }
-    }
-}
+// row_width<KIND>(M), row_of<KIND>(i, M, q, r): gaussian_act.h
 
 // One element.  g arrives as the gradient with respect to the activated value; `act` receives the activation of the new
 // raw value (scales, opacities).

@@ -10,6 +10,12 @@ the result in one pass over the bytes (DESIGN.md "Gaussian Adam").  With `sparse
 and skips every Gaussian the view did not see -- its gradients are not read, its parameters and moments are not written (the
 sparse Adam of 3DGS trainers).  Nothing synchronises with the host; a step can be captured in a graph.  Device tensors only:
 there is no CPU / eager path.
+
+Adaptive density control (include/freesplat_amd_density.h, csrc/gaussian_density.hip, DESIGN.md "Gaussian density control"):
+`.viewspace` goes in as the rasterizer's `means2D`, `accumulate(radii)` folds its gradient into per-Gaussian statistics,
+`densify(extent, ...)` clones, splits and prunes in one compaction over parameters and moments and REPLACES the leaves with
+tensors of the new size, `reset_opacity()` clamps the opacities.  densify() reads four counters back to size the new buffers:
+the one host synchronisation of this module, once per densification.
 """
 from __future__ import annotations
 
@@ -24,6 +30,7 @@ ARRAYS = ("means", "scales", "rotations", "opacities", "shs")                   
 GROUPS = ("means", "scales", "rotations", "opacity", "sh_dc", "sh_rest")            # FS_OPTIM_LR_*: the order of `lr`
 DEFAULT_LR = dict(means=1.6e-4, sh_dc=2.5e-3, sh_rest=1.25e-4, opacity=5e-2, scales=5e-3, rotations=1e-3)   # the usual 3DGS rates
 _RAW = ("means", "log_scales", "rotations", "logits", "shs")                        # state_dict names of the raw arrays
+_STATS = ("grad_accum", "denom", "max_radii")                                       # density statistics, "density." + name in a state_dict
 
 
 def _device_f32(t, what: str) -> Tensor:
@@ -82,9 +89,17 @@ class GaussianAdam:
         self._scales = torch.empty(N, 3, dtype=torch.float32, device=dev)
         self._opacities = torch.empty(N, 1, dtype=torch.float32, device=dev)
         self._activate()
+        self.densify_calls = 0
+        self._bind()
+
+    def _bind(self) -> None:
+        """Leaves, pointer tables, density statistics and the view-space leaf for the buffers this object holds now."""
+        dev = self.lr.device
         self.means, self.rotations, self.shs = (self._raw[i].requires_grad_(True) for i in (0, 2, 4))
         self.scales, self.opacities = self._scales.requires_grad_(True), self._opacities.requires_grad_(True)
         self._tables = tuple(_table(ts) for ts in (self._raw, self.exp_avg, self.exp_avg_sq))
+        self.grad_accum, self.denom, self.max_radii = (torch.zeros(self.N, dtype=torch.float32, device=dev) for _ in _STATS)
+        self.viewspace = torch.zeros(self.N, 3, dtype=torch.float32, device=dev).requires_grad_(True)
 
     @classmethod
     def from_gaussians(cls, gaussians, **kw) -> "GaussianAdam":
@@ -154,26 +169,135 @@ class GaussianAdam:
                                                         p(self._opacities), _lib.current_stream()), "fs_gaussian_adam_step")
         self.zero_grad()
 
+    # ---- adaptive density control ----------------------------------------------------------------------------------------
+
+    def _radii(self, radii) -> Tensor:
+        if not isinstance(radii, Tensor) or radii.device != self.lr.device or radii.dtype != torch.int32 or tuple(radii.shape) != (self.N,):
+            raise ValueError(f"freesplat_amd.refine: radii must be an int32 [{self.N}] tensor on {self.lr.device}")
+        return radii.detach().contiguous()
+
+    def accumulate(self, radii) -> None:
+        """Fold the view-space gradient of the last backward into the density statistics: for every Gaussian the view saw
+        (radii > 0) the norm of the (x, y) gradient of `.viewspace` (NDC units) is added to `grad_accum`, `denom` counts the
+        view, `max_radii` keeps the largest screen radius.  Consumes and clears `viewspace.grad`; one library call, no host
+        synchronisation.  Independent of step(): either order gives the same result (step() does not touch viewspace.grad)."""
+        g = self.viewspace.grad
+        if g is None:
+            raise ValueError("freesplat_amd.refine: accumulate() without a view-space gradient (pass opt.viewspace as the "
+                             "rasterizer's means2D and call backward() first)")
+        radii = self._radii(radii)
+        if tuple(g.shape) != (self.N, 3) or g.device != self.lr.device:
+            raise ValueError(f"freesplat_amd.refine: the gradient of viewspace is {tuple(g.shape)} on {g.device}")
+        if g.dtype != torch.float32 or not g.is_contiguous():
+            g = g.float().contiguous()
+        p = _lib.ptr
+        _lib.check(_lib.lib().fs_density_accumulate(self.N, p(g), p(radii), p(self.grad_accum), p(self.denom), p(self.max_radii),
+                                                    _lib.current_stream()), "fs_density_accumulate")
+        self.viewspace.grad = None
+
+    def _plan(self, thresholds):
+        """fs_density_plan with six float thresholds -> (kind, offset, src, [n_out, n_cloned, n_split, n_dropped]); the list is
+        read back to the host (a synchronisation)."""
+        dev, N, p = self.lr.device, self.N, _lib.ptr
+        L = _lib.lib()
+        kind = torch.empty(N, dtype=torch.uint8, device=dev)
+        offset = torch.empty(N, dtype=torch.int32, device=dev)               # uint32 in the library
+        src = torch.empty(2 * N, dtype=torch.int32, device=dev)              # uint32 in the library
+        totals = torch.empty(4, dtype=torch.int32, device=dev)
+        scratch = torch.empty(int(L.fs_density_plan_scratch_bytes(N)), dtype=torch.uint8, device=dev)
+        _lib.check(L.fs_density_plan(N, p(self.grad_accum), p(self.denom), p(self.max_radii), p(self._scales), p(self._opacities),
+                                     *thresholds, p(kind), p(offset), p(src), p(totals), p(scratch), _lib.current_stream()),
+                   "fs_density_plan")
+        return kind, offset, src, [int(x) for x in totals.tolist()]
+
+    def densify(self, extent, grad_threshold=2e-4, min_opacity=0.005, percent_dense=0.01, max_screen_size=None, prune_big=False,
+                seed=None, max_gaussians=None) -> dict:
+        """Clone, split and prune in one pass (the set 3DGS's clone -> split -> prune sequence leaves).  With avg = grad_accum /
+        denom over the views accumulated since the last densify and s_max the largest scale of a Gaussian:
+          avg >= grad_threshold and s_max <= percent_dense * extent   clone: the Gaussian keeps its moments, a copy starts with none
+          avg >= grad_threshold and s_max >  percent_dense * extent   split: two children, scales / 1.6, means drawn from the parent
+          opacity < min_opacity, screen radius > max_screen_size (if given), s_max > 0.1 * extent (if prune_big)   dropped
+        (a split parent is dropped when its children would exceed 0.1 * extent; its screen radius is not tested).  `extent`: the
+        scene's radius in world units.  `seed`: of the children's positions; None = the number of densify calls so far.
+        `max_gaussians`: if the result would be larger, the plan is redone with cloning and splitting off (prune only).
+        Returns {n_out, n_cloned, n_split, n_dropped}.
+
+        The new size is known only on the device: the four counters are read back before the new buffers are allocated.  That
+        read is the ONE host synchronisation of this module; it happens once per densification (twice when max_gaussians
+        forces the prune-only plan), never per step.
+
+        The raw arrays, both moments, the pointer tables and the leaves `.means`, `.scales`, `.rotations`, `.opacities`, `.shs`
+        and `.viewspace` are REPLACED by tensors of the new size: re-read the leaves after a densify (tensors taken before it
+        are stale), and capture a graph of step() again.  The density statistics start from zero; step_count, lr, betas and
+        eps are kept.  A result of no Gaussians raises ValueError and leaves the optimizer untouched."""
+        inf = float("inf")
+        dense_scale = float(percent_dense) * float(extent)
+        prune_scale = 0.1 * float(extent) if prune_big else 0.0
+        screen = 0.0 if max_screen_size is None else float(max_screen_size)
+        th = [float(grad_threshold), dense_scale, float(min_opacity), screen, prune_scale, 1.6 * prune_scale]
+        if not all(t >= 0.0 for t in th):
+            raise ValueError(f"freesplat_amd.refine: densify thresholds must not be negative or NaN, got grad_threshold={grad_threshold}, "
+                             f"extent={extent}, percent_dense={percent_dense}, min_opacity={min_opacity}, max_screen_size={max_screen_size}")
+        seed = self.densify_calls if seed is None else int(seed)
+        kind, offset, src, totals = self._plan(th)
+        if max_gaussians is not None and totals[0] > int(max_gaussians):
+            kind, offset, src, totals = self._plan([inf] + th[1:])
+        n_out = totals[0]
+        if n_out == 0:
+            raise ValueError("freesplat_amd.refine: densify() would drop every Gaussian; the optimizer is unchanged")
+        dev, p = self.lr.device, _lib.ptr
+        new = [[torch.empty((n_out,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev) for t in self._raw] for _ in range(3)]
+        scales = torch.empty(n_out, 3, dtype=torch.float32, device=dev)
+        opacities = torch.empty(n_out, 1, dtype=torch.float32, device=dev)
+        with torch.no_grad():
+            _lib.check(_lib.lib().fs_density_apply(self.N, self.M, n_out, p(src), *self._tables, *[_table(ts) for ts in new],
+                                                   p(scales), p(opacities), seed & 0xFFFFFFFF, _lib.current_stream()),
+                       "fs_density_apply")
+        self.N = n_out
+        self._raw, self.exp_avg, self.exp_avg_sq = new
+        self._scales, self._opacities = scales, opacities
+        self._bind()
+        self.densify_calls += 1
+        return dict(zip(("n_out", "n_cloned", "n_split", "n_dropped"), totals))
+
+    def reset_opacity(self, max_opacity=0.01) -> None:
+        """opacity = min(opacity, max_opacity) on the raw logits, both opacity moments set to zero, `.opacities` rewritten: one
+        launch, no host synchronisation.  Everything else is left as it is."""
+        if not 0.0 < float(max_opacity) < 1.0:
+            raise ValueError(f"freesplat_amd.refine: max_opacity must lie inside (0, 1), got {max_opacity}")
+        p = _lib.ptr
+        with torch.no_grad():
+            _lib.check(_lib.lib().fs_density_reset_opacity(self.N, float(max_opacity), p(self._raw[3]), p(self.exp_avg[3]),
+                                                           p(self.exp_avg_sq[3]), p(self._opacities), _lib.current_stream()),
+                       "fs_density_reset_opacity")
+
     def state_dict(self) -> dict:
-        """Copies of the raw parameters, both moments, the step counter and the rates (device tensors) and the scalars."""
+        """Copies of the raw parameters, both moments, the density statistics, the step counter and the rates (device tensors)
+        and the scalars."""
         out = {k: t.detach().clone() for k, t in zip(_RAW, self._raw)}
         out.update({"exp_avg." + k: t.clone() for k, t in zip(_RAW, self.exp_avg)})
         out.update({"exp_avg_sq." + k: t.clone() for k, t in zip(_RAW, self.exp_avg_sq)})
+        out.update({"density." + k: getattr(self, k).clone() for k in _STATS})
         out.update(step=self.step_count.clone(), lr=self.lr.clone(), betas=self.betas, eps=self.eps, sparse=self.sparse)
         return out
 
     def load_state_dict(self, state: dict) -> None:
         """Into the buffers this object already owns (the leaves stay the same tensors); `.scales` / `.opacities` are rewritten
-        from the loaded raw values.  betas, eps and `sparse` are taken over as well."""
+        from the loaded raw values.  betas, eps and `sparse` are taken over as well; the density statistics are taken when the
+        state has them and zeroed when it does not."""
         pairs = [(t, state[k]) for k, t in zip(_RAW, self._raw)]
         pairs += [(t, state["exp_avg." + k]) for k, t in zip(_RAW, self.exp_avg)]
         pairs += [(t, state["exp_avg_sq." + k]) for k, t in zip(_RAW, self.exp_avg_sq)]
         pairs += [(self.step_count, state["step"]), (self.lr, state["lr"])]
+        pairs += [(getattr(self, k), state["density." + k]) for k in _STATS if "density." + k in state]
         for dst, src in pairs:
             if tuple(dst.shape) != tuple(src.shape) or dst.dtype != src.dtype:
                 raise ValueError(f"freesplat_amd.refine: state of shape {tuple(src.shape)} {src.dtype} for a buffer "
                                  f"{tuple(dst.shape)} {dst.dtype}")
         with torch.no_grad():
+            for k in _STATS:
+                if "density." + k not in state:
+                    getattr(self, k).zero_()
             for dst, src in pairs:
                 dst.copy_(src)
             self._activate()
