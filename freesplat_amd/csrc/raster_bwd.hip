@@ -14,6 +14,7 @@
 #include <type_traits>
 
 #include "fs_common.h"
+#include "raster_host.h"
 
 namespace fs {
 
@@ -934,12 +935,11 @@ int launch_render_bwd(const fs_raster_dims& d, const float* bg, const void* geom
                       float* grad, hipStream_t st, const DetRegion* det = nullptr, uint32_t cap_lim = 0xffffffffu)
 {
     const int T = num_tiles(d.H, d.W);
-    const size_t P = (size_t)d.H * d.W;
     const GeomView g = geom_view(const_cast<void*>(geom), d.N);
     const uint32_t* offsets = (const uint32_t*)binning;
-    const uint32_t* point_list = (const uint32_t*)((const char*)binning + binning_offsets_bytes(d.H, d.W));
+    const uint32_t* point_list = at<const uint32_t>(binning, BinningLayout(d.H, d.W).point_list);
     const float* final_T = (const float*)image;
-    const int32_t* n_contrib = (const int32_t*)((const char*)image + align_up(P * 4, 256));
+    const int32_t* n_contrib = at<const int32_t>(image, ImageLayout(d.H, d.W).n_contrib);
     // zero the view's 48 N bytes of screen-space gradient rows with a kernel of our own: hipMemsetAsync's fill kernel ran this at
     // 0.18 TB/s (264 us per view at 1.0 M Gaussians, 19 % of the training step's GPU time: profiles/r6_bwd_fill_ab.txt)
     // (deterministic mode: the counts of the index instead -- det_finish writes every gradient row)
@@ -1002,6 +1002,88 @@ int launch_preprocess_bwd(const fs_raster_dims& d, int V, const float* means3D, 
 
 }  // namespace
 
+namespace {
+
+// The one argument check of the six backward entry points (statuses: tests/test_abi.py RASTER_STATUS_TABLE).  FS_OK with
+// *empty set: nothing to do (no views, or an empty Gaussian set, whose arrays may be NULL as in the forward).
+int check_backward_args(const fs_raster_dims* dims, int32_t v, const float* means3D, const float* cov3D, const float* shs,
+                        const float* colors_precomp, const float* opacities, bool required, const size_t* strides,
+                        const float* dL_dshs, const float* dL_dcolors, int32_t n_streams, void* const* streams, int32_t row0,
+                        int32_t nrows, bool* empty)
+{
+    *empty = false;
+    if (!dims || v < 0 || !strides || n_streams < 0 || n_streams > kMaxStreams || (n_streams > 0 && !streams))
+        return FS_ERR_INVALID_ARG;
+    const fs_raster_dims& d = *dims;
+    if (row0 < 0 || (nrows >= 0 && (long long)row0 + nrows > d.N)) return FS_ERR_INVALID_ARG;
+    if ((d.flags & FS_RASTER_SCALE_ROT) && (d.flags & FS_RASTER_COV_FULL)) return FS_ERR_INVALID_ARG;   // two row layouts
+    if (v == 0) { *empty = true; return FS_OK; }
+    if (d.N < 0 || (d.flags & FS_RASTER_NO_BACKWARD_STATE)) return FS_ERR_INVALID_ARG;   // (that forward kept no n_contrib)
+    if (d.N == 0) { *empty = true; return FS_OK; }
+    if (!means3D || !cov3D || !opacities || !required) return FS_ERR_INVALID_ARG;
+    if ((shs == nullptr) == (colors_precomp == nullptr)) return FS_ERR_INVALID_ARG;
+    if (shs ? !dL_dshs : !dL_dcolors) return FS_ERR_INVALID_ARG;
+    if (shs && d.M * 3 > 48) return FS_ERR_UNSUPPORTED;
+    return FS_OK;
+}
+
+size_t det_region_bytes(const fs_raster_dims& d, size_t cap) { return (d.flags & FS_RASTER_DETERMINISTIC) ? DetRegion::bytes(d.N, cap) : 0; }
+
+// The one backward driver: the blend backward of each of the v views into its gradient rows, alternating over the side streams
+// (ns > 1), then ONE pass over rows [row0, row0 + nrows) of the Gaussians that sums the parameter gradients of all views.
+// `cap_lim`: instance capacity of the deterministic regions.  The single-view entry points are this with v = 1, zero strides
+// and no side streams.
+int raster_backward_driver(const fs_raster_dims* dims, int32_t v, const float* means3D, const float* cov3D, const float* shs,
+                           const float* colors_precomp, const float* opacities, const float* bg, const float* viewmatrix,
+                           const float* projmatrix, const float* campos, const float* tanfov, const float* scale,
+                           const void* geom, const void* binning, const void* image, const uint32_t* counters,
+                           const size_t strides[3], size_t cap_lim, const float* dL_dcolor, const float* dL_ddepth,
+                           const float* dL_dalpha, void* grad_scratch, float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcov3D,
+                           float* dL_dshs, float* dL_dcolors, float* dL_dopacities, int32_t accumulate, int32_t n_streams,
+                           void* const* streams, void* main_stream, int32_t row0, int32_t nrows, int32_t with_blend)
+{
+    bool empty;
+    int rc = check_backward_args(dims, v, means3D, cov3D, shs, colors_precomp, opacities,
+                                 bg && viewmatrix && projmatrix && campos && geom && binning && image && dL_dcolor && grad_scratch &&
+                                     dL_dmeans3D && dL_dmeans2D && dL_dcov3D && dL_dopacities,
+                                 strides, dL_dshs, dL_dcolors, n_streams, streams, row0, nrows, &empty);
+    if (rc != FS_OK || empty) return rc;
+    const fs_raster_dims d = *dims;
+    const int ns = n_streams <= 1 ? 0 : (n_streams < v ? n_streams : v);
+    hipStream_t main = (hipStream_t)main_stream;
+    const bool det = (d.flags & FS_RASTER_DETERMINISTIC) != 0;
+    // deterministic mode: one slab + index region per stream in flight, after the v gradient buffers
+    const BwdScratchLayout gl(d.N, v, det ? 1 : 0, det_region_bytes(d, cap_lim));
+    const size_t P = (size_t)d.H * d.W;
+    if (with_blend) {   // (not for a later chunk of a chunked gradient exchange: the blend backward of every view already ran)
+        if (det && cap_lim == 0) return FS_ERR_INVALID_ARG;   // (a binning stride too small to hold a point list)
+        ForkJoin* const fj = ns > 0 ? ForkJoin::get() : nullptr;   // (the device and the events only where side streams are used)
+        if (ns > 0 && (!fj || fj->fork(main, streams, ns) != FS_OK)) return FS_ERR_LAUNCH;
+        for (int i = 0; i < v && rc == FS_OK; ++i) {
+            const DetRegion region(at<char>(grad_scratch, gl.region(ns > 0 ? i % ns : 0)), d.N);
+            rc = launch_render_bwd(d, bg + 3 * (size_t)i, at<char>(geom, strides[0] * i), at<char>(binning, strides[1] * i),
+                                   at<char>(image, strides[2] * i), counters ? counters + 2 * (size_t)i : nullptr,
+                                   dL_dcolor + 3 * P * i, dL_ddepth ? dL_ddepth + P * i : nullptr,
+                                   dL_dalpha ? dL_dalpha + P * i : nullptr, at<float>(grad_scratch, gl.rows(i)),
+                                   ns > 0 ? (hipStream_t)streams[i % ns] : main, det ? &region : nullptr,
+                                   (uint32_t)std::min<size_t>(cap_lim, 0xffffffffu));
+        }
+        if (ns > 0 && fj->join(main, streams, ns) != FS_OK) return FS_ERR_LAUNCH;
+        if (rc != FS_OK) return rc;
+    }
+    return launch_preprocess_bwd(d, v, means3D, cov3D, shs, opacities, viewmatrix, projmatrix, campos, tanfov, scale, geom,
+                                 strides[0], grad_scratch, gl.row_stride, dL_dmeans3D, dL_dmeans2D, dL_dcov3D, dL_dshs,
+                                 dL_dcolors, dL_dopacities, accumulate, main, row0, nrows);
+}
+
+// instance capacity of a views call's deterministic regions: what its binning stride holds past the tile ranges
+size_t views_cap(const fs_raster_dims* dims, const size_t* strides)
+{
+    return dims && strides ? BinningLayout::capacity(dims->H, dims->W, strides[1]) : 0;
+}
+
+}  // namespace
+
 FS_API int fs_raster_backward_alpha(const fs_raster_dims* dims, const float* means3D, const float* cov3D,
                                     const float* shs, const float* colors_precomp, const float* opacities, const float* bg,
                                     const float* viewmatrix, const float* projmatrix, const float* campos,
@@ -1012,27 +1094,11 @@ FS_API int fs_raster_backward_alpha(const fs_raster_dims* dims, const float* mea
                                     float* dL_dshs, float* dL_dcolors, float* dL_dopacities, int accumulate,
                                     void* stream_)
 {
-    if (!dims) return FS_ERR_INVALID_ARG;
-    const fs_raster_dims d = *dims;
-    if (d.N < 0 || (d.flags & FS_RASTER_NO_BACKWARD_STATE)) return FS_ERR_INVALID_ARG;   // (that forward kept no n_contrib)
-    if ((d.flags & FS_RASTER_SCALE_ROT) && (d.flags & FS_RASTER_COV_FULL)) return FS_ERR_INVALID_ARG;
-    if (d.N == 0) return FS_OK;  // an empty Gaussian set has empty gradients; its arrays may be NULL (as in the forward)
-    if (!means3D || !cov3D || !opacities || !bg || !viewmatrix || !projmatrix || !campos || !geom ||
-        !binning || !image || !dL_dcolor || !grad_scratch || !dL_dmeans3D || !dL_dmeans2D ||
-        !dL_dcov3D || !dL_dopacities)
-        return FS_ERR_INVALID_ARG;
-    if ((shs == nullptr) == (colors_precomp == nullptr)) return FS_ERR_INVALID_ARG;
-    if (shs ? !dL_dshs : !dL_dcolors) return FS_ERR_INVALID_ARG;
-    if (shs && d.M * 3 > 48) return FS_ERR_UNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream_;
-    // deterministic mode: the view's slab and index follow its gradient rows (fs_raster_backward_scratch_bytes with v = 0)
-    const DetRegion det((char*)grad_scratch + align_up((size_t)d.N * 48, 256), d.N);
-    int rc = launch_render_bwd(d, bg, geom, binning, image, counters, dL_dcolor, dL_ddepth, dL_dalpha, (float*)grad_scratch, st,
-                               (d.flags & FS_RASTER_DETERMINISTIC) ? &det : nullptr);
-    if (rc != FS_OK) return rc;
-    return launch_preprocess_bwd(d, 1, means3D, cov3D, shs, opacities, viewmatrix, projmatrix, campos, tanfov_dev, scale_dev, geom, 0,
-                                 grad_scratch, 0, dL_dmeans3D, dL_dmeans2D, dL_dcov3D, dL_dshs, dL_dcolors,
-                                 dL_dopacities, accumulate, st);
+    static const size_t no_strides[3] = {0, 0, 0};
+    return raster_backward_driver(dims, 1, means3D, cov3D, shs, colors_precomp, opacities, bg, viewmatrix, projmatrix, campos,
+                                  tanfov_dev, scale_dev, geom, binning, image, counters, no_strides, 0xffffffffu, dL_dcolor,
+                                  dL_ddepth, dL_dalpha, grad_scratch, dL_dmeans3D, dL_dmeans2D, dL_dcov3D, dL_dshs, dL_dcolors,
+                                  dL_dopacities, accumulate, 0, nullptr, stream_, 0, -1, 1);
 }
 
 FS_API int fs_raster_backward(const fs_raster_dims* dims, const float* means3D, const float* cov3D,
@@ -1051,115 +1117,14 @@ FS_API int fs_raster_backward(const fs_raster_dims* dims, const float* means3D, 
                                     accumulate, stream_);
 }
 
-namespace {
-constexpr int kMaxStreamsBwd = 8;
-// instance capacity of a views call's deterministic regions: what its binning stride holds past the tile ranges (0: too small)
-size_t det_capacity(const fs_raster_dims& d, size_t binning_stride)
-{
-    const size_t ranges = binning_offsets_bytes(d.H, d.W);
-    return binning_stride > ranges ? (binning_stride - ranges) / 4 : 0;
-}
-}  // namespace
-
 FS_API size_t fs_raster_backward_scratch_bytes(const fs_raster_dims* dims, int32_t v, int32_t n_streams, int64_t inst_capacity)
 {
     if (!dims || dims->N < 0 || dims->H <= 0 || dims->W <= 0 || v < 0 || inst_capacity < 0) return 0;
-    const size_t N = (size_t)dims->N, rows = align_up(N * 48, 256);
-    if (!(dims->flags & FS_RASTER_DETERMINISTIC)) return v == 0 ? N * 12 * 4 : (size_t)v * rows;
+    if (!(dims->flags & FS_RASTER_DETERMINISTIC)) return BwdScratchLayout(dims->N, v, 0, 0).total;
     // the capacity as fs_raster_buffer_sizes stores it in the binning buffer (a views call reads it back from strides[1])
-    const size_t cap = align_up((size_t)(inst_capacity > 0 ? inst_capacity : 1) * 4, 256) / 4;
-    const int regions = (v == 0 || n_streams <= 1) ? 1 : std::min(std::min(n_streams, v), kMaxStreamsBwd);
-    return (v == 0 ? rows : (size_t)v * rows) + (size_t)regions * DetRegion::bytes(dims->N, cap);
-}
-
-namespace {
-struct ForkJoinBwd {
-    hipEvent_t ready = nullptr, done[kMaxStreamsBwd] = {};
-    bool ok = false;
-    ForkJoinBwd()
-    {
-        ok = hipEventCreateWithFlags(&ready, hipEventDisableTiming) == hipSuccess;
-        for (int i = 0; i < kMaxStreamsBwd && ok; ++i)
-            ok = hipEventCreateWithFlags(&done[i], hipEventDisableTiming) == hipSuccess;
-    }
-};
-}  // namespace
-
-static int raster_backward_views_impl(const fs_raster_dims* dims, int32_t v, const float* means3D, const float* cov3D,
-                                    const float* shs, const float* colors_precomp, const float* opacities, const float* bg,
-                                    const float* viewmatrix, const float* projmatrix, const float* campos,
-                                    const float* tanfov, const float* scale, const void* geom, const void* binning,
-                                    const void* image, const uint32_t* counters, const size_t strides[3], const float* dL_dcolor,
-                                    const float* dL_ddepth, const float* dL_dalpha, void* grad_scratch, float* dL_dmeans3D,
-                                    float* dL_dmeans2D, float* dL_dcov3D, float* dL_dshs, float* dL_dcolors, float* dL_dopacities,
-                                    int32_t accumulate, int32_t n_streams, void* const* streams, void* main_stream,
-                                    int32_t row0, int32_t nrows, int32_t with_blend)
-{
-    if (!dims || v < 0 || !strides || n_streams < 0 || n_streams > kMaxStreamsBwd || (n_streams > 0 && !streams))
-        return FS_ERR_INVALID_ARG;
-    if (row0 < 0 || (nrows >= 0 && (long long)row0 + nrows > dims->N)) return FS_ERR_INVALID_ARG;
-    if ((dims->flags & FS_RASTER_SCALE_ROT) && (dims->flags & FS_RASTER_COV_FULL)) return FS_ERR_INVALID_ARG;
-    if (v == 0) return FS_OK;
-    const fs_raster_dims d = *dims;
-    if (d.N < 0 || (d.flags & FS_RASTER_NO_BACKWARD_STATE)) return FS_ERR_INVALID_ARG;
-    if (d.N == 0) return FS_OK;
-    if (!means3D || !cov3D || !opacities || !bg || !viewmatrix || !projmatrix || !campos || !geom || !binning || !image ||
-        !dL_dcolor || !grad_scratch || !dL_dmeans3D || !dL_dmeans2D || !dL_dcov3D || !dL_dopacities)
-        return FS_ERR_INVALID_ARG;
-    if ((shs == nullptr) == (colors_precomp == nullptr)) return FS_ERR_INVALID_ARG;
-    if (shs ? !dL_dshs : !dL_dcolors) return FS_ERR_INVALID_ARG;
-    if (shs && d.M * 3 > 48) return FS_ERR_UNSUPPORTED;
-    // events belong to the device that was current when they were created: one cached set per (thread, device)
-    static thread_local ForkJoinBwd* fj_dev[64] = {};
-    int dev_ = 0;
-    if (hipGetDevice(&dev_) != hipSuccess || dev_ < 0 || dev_ >= 64) { set_last_error("hipGetDevice", hipGetLastError()); return FS_ERR_LAUNCH; }
-    if (!fj_dev[dev_]) fj_dev[dev_] = new ForkJoinBwd();
-    ForkJoinBwd& fj = *fj_dev[dev_];
-    const int ns = n_streams <= 1 ? 0 : (n_streams < v ? n_streams : v);
-    hipStream_t main = (hipStream_t)main_stream;
-    const size_t P = (size_t)d.H * d.W, grad_stride = align_up((size_t)d.N * kGradStride * 4, 256);
-    if (!with_blend)   // a later chunk of a chunked gradient exchange: the blend backward of every view already ran
-        return launch_preprocess_bwd(d, v, means3D, cov3D, shs, opacities, viewmatrix, projmatrix, campos, tanfov, scale, geom,
-                                     strides[0], grad_scratch, grad_stride, dL_dmeans3D, dL_dmeans2D, dL_dcov3D, dL_dshs,
-                                     dL_dcolors, dL_dopacities, accumulate, main, row0, nrows);
-    if (ns > 0) {
-        if (!fj.ok || hipEventRecord(fj.ready, main) != hipSuccess) {
-            set_last_error("event record", hipGetLastError());
-            return FS_ERR_LAUNCH;
-        }
-        for (int s = 0; s < ns; ++s)
-            if (hipStreamWaitEvent((hipStream_t)streams[s], fj.ready, 0) != hipSuccess) {
-                set_last_error("stream wait", hipGetLastError());
-                return FS_ERR_LAUNCH;
-            }
-    }
-    // deterministic mode: one slab + index region per stream in flight, after the v gradient buffers, sized by the instance
-    // capacity that the binning stride holds (fs_raster_backward_scratch_bytes)
-    const bool det = (d.flags & FS_RASTER_DETERMINISTIC) != 0;
-    const size_t cap_det = det ? det_capacity(d, strides[1]) : 0;
-    if (det && cap_det == 0) return FS_ERR_INVALID_ARG;
-    const size_t region_bytes = det ? DetRegion::bytes(d.N, cap_det) : 0;
-    int rc = FS_OK;
-    for (int i = 0; i < v && rc == FS_OK; ++i) {  // the blend backward of every view, alternating over the streams
-        hipStream_t st = ns > 0 ? (hipStream_t)streams[i % ns] : main;
-        const DetRegion region((char*)grad_scratch + grad_stride * v + region_bytes * (ns > 0 ? i % ns : 0), d.N);
-        rc = launch_render_bwd(d, bg + 3 * (size_t)i, (const char*)geom + strides[0] * i,
-                               (const char*)binning + strides[1] * i, (const char*)image + strides[2] * i,
-                               counters ? counters + 2 * (size_t)i : nullptr, dL_dcolor + 3 * P * i, dL_ddepth ? dL_ddepth + P * i : nullptr,
-                               dL_dalpha ? dL_dalpha + P * i : nullptr, (float*)((char*)grad_scratch + grad_stride * i), st, det ? &region : nullptr,
-                               (uint32_t)std::min<size_t>(cap_det, 0xffffffffu));
-    }
-    for (int s = 0; s < ns; ++s)
-        if (hipEventRecord(fj.done[s], (hipStream_t)streams[s]) != hipSuccess ||
-            hipStreamWaitEvent(main, fj.done[s], 0) != hipSuccess) {
-            set_last_error("stream join", hipGetLastError());
-            return FS_ERR_LAUNCH;
-        }
-    if (rc != FS_OK) return rc;
-    // one pass over the Gaussians for all views
-    return launch_preprocess_bwd(d, v, means3D, cov3D, shs, opacities, viewmatrix, projmatrix, campos, tanfov, scale, geom,
-                                 strides[0], grad_scratch, grad_stride, dL_dmeans3D, dL_dmeans2D, dL_dcov3D, dL_dshs,
-                                 dL_dcolors, dL_dopacities, accumulate, main, row0, nrows);
+    const size_t cap = BinningLayout::capacity(dims->H, dims->W, BinningLayout(dims->H, dims->W, inst_capacity).total);
+    const int regions = (v == 0 || n_streams <= 1) ? 1 : std::min(std::min(n_streams, v), kMaxStreams);
+    return BwdScratchLayout(dims->N, v, regions, det_region_bytes(*dims, cap)).total;
 }
 
 FS_API int fs_raster_backward_views_alpha(const fs_raster_dims* dims, int32_t v, const float* means3D, const float* cov3D,
@@ -1172,10 +1137,10 @@ FS_API int fs_raster_backward_views_alpha(const fs_raster_dims* dims, int32_t v,
                                           float* dL_dcolors, float* dL_dopacities, int32_t accumulate, int32_t n_streams,
                                           void* const* streams, void* main_stream)
 {
-    return raster_backward_views_impl(dims, v, means3D, cov3D, shs, colors_precomp, opacities, bg, viewmatrix, projmatrix, campos,
-                                      tanfov, scale, geom, binning, image, counters, strides, dL_dcolor, dL_ddepth, dL_dalpha,
-                                      grad_scratch, dL_dmeans3D, dL_dmeans2D, dL_dcov3D, dL_dshs, dL_dcolors, dL_dopacities,
-                                      accumulate, n_streams, streams, main_stream, 0, -1, 1);
+    return raster_backward_driver(dims, v, means3D, cov3D, shs, colors_precomp, opacities, bg, viewmatrix, projmatrix, campos,
+                                  tanfov, scale, geom, binning, image, counters, strides, views_cap(dims, strides), dL_dcolor,
+                                  dL_ddepth, dL_dalpha, grad_scratch, dL_dmeans3D, dL_dmeans2D, dL_dcov3D, dL_dshs, dL_dcolors,
+                                  dL_dopacities, accumulate, n_streams, streams, main_stream, 0, -1, 1);
 }
 
 FS_API int fs_raster_backward_views(const fs_raster_dims* dims, int32_t v, const float* means3D, const float* cov3D,
@@ -1210,10 +1175,10 @@ FS_API int fs_raster_backward_views_rows_alpha(const fs_raster_dims* dims, int32
                                                int32_t with_blend)
 {
     if (nrows < 0) return FS_ERR_INVALID_ARG;
-    return raster_backward_views_impl(dims, v, means3D, cov3D, shs, colors_precomp, opacities, bg, viewmatrix, projmatrix, campos,
-                                      tanfov, scale, geom, binning, image, counters, strides, dL_dcolor, dL_ddepth, dL_dalpha,
-                                      grad_scratch, dL_dmeans3D, dL_dmeans2D, dL_dcov3D, dL_dshs, dL_dcolors, dL_dopacities,
-                                      accumulate, n_streams, streams, main_stream, row0, nrows, with_blend);
+    return raster_backward_driver(dims, v, means3D, cov3D, shs, colors_precomp, opacities, bg, viewmatrix, projmatrix, campos,
+                                  tanfov, scale, geom, binning, image, counters, strides, views_cap(dims, strides), dL_dcolor,
+                                  dL_ddepth, dL_dalpha, grad_scratch, dL_dmeans3D, dL_dmeans2D, dL_dcov3D, dL_dshs, dL_dcolors,
+                                  dL_dopacities, accumulate, n_streams, streams, main_stream, row0, nrows, with_blend);
 }
 
 FS_API int fs_raster_backward_views_rows(const fs_raster_dims* dims, int32_t v, const float* means3D, const float* cov3D,

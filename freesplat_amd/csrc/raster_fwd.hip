@@ -34,6 +34,7 @@
 #include <type_traits>
 
 #include "fs_common.h"
+#include "raster_host.h"
 
 namespace fs {
 
@@ -1408,11 +1409,10 @@ using namespace fs;
 FS_API int fs_raster_buffer_sizes(int32_t N, int32_t H, int32_t W, int64_t cap, size_t out[4])
 {
     if (N < 0 || H <= 0 || W <= 0 || cap < 0 || !out) return FS_ERR_INVALID_ARG;
-    const size_t T = (size_t)num_tiles(H, W), P = (size_t)H * W;
     out[0] = geom_bytes(N > 0 ? N : 1);
-    out[1] = binning_offsets_bytes(H, W) + align_up((size_t)(cap > 0 ? cap : 1) * 4, 256);
-    out[2] = align_up(P * 4, 256) * 2;
-    out[3] = align_up(T * 4, 256) + align_up(T * (size_t)tile_capacity(cap, (int)T) * 8, 256);
+    out[1] = BinningLayout(H, W, cap).total;
+    out[2] = ImageLayout(H, W).total;
+    out[3] = FwdScratchLayout(H, W, cap).total;
     return FS_OK;
 }
 
@@ -1422,17 +1422,16 @@ FS_API const uint32_t* fs_raster_tile_ranges(const void* binning, int32_t, int32
 }
 FS_API const uint32_t* fs_raster_point_list(const void* binning, int32_t H, int32_t W)
 {
-    return (const uint32_t*)((const char*)binning + binning_offsets_bytes(H, W));
+    return at<const uint32_t>(binning, BinningLayout(H, W).point_list);
 }
 FS_API const float* fs_raster_geom_records(const void* geom) { return (const float*)geom; }
 FS_API const float* fs_raster_final_T(const void* image) { return (const float*)image; }
 FS_API const int32_t* fs_raster_n_contrib(const void* image, int32_t H, int32_t W)
 {
-    return (const int32_t*)((const char*)image + align_up((size_t)H * W * 4, 256));
+    return at<const int32_t>(image, ImageLayout(H, W).n_contrib);
 }
 
 namespace fs {
-constexpr int kMaxViewsInFlight = 16;   // key areas (scratch slots) a multi-view call may use at once
 // FREESPLAT_RASTER_BATCH: views per projection launch of a multi-view call (default 16 = all views of a call in flight).  The blends of one batch run on the
 // side streams while the projection of the next batch runs on the main stream.
 static int raster_batch()
@@ -1445,9 +1444,11 @@ static int raster_batch()
     return n;
 }
 
-static int check_forward_args(const fs_raster_dims& d, const float* means3D, const float* cov3D, const float* shs,
+// One check for both forward entry points; `required`: every per-call pointer that may never be NULL, as one conjunction.
+static int check_forward_args(bool required, const fs_raster_dims& d, const float* means3D, const float* cov3D, const float* shs,
                               const float* colors_precomp, const float* opacities, const int32_t* radii, int64_t cap)
 {
+    if (!required) return FS_ERR_INVALID_ARG;
     if (d.N < 0 || d.H <= 0 || d.W <= 0 || cap < 1) return FS_ERR_INVALID_ARG;
     if ((d.flags & FS_RASTER_SCALE_ROT) && (d.flags & FS_RASTER_COV_FULL)) return FS_ERR_INVALID_ARG;  // two row layouts
     if (d.N > 0) {  // an empty Gaussian set renders the background; its arrays may be NULL
@@ -1472,8 +1473,9 @@ static int launch_binning(const fs_raster_dims& d, int nv, const float* means3D,
                           void* geom, size_t geom_stride, void* binning, size_t binning_stride, void* scratch,
                           size_t scratch_stride, int64_t cap, int32_t* radii, uint32_t* counters, hipStream_t st)
 {
-    const int T = num_tiles(d.H, d.W);
-    const uint32_t tile_cap = tile_capacity(cap, T);
+    const FwdScratchLayout sl(d.H, d.W, cap);
+    const int T = sl.T;
+    const uint32_t tile_cap = sl.tile_cap;
     hipLaunchKernelGGL(zero_counts_kernel, dim3((T + 255) / 256, nv), dim3(256), 0, st, (char*)scratch, scratch_stride, T);
     FS_CHECK_LAUNCH("zero tile counts");
     if (d.N > 0) {
@@ -1513,16 +1515,15 @@ static int launch_blend(const fs_raster_dims& d, const float* bg, void* geom, vo
                         hipStream_t st)
 {
     const int gx = (d.W + kTile - 1) / kTile, gy = (d.H + kTile - 1) / kTile;
-    const int T = gx * gy;
-    const size_t P = (size_t)d.H * d.W;
+    const FwdScratchLayout sl(d.H, d.W, cap);
     const GeomView g = geom_view(geom, d.N > 0 ? d.N : 1);
     uint32_t* offsets = (uint32_t*)binning;
-    uint32_t* point_list = (uint32_t*)((char*)binning + binning_offsets_bytes(d.H, d.W));
+    uint32_t* point_list = at<uint32_t>(binning, BinningLayout(d.H, d.W).point_list);
     float* final_T = (float*)image;
-    int32_t* n_contrib = (int32_t*)((char*)image + align_up(P * 4, 256));
+    int32_t* n_contrib = at<int32_t>(image, ImageLayout(d.H, d.W).n_contrib);
     uint32_t* counts = (uint32_t*)scratch;
-    unsigned long long* keys = (unsigned long long*)((char*)scratch + align_up((size_t)T * 4, 256));
-    const uint32_t tile_cap = tile_capacity(cap, T);
+    unsigned long long* keys = at<unsigned long long>(scratch, sl.keys);
+    const uint32_t tile_cap = sl.tile_cap;
     const int nblk = tile_grid_blocks(gx, gy);
     {
         ScopedStage prof_(kStRender, st);
@@ -1572,11 +1573,11 @@ FS_API int fs_raster_forward(const fs_raster_dims* dims, const float* means3D, c
                              void* geom, void* binning, void* image, void* scratch, int64_t cap, float* out_color, float* out_depth,
                              float* out_alpha, int32_t* radii, uint32_t* counters, void* stream_)
 {
-    if (!dims || !bg || !viewmatrix || !projmatrix || !campos || !geom || !binning || !image ||
-        !scratch || !out_color || !out_depth || !out_alpha || !counters)
-        return FS_ERR_INVALID_ARG;
+    if (!dims) return FS_ERR_INVALID_ARG;
     const fs_raster_dims d = *dims;
-    int rc = check_forward_args(d, means3D, cov3D, shs, colors_precomp, opacities, radii, cap);
+    int rc = check_forward_args(bg && viewmatrix && projmatrix && campos && geom && binning && image && scratch && out_color &&
+                                    out_depth && out_alpha && counters,
+                                d, means3D, cov3D, shs, colors_precomp, opacities, radii, cap);
     if (rc != FS_OK) return rc;
     hipStream_t st = (hipStream_t)stream_;
     rc = launch_binning(d, 1, means3D, cov3D, shs, colors_precomp, opacities, viewmatrix, projmatrix, campos, tanfov_dev,
@@ -1586,20 +1587,6 @@ FS_API int fs_raster_forward(const fs_raster_dims* dims, const float* means3D, c
 }
 
 // ---- all views of one call in ONE host call (decoder path) ---------------------------------------------------
-namespace fs {
-constexpr int kMaxStreams = 8;
-struct ForkJoin {  // cached events: fork `main` into the side streams, join them back
-    hipEvent_t ready = nullptr, done[kMaxStreams] = {}, batch[kMaxViewsInFlight] = {};
-    bool ok = false;
-    ForkJoin()
-    {
-        ok = hipEventCreateWithFlags(&ready, hipEventDisableTiming) == hipSuccess;
-        for (int i = 0; i < kMaxStreams && ok; ++i) ok = hipEventCreateWithFlags(&done[i], hipEventDisableTiming) == hipSuccess;
-        for (int i = 0; i < kMaxViewsInFlight && ok; ++i) ok = hipEventCreateWithFlags(&batch[i], hipEventDisableTiming) == hipSuccess;
-    }
-};
-}  // namespace fs
-
 FS_API int fs_raster_scratch_slots(int32_t v, int32_t n_streams)
 {
     if (v < 0 || n_streams < 0) return FS_ERR_INVALID_ARG;
@@ -1617,31 +1604,16 @@ FS_API int fs_raster_forward_views(const fs_raster_dims* dims, int32_t v, const 
     if (!dims || v < 0 || !strides || n_streams < 0 || n_streams > fs::kMaxStreams || (n_streams > 0 && !streams))
         return FS_ERR_INVALID_ARG;
     if (v == 0) return FS_OK;
-    if (!bg || !viewmatrix || !projmatrix || !campos || !geom || !binning || !image || !scratch || !out_color ||
-        !out_depth || !out_alpha || !counters)
-        return FS_ERR_INVALID_ARG;
     const fs_raster_dims d = *dims;
-    int rc = check_forward_args(d, means3D, cov3D, shs, colors_precomp, opacities, radii, cap);
+    int rc = check_forward_args(bg && viewmatrix && projmatrix && campos && geom && binning && image && scratch && out_color &&
+                                    out_depth && out_alpha && counters,
+                                d, means3D, cov3D, shs, colors_precomp, opacities, radii, cap);
     if (rc != FS_OK) return rc;
-    // events belong to the device that was current when they were created: one cached set per (thread, device)
-    static thread_local fs::ForkJoin* fj_dev[64] = {};
-    int dev_ = 0;
-    if (hipGetDevice(&dev_) != hipSuccess || dev_ < 0 || dev_ >= 64) { set_last_error("hipGetDevice", hipGetLastError()); return FS_ERR_LAUNCH; }
-    if (!fj_dev[dev_]) fj_dev[dev_] = new fs::ForkJoin();
-    fs::ForkJoin& fj = *fj_dev[dev_];
     const int ns = n_streams <= 1 ? 0 : (n_streams < v ? n_streams : v);
     hipStream_t main = (hipStream_t)main_stream;
-    if (ns > 0 && !fj.ok) { set_last_error("event create", hipGetLastError()); return FS_ERR_LAUNCH; }
+    fs::ForkJoin* const fj = ns > 0 ? fs::ForkJoin::get() : nullptr;   // (the device and the events only where side streams are used)
+    if (ns > 0 && !fj) return FS_ERR_LAUNCH;
     const size_t P = (size_t)d.H * d.W;
-    auto join = [&]() -> int {   // main waits for everything queued on the side streams
-        for (int s = 0; s < ns; ++s)
-            if (hipEventRecord(fj.done[s], (hipStream_t)streams[s]) != hipSuccess ||
-                hipStreamWaitEvent(main, fj.done[s], 0) != hipSuccess) {
-                set_last_error("stream join", hipGetLastError());
-                return FS_ERR_LAUNCH;
-            }
-        return FS_OK;
-    };
     auto blend = [&](int i, void* scratch_i, hipStream_t st) {
         return fs::launch_blend(d, bg + 3 * (size_t)i, (char*)geom + strides[0] * i, (char*)binning + strides[1] * i,
                                 (char*)image + strides[2] * i, scratch_i, cap, out_color + 3 * P * i, out_depth + P * i,
@@ -1663,14 +1635,14 @@ FS_API int fs_raster_forward_views(const fs_raster_dims* dims, int32_t v, const 
                                     scratch_b, strides[3], cap, radii ? radii + (size_t)d.N * b0 : nullptr,
                                     counters + 2 * (size_t)b0, main);
             if (rc != FS_OK) break;
-            if (ns > 0 && hipEventRecord(fj.batch[k], main) != hipSuccess) { set_last_error("event record", hipGetLastError()); rc = FS_ERR_LAUNCH; break; }
-            for (int i = b0; i < b0 + nb && rc == FS_OK; ++i) {
+            if (ns > 0) rc = fs::ForkJoin::record(fj->batch[k], main);
+            for (int i = b0; i < b0 + nb && rc == FS_OK; ++i) {   // each view's stream waits for the batch's projection
                 hipStream_t st = ns > 0 ? (hipStream_t)streams[i % ns] : main;
-                if (ns > 0 && hipStreamWaitEvent(st, fj.batch[k], 0) != hipSuccess) { set_last_error("stream wait", hipGetLastError()); rc = FS_ERR_LAUNCH; break; }
-                rc = blend(i, scratch_b + strides[3] * (size_t)(i - b0), st);
+                if (ns > 0) rc = fs::ForkJoin::wait(st, fj->batch[k]);
+                if (rc == FS_OK) rc = blend(i, scratch_b + strides[3] * (size_t)(i - b0), st);
             }
         }
-        const int jr = join();
+        const int jr = ns > 0 ? fj->join(main, streams, ns) : FS_OK;
         if (rc == FS_OK) rc = jr;
     }
     return rc;

@@ -19,7 +19,6 @@ from dataclasses import dataclass
 from math import isqrt
 from typing import Optional
 
-import ctypes as C
 import os
 
 import torch
@@ -154,19 +153,11 @@ def check_deferred() -> None:
     counters = torch.cat([c for c, _, _, _ in pend]).tolist()
     bad, k = 0, 0
     for c, states, dev, hw in pend:
-        st = R._state(dev)
-        for i in range(c.shape[0]):
-            n_inst, overflow = counters[k]
-            k += 1
-            n_inst &= 0xFFFFFFFF
-            if states is not None:
-                states[i].num_rendered = n_inst
-            st.last_instances = max(st.last_instances, n_inst)
-            if overflow:    # (non-zero = the largest tile list: sizes the next call's capacity)
-                bad += 1
-                st.note_overflow(n_inst, overflow & 0xFFFFFFFF, *hw)
-        if not bad:
-            st.note_fit(*hw)
+        # (an overflow sizes the next call's capacity; no call after the first overflowed one counts as a fit)
+        counts, redo = R.capacity_verdict(R._state(dev), counters[k:k + len(c)], *hw, lower=False, may_fit=not bad)
+        k, bad = k + len(c), bad + len(redo)
+        for rs, n in zip(states or (), counts):
+            rs.num_rendered = n
     if bad:
         raise R._lib.FreeSplatHipError(f"{bad} deferred view(s) overflowed their instance capacity; "
                                        "re-render them (capacity history has been updated)")
@@ -174,91 +165,30 @@ def check_deferred() -> None:
 
 class _RenderViews(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, means, cov6, shs, opac, views, fulls, campos, bgs, tanfov, scale, h, w, degree,
-                deferred):
+    def forward(ctx, means, cov6, shs, opac, views, fulls, campos, bgs, tanfov, scale, h, w, degree, deferred):
         # cov6 = covariances [G,3,3], shs = harmonics [G,3,d_sh]: the reference's own layouts, read in place
-        v = views.shape[0]
-        N = means.shape[0]
-        dev = means.device
-        st = R._state(dev)
-        cap = R.default_capacity(N, st, h, w)
-        color = torch.empty(v, 3, h, w, dtype=torch.float32, device=dev)
-        depth = torch.empty(v, h, w, dtype=torch.float32, device=dev)
-        alpha = torch.empty(v, h, w, dtype=torch.float32, device=dev)
+        N, dev = means.shape[0], means.device
         s0 = GaussianRasterizationSettings(h, w, 0.0, 0.0, None, 1.0, None, None, degree, None, False, False)
-        inference = not any(ctx.needs_input_grad[:4])     # no backward will follow: the blend skips the contributor count
-
-        def launch(i, cap_i):   # single-view re-render (capacity overflow)
-            dims = R.make_dims(N, shs.shape[2], s0, sh_fp16=shs.dtype == torch.float16, native_layout=True,
-                               inference=inference)
-            rs, _, _, _ = R._launch_forward(dims, means, cov6, shs, None, opac, bgs[i], views[i], fulls[i],
-                                            campos[i], cap_i, tanfov=tanfov[i],
-                                            scale=None if scale is None else scale[i],
-                                            out=(color[i], depth[i], alpha[i]))
-            return rs
-
-        # all v views in ONE library call (fs_raster_forward_views): per-view host work is a few pointer offsets
-        # instead of seven allocations and a 23-argument ctypes call, the views alternate over the side streams
-        # inside the library and are joined back into the current stream before the call returns
-        dims = R.make_dims(N, shs.shape[2], s0, sh_fp16=shs.dtype == torch.float16, native_layout=True, inference=inference)
-        n_streams = min(R.NUM_STREAMS, v)
-        while len(st.side_streams) < n_streams:
-            st.side_streams.append(torch.cuda.Stream(device=dev))
-        sz = R._buffer_sizes(N, h, w, cap)
-        u8 = lambda n: torch.empty(n, dtype=torch.uint8, device=dev)
-        geom, binning, image = u8(v * sz[0]), u8(v * sz[1]), u8(v * sz[2])
-        # one key area per view in flight (the projection of a whole batch of views is ONE launch, fs_raster_forward_views)
-        scratch = u8(max(R._lib.lib().fs_raster_scratch_slots(v, n_streams if n_streams > 1 else 0), 1) * sz[3])
-        radii = torch.empty(v, N, dtype=torch.int32, device=dev)
-        counters = torch.empty(v, 2, dtype=torch.int32, device=dev)
-        strides = (C.c_size_t * 4)(*sz)
-        handles = (C.c_void_p * max(n_streams, 1))(*[s.cuda_stream for s in st.side_streams[:n_streams]])
-        p = R._lib.ptr
-        if v > 0:
-            R._lib.check(R._lib.lib().fs_raster_forward_views(
-                C.byref(dims), v, p(means), p(cov6), p(shs), None, p(opac), p(bgs), p(views), p(fulls), p(campos),
-                p(tanfov), p(scale), p(geom), p(binning), p(image), p(scratch), strides, cap, p(color), p(depth),
-                p(alpha), p(radii), p(counters), n_streams if n_streams > 1 else 0, handles,
-                R._lib.current_stream()), "fs_raster_forward_views")
-        states = []
-        for i in range(v):
-            rs = R.RasterState()
-            rs.dims = dims
-            rs.geom, rs.binning, rs.image = (t[i * n:(i + 1) * n] for t, n in ((geom, sz[0]), (binning, sz[1]), (image, sz[2])))
-            rs.radii, rs.counters, rs.cap = radii[i], counters[i], cap
-            rs.bg, rs.view, rs.proj, rs.campos = bgs[i], views[i], fulls[i], campos[i]
-            rs.tanfov, rs.scale = tanfov[i], None if scale is None else scale[i]
-            rs.num_rendered = -1
-            states.append(rs)
-        # everything the one-call backward needs while the views still live in the strided buffers of this call
-        batch = dict(dims=dims, sz=sz, cap=cap, geom=geom, binning=binning, image=image, counters=counters, bgs=bgs, views=views, fulls=fulls,
-                     campos=campos, tanfov=tanfov, scale=scale)
+        dims = R.make_dims(N, shs.shape[2], s0, sh_fp16=shs.dtype == torch.float16, native_layout=True,
+                           inference=not any(ctx.needs_input_grad[:4]))    # (no backward to come: the blend skips the contributor count)
+        batch, color, depth, alpha = R.rasterize_forward_views(dims, means, cov6, shs, None, opac, bgs, views, fulls, campos, tanfov,
+                                                               scale, R.default_capacity(N, R._state(dev), h, w))
+        states = [batch.state(i) for i in range(batch.v)]
         if deferred:
             # without a backward to come only the 8-byte counter pairs stay alive until the check, not the buffers
-            _pending_checks.append((counters, states if any(ctx.needs_input_grad) else None, dev, (h, w)))
+            _pending_checks.append((batch.counters, states if any(ctx.needs_input_grad) else None, dev, (h, w)))
         else:
-            counters = torch.stack([rs.counters for rs in states]).tolist()  # the single sync
-            worst, redone = 0, []
-            for i, (n_inst, overflow) in enumerate(counters):
-                n_inst &= 0xFFFFFFFF
-                if overflow:
-                    states[i] = launch(i, st.note_overflow(n_inst, overflow & 0xFFFFFFFF, h, w))
-                    redone.append(i)
-                    batch = None        # that view now lives in its own buffers: backward goes view by view
-                states[i].num_rendered = n_inst
-                worst = max(worst, n_inst)
-            if redone:
-                # the relaunches must have fitted: a second overflow (capacity clamp, saturated instance count) would
-                # leave the blend unrun and the uninitialised colour buffer returned as the image
-                again = torch.stack([states[i].counters for i in redone]).tolist()
-                if any(o for _, o in again):
-                    raise R._lib.FreeSplatHipError("rasterizer instance list overflowed twice (views "
-                                                   f"{[i for i, (_, o) in zip(redone, again) if o]})")
-            else:
-                st.note_fit(h, w)
-            st.last_instances = worst
-        ctx.states = states
-        ctx.batch = batch
+            counts, redo = R.capacity_verdict(R._state(dev), batch.counters.tolist(), h, w)  # the single sync
+            for i, cap_i in redo.items():   # single-view re-render into the view's images
+                states[i] = R._launch_forward(dims, means, cov6, shs, None, opac, bgs[i], views[i], fulls[i], campos[i], cap_i,
+                                              tanfov=tanfov[i], scale=None if scale is None else scale[i],
+                                              out=(color[i], depth[i], alpha[i]))[0]
+            for rs, n in zip(states, counts):
+                rs.num_rendered = n
+            if redo:
+                R.relaunched_fit({i: states[i] for i in redo})
+                batch = None        # those views now live in their own buffers: backward goes view by view
+        ctx.states, ctx.batch = states, batch       # (batch: while the views still live in the strided buffers of this call)
         ctx.save_for_backward(means, cov6, shs, opac)
         ctx.set_materialize_grads(False)
         return color, depth
@@ -268,57 +198,27 @@ class _RenderViews(torch.autograd.Function):
         means, cov6, shs, opac = ctx.saved_tensors
         if g_color is None and g_depth is None:
             return (None,) * 14
-        v = len(ctx.states)
-        n_streams = min(R.NUM_STREAMS, v)
-        if g_color is not None:
-            g_color = g_color.contiguous()
-        if g_depth is not None:
-            g_depth = g_depth.contiguous()
-        dev = means.device
-        N = means.shape[0]
-        if N == 0 or v == 0:   # nothing rendered: empty / zero gradients (torch hands out NULL pointers for empty tensors)
+        N, dev = means.shape[0], means.device
+        if N == 0 or not ctx.states:   # nothing rendered: empty / zero gradients (torch hands out NULL pointers for empty tensors)
             return (torch.zeros_like(means), torch.zeros_like(cov6), torch.zeros_like(shs),
                     torch.zeros(N, dtype=torch.float32, device=dev)) + (None,) * 10
-        if ctx.batch is not None:
-            # one library call: the blend backward of the views alternates over the side streams, then ONE pass
-            # over the Gaussians sums the parameter gradients of all views (fs_raster_backward_views)
-            b = ctx.batch
-            st = R._state(dev)
-            while len(st.side_streams) < n_streams:
-                st.side_streams.append(torch.cuda.Stream(device=dev))
-            if g_color is None:
-                g_color = torch.zeros(v, 3, b["dims"].H, b["dims"].W, dtype=torch.float32, device=dev)
-            f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
-            out = dict(means3D=f32(N, 3), means2D=f32(N, 3), cov3D=f32(*cov6.shape), shs=f32(*shs.shape), opacities=f32(N))
-            dims = R.backward_dims(b["dims"])       # (+ FS_RASTER_DETERMINISTIC: slabs sized by the forward's capacity)
-            scratch = torch.empty(R.backward_scratch_bytes(dims, v, n_streams if n_streams > 1 else 0, b["cap"]),
-                                  dtype=torch.uint8, device=dev)
-            strides = (C.c_size_t * 3)(*b["sz"][:3])
-            handles = (C.c_void_p * max(n_streams, 1))(*[s.cuda_stream for s in st.side_streams[:n_streams]])
-            p = R._lib.ptr
-            common = (C.byref(dims), v, p(means), p(cov6), p(shs), None, p(opac), p(b["bgs"]), p(b["views"]), p(b["fulls"]),
-                      p(b["campos"]), p(b["tanfov"]), p(b["scale"]), p(b["geom"]), p(b["binning"]), p(b["image"]), p(b["counters"]),
-                      strides, p(g_color), p(g_depth), p(scratch), p(out["means3D"]), p(out["means2D"]), p(out["cov3D"]),
-                      p(out["shs"]), None, p(out["opacities"]), 0, n_streams if n_streams > 1 else 0, handles)
-            hook = GRAD_EXCHANGE_HOOK
-            if hook is None:
-                R._lib.check(R._lib.lib().fs_raster_backward_views(*common, R._lib.current_stream()), "fs_raster_backward_views")
-            else:
-                # chunked gradient exchange (view_sharding.GradExchange("chunked")): the per-Gaussian pass runs chunk by chunk of
-                # the rows, and the reduce-scatter of chunk c (on the hook's side stream) overlaps the pass over chunk c + 1
-                hook.begin(N)
-                for ci, (c0, c1) in enumerate(hook.chunk_rows(N)):
-                    R._lib.check(R._lib.lib().fs_raster_backward_views_rows(*common, R._lib.current_stream(), c0, c1 - c0,
-                                                                            1 if ci == 0 else 0), "fs_raster_backward_views_rows")
-                    hook.chunk_ready(c0, c1, [out["means3D"], out["cov3D"], out["shs"], out["opacities"]])
-        else:
-            view_grads = lambda i: (None if g_color is None else g_color[i], None if g_depth is None else g_depth[i])
-            out = None
+        hook = GRAD_EXCHANGE_HOOK
+        final = lambda out: [out["means3D"], out["cov3D"], out["shs"], out["opacities"]]
+        if ctx.batch is None:
+            out, row = None, lambda g, i: None if g is None else g[i]
             for i, rs in enumerate(ctx.states):
-                out = R.rasterize_backward(rs, means, cov6, shs, None, opac, *view_grads(i), out=out, accumulate=i > 0)
-            if GRAD_EXCHANGE_HOOK is not None:     # (a re-rendered view forced the view-by-view backward: one chunk, no overlap)
-                GRAD_EXCHANGE_HOOK.begin(N)
-                GRAD_EXCHANGE_HOOK.chunk_ready(0, N, [out["means3D"], out["cov3D"], out["shs"], out["opacities"]])
+                out = R.rasterize_backward(rs, means, cov6, shs, None, opac, row(g_color, i), row(g_depth, i), out=out, accumulate=i > 0)
+            if hook is not None:     # (a re-rendered view forced the view-by-view backward: one chunk, no overlap)
+                hook.begin(N)
+                hook.chunk_ready(0, N, final(out))
+        elif hook is None:
+            out = R.rasterize_backward_views(ctx.batch, means, cov6, shs, None, opac, g_color, g_depth)
+        else:
+            # chunked gradient exchange (view_sharding.GradExchange("chunked")): the per-Gaussian pass runs chunk by chunk of
+            # the rows, and the reduce-scatter of chunk c (on the hook's side stream) overlaps the pass over chunk c + 1
+            hook.begin(N)
+            out = R.rasterize_backward_views(ctx.batch, means, cov6, shs, None, opac, g_color, g_depth, row_chunks=hook.chunk_rows(N),
+                                             chunk_ready=lambda c0, c1, out: hook.chunk_ready(c0, c1, final(out)))
         g_shs = out["shs"] if shs.dtype == torch.float32 else out["shs"].to(shs.dtype)
         return (out["means3D"], out["cov3D"], g_shs, out["opacities"]) + (None,) * 10
 

@@ -141,44 +141,94 @@ class RasterState:
     __slots__ = ("dims", "geom", "binning", "image", "radii", "counters", "cap", "bg", "view", "proj",
                  "campos", "tanfov", "scale", "num_rendered")
 
+    def __init__(self, dims, geom, binning, image, radii, counters, cap, bg, view, proj, campos, tanfov, scale):
+        self.dims, self.geom, self.binning, self.image = dims, geom, binning, image
+        self.radii, self.counters, self.cap = radii, counters, cap
+        self.bg, self.view, self.proj, self.campos, self.tanfov, self.scale = bg, view, proj, campos, tanfov, scale
+        self.num_rendered = -1
 
-def _launch_forward(dims: _lib.RasterDims, means3D, cov3D, shs, colors, opacities, bg, view, proj,
-                    campos, cap: int, tanfov: Optional[Tensor] = None, scale: Optional[Tensor] = None,
-                    out: Optional[tuple] = None) -> tuple[RasterState, Tensor, Tensor, Tensor]:
-    """One stream-ordered forward launch (no host sync).  `tanfov` [2] / `scale` [1]: optional
-    device-resident settings; `out` = (color[3,H,W], depth[H,W], alpha[H,W]) views to write into."""
-    dev = means3D.device
-    N, H, W = dims.N, dims.H, dims.W
+
+def _u8(n: int, dev) -> Tensor:
+    return torch.empty(n, dtype=torch.uint8, device=dev)
+
+
+def _images(lead: tuple, H: int, W: int, dev) -> list:      # color [*lead,3,H,W], depth [*lead,H,W], alpha [*lead,H,W]
+    return [torch.empty(*lead, *c, H, W, dtype=torch.float32, device=dev) for c in ((3,), (), ())]
+
+
+def _launch_forward(dims: _lib.RasterDims, means3D, cov3D, shs, colors, opacities, bg, view, proj, campos, cap: int,
+                    tanfov: Optional[Tensor] = None, scale: Optional[Tensor] = None, out: Optional[tuple] = None):
+    """One stream-ordered forward launch (no host sync) -> (RasterState, color, depth, alpha).  `tanfov` [2] / `scale` [1]:
+    optional device-resident settings; `out` = (color[3,H,W], depth[H,W], alpha[H,W]) views to write into."""
+    dev, N, H, W = means3D.device, dims.N, dims.H, dims.W
     sz = _buffer_sizes(N, H, W, cap)
-    st = _state(dev)
-    skey = torch.cuda.current_stream().cuda_stream
+    st, skey = _state(dev), torch.cuda.current_stream().cuda_stream
     scratch = st.scratch.get(skey)
     if scratch is None or scratch.numel() < sz[3]:
-        scratch = st.scratch[skey] = torch.empty(sz[3], dtype=torch.uint8, device=dev)
-    rs = RasterState()
-    rs.dims = dims
-    rs.geom = torch.empty(sz[0], dtype=torch.uint8, device=dev)
-    rs.binning = torch.empty(sz[1], dtype=torch.uint8, device=dev)
-    rs.image = torch.empty(sz[2], dtype=torch.uint8, device=dev)
-    rs.radii = torch.empty(N, dtype=torch.int32, device=dev)
-    rs.counters = torch.empty(2, dtype=torch.int32, device=dev)
-    rs.cap = cap
-    rs.bg, rs.view, rs.proj, rs.campos = bg, view, proj, campos
-    rs.tanfov, rs.scale = tanfov, scale
-    rs.num_rendered = -1
-    if out is None:
-        color = torch.empty(3, H, W, dtype=torch.float32, device=dev)
-        depth = torch.empty(H, W, dtype=torch.float32, device=dev)
-        alpha = torch.empty(H, W, dtype=torch.float32, device=dev)
-    else:
-        color, depth, alpha = out
+        scratch = st.scratch[skey] = _u8(sz[3], dev)
+    rs = RasterState(dims, _u8(sz[0], dev), _u8(sz[1], dev), _u8(sz[2], dev), torch.empty(N, dtype=torch.int32, device=dev),
+                     torch.empty(2, dtype=torch.int32, device=dev), cap, bg, view, proj, campos, tanfov, scale)
+    color, depth, alpha = out if out is not None else _images((), H, W, dev)
     p = _lib.ptr
     _lib.check(_lib.lib().fs_raster_forward(
         C.byref(dims), p(means3D), p(cov3D), p(shs), p(colors), p(opacities), p(bg), p(view), p(proj),
         p(campos), p(tanfov), p(scale), p(rs.geom), p(rs.binning), p(rs.image), p(scratch), cap,
-        p(color), p(depth),
-        p(alpha), p(rs.radii), p(rs.counters), _lib.current_stream()), "fs_raster_forward")
+        p(color), p(depth), p(alpha), p(rs.radii), p(rs.counters), _lib.current_stream()), "fs_raster_forward")
     return rs, color, depth, alpha
+
+
+class ViewBuffers:
+    """The strided buffers of one views call (fs_raster_forward_views / fs_raster_backward_views*): the opaque buffers of the v
+    views lie sz[k] bytes apart in one allocation each, the cameras are the rows of [v, ...] tensors.  state(i) is view i as
+    the RasterState of a single-view forward (slices, no copies)."""
+
+    def __init__(self, dims: _lib.RasterDims, cap: int, bgs, views, fulls, campos, tanfov, scale):
+        dev, v, N = views.device, views.shape[0], dims.N
+        self.dims, self.v, self.cap = dims, v, cap
+        self.sz = sz = _buffer_sizes(N, dims.H, dims.W, cap)
+        self.geom, self.binning, self.image = _u8(v * sz[0], dev), _u8(v * sz[1], dev), _u8(v * sz[2], dev)
+        self.radii = torch.empty(v, N, dtype=torch.int32, device=dev)
+        self.counters = torch.empty(v, 2, dtype=torch.int32, device=dev)
+        self.bgs, self.views, self.fulls, self.campos, self.tanfov, self.scale = bgs, views, fulls, campos, tanfov, scale
+
+    def state(self, i: int) -> RasterState:
+        a, b, c = self.sz[:3]
+        return RasterState(self.dims, self.geom[i * a:(i + 1) * a], self.binning[i * b:(i + 1) * b], self.image[i * c:(i + 1) * c],
+                           self.radii[i], self.counters[i], self.cap, self.bgs[i], self.views[i], self.fulls[i], self.campos[i],
+                           None if self.tanfov is None else self.tanfov[i], None if self.scale is None else self.scale[i])
+
+
+def _side_streams(dev, v: int, n_streams: Optional[int] = None):
+    """(n_streams, streams) arguments of a views call: the views alternate over min(NUM_STREAMS, v) side streams of the device
+    (created on first use and kept); one stream means none, the call then runs on the current stream alone."""
+    st = _state(dev)
+    n = min(NUM_STREAMS, v) if n_streams is None else n_streams
+    while len(st.side_streams) < n:
+        st.side_streams.append(torch.cuda.Stream(device=dev))
+    handles = (C.c_void_p * max(n, 1))(*[s.cuda_stream for s in st.side_streams[:n]])
+    return (n if n > 1 else 0), handles
+
+
+def rasterize_forward_views(dims: _lib.RasterDims, means3D, cov3D, shs, colors, opacities, bgs, views, fulls, campos, tanfov,
+                            scale, cap: int, n_streams: Optional[int] = None):
+    """All v views of one Gaussian set in ONE library call (fs_raster_forward_views; no host sync): per-view host work is a few
+    pointer offsets instead of seven allocations and a 23-argument ctypes call, the views alternate over the side streams
+    inside the library and are joined back into the current stream before the call returns.  `cov3D` in the form `dims` names
+    ([N,6], [N,3,3] or the (scales, rotation) rows [N,7]).  Returns (ViewBuffers, color [v,3,H,W], depth [v,H,W],
+    alpha [v,H,W]); the capacity check is the caller's (capacity_verdict on buffers.counters)."""
+    dev, v, H, W = means3D.device, views.shape[0], dims.H, dims.W
+    buf = ViewBuffers(dims, cap, bgs, views, fulls, campos, tanfov, scale)
+    color, depth, alpha = _images((v,), H, W, dev)
+    ns, handles = _side_streams(dev, v, n_streams)
+    # one key area per view in flight (the projection of a whole batch of views is ONE launch)
+    scratch = _u8(max(_lib.lib().fs_raster_scratch_slots(v, ns), 1) * buf.sz[3], dev)
+    p = _lib.ptr
+    if v > 0:
+        _lib.check(_lib.lib().fs_raster_forward_views(
+            C.byref(dims), v, p(means3D), p(cov3D), p(shs), p(colors), p(opacities), p(bgs), p(views), p(fulls), p(campos),
+            p(tanfov), p(scale), p(buf.geom), p(buf.binning), p(buf.image), p(scratch), (C.c_size_t * 4)(*buf.sz), cap, p(color),
+            p(depth), p(alpha), p(buf.radii), p(buf.counters), ns, handles, _lib.current_stream()), "fs_raster_forward_views")
+    return buf, color, depth, alpha
 
 
 def _f32c(t: Tensor, name: str, allow_half: bool = False) -> Tensor:
@@ -233,62 +283,109 @@ def backward_scratch_bytes(dims: _lib.RasterDims, v: int, n_streams: int, cap: i
     return n
 
 
+def capacity_verdict(st: _DeviceState, pairs, H: int, W: int, lower: bool = True, may_fit: bool = True):
+    """The one reading of the instance-capacity counters.  `pairs`: the host copies of one call's counters, per view (instances,
+    0 | largest tile list of an overflowed view) as int32.  Returns (instances per view, {view: capacity to re-render it with})
+    and updates the capacity history of `st`:
+      * every overflowed view notes its overflow (note_overflow; what that returns is the view's retry capacity);
+      * a call none of whose views overflowed notes a fit -- unless `may_fit` is false: the deferred check withholds it from
+        every pending call after the first overflowed one;
+      * last_instances becomes the largest count of the call (a single view: its count); with `lower` false (the deferred
+        check, which runs after later calls were sized) it is only ever raised."""
+    counts = [int(n) & 0xFFFFFFFF for n, _ in pairs]
+    redo = {i: st.note_overflow(counts[i], int(o) & 0xFFFFFFFF, H, W) for i, (_, o) in enumerate(pairs) if o}
+    if not redo and may_fit:
+        st.note_fit(H, W)
+    worst = max(counts, default=0)
+    st.last_instances = worst if lower else max(st.last_instances, worst)
+    return counts, redo
+
+
+def relaunched_fit(states: dict) -> list:
+    """The re-rendered views {view: RasterState} must have fitted (one host sync; returns their instance counts): a second overflow
+    (capacity clamp, saturated count) would leave the blend unrun and the uninitialised colour buffer returned as the image."""
+    pairs = torch.stack([rs.counters for rs in states.values()]).tolist()
+    bad = [i for i, (_, o) in zip(states, pairs) if o]
+    if bad:
+        raise _lib.FreeSplatHipError("rasterizer instance list overflowed twice" + (f" (views {bad})" if bad != [None] else ""))
+    return [int(n) & 0xFFFFFFFF for n, _ in pairs]
+
+
 def rasterize_forward_checked(dims, means3D, cov3D, shs, colors, opacities, bg, view, proj, campos):
     """Forward + capacity check (one host sync on the 8-byte counter pair), retrying once with the
     exact capacity when the instance list overflowed."""
     st = _state(means3D.device)
-    cap = default_capacity(dims.N, st, dims.H, dims.W)
-    rs, color, depth, alpha = _launch_forward(dims, means3D, cov3D, shs, colors, opacities, bg, view,
-                                              proj, campos, cap)
-    n_inst, overflow = (int(x) & 0xFFFFFFFF for x in rs.counters.tolist())
-    if not overflow:
-        st.note_fit(dims.H, dims.W)
-    else:          # (non-zero = the largest tile list)
-        cap = st.note_overflow(n_inst, overflow, dims.H, dims.W)
-        rs, color, depth, alpha = _launch_forward(dims, means3D, cov3D, shs, colors, opacities, bg,
-                                                  view, proj, campos, cap)
-        n_inst, overflow = (int(x) & 0xFFFFFFFF for x in rs.counters.tolist())
-        if overflow:
-            raise _lib.FreeSplatHipError("rasterizer instance list overflowed twice")
+    launch = lambda cap: _launch_forward(dims, means3D, cov3D, shs, colors, opacities, bg, view, proj, campos, cap)
+    rs, color, depth, alpha = launch(default_capacity(dims.N, st, dims.H, dims.W))
+    (n_inst,), redo = capacity_verdict(st, [rs.counters.tolist()], dims.H, dims.W)
+    if redo:
+        rs, color, depth, alpha = launch(redo[0])
+        n_inst, = relaunched_fit({None: rs})
+        st.last_instances = n_inst
     rs.num_rendered = n_inst
-    st.last_instances = n_inst
     return rs, color, depth, alpha
+
+
+def _alloc_grads(N: int, cov3D, shs, colors, dev) -> dict:
+    f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+    return dict(means3D=f32(N, 3), means2D=f32(N, 3), cov3D=f32(cov3D.shape), shs=None if shs is None else f32(shs.shape),
+                colors=None if colors is None else f32(N, 3), opacities=f32(N))
+
+
+def _cotangents(g_color, g_depth, g_alpha, shape, dev):
+    """Contiguous cotangents (the caller keeps them referenced over the launch); dL_dcolor is required by the library."""
+    if g_color is None:
+        g_color = torch.zeros(shape, dtype=torch.float32, device=dev)
+    return tuple(None if g is None else g.contiguous() for g in (g_color, g_depth, g_alpha))
 
 
 def rasterize_backward(rs: RasterState, means3D, cov3D, shs, colors, opacities, g_color, g_depth, out=None,
                        accumulate: bool = False, g_alpha=None):
     """Launch the backward of one view.  `out` = dict of preallocated gradient tensors (for the
     multi-view accumulate path) or None to allocate.  `g_alpha` [H,W] | None: cotangent of the accumulated alpha."""
-    dev = means3D.device
-    d = backward_dims(rs.dims)
-    N = d.N
-    if out is None:
-        out = dict(
-            means3D=torch.empty(N, 3, dtype=torch.float32, device=dev),
-            means2D=torch.empty(N, 3, dtype=torch.float32, device=dev),
-            cov3D=torch.empty(cov3D.shape, dtype=torch.float32, device=dev),
-            shs=None if shs is None else torch.empty(shs.shape, dtype=torch.float32, device=dev),
-            colors=None if colors is None else torch.empty(N, 3, dtype=torch.float32, device=dev),
-            opacities=torch.empty(N, dtype=torch.float32, device=dev),
-        )
+    dev, d, N = means3D.device, backward_dims(rs.dims), rs.dims.N
+    out = _alloc_grads(N, cov3D, shs, colors, dev) if out is None else out
     if d.flags & _lib.RASTER_DETERMINISTIC:
         scratch = torch.empty(max(backward_scratch_bytes(d, 0, 0, rs.cap), 1), dtype=torch.uint8, device=dev)
     else:
         scratch = torch.empty(max(N, 1) * 12, dtype=torch.float32, device=dev)
-    if g_color is None:
-        g_color = torch.zeros(3, d.H, d.W, dtype=torch.float32, device=dev)
-    g_color = g_color.contiguous()
-    if g_depth is not None:
-        g_depth = g_depth.contiguous()
-    if g_alpha is not None:
-        g_alpha = g_alpha.contiguous()
+    g_color, g_depth, g_alpha = _cotangents(g_color, g_depth, g_alpha, (3, d.H, d.W), dev)
     p = _lib.ptr
     _lib.check(_lib.lib().fs_raster_backward_alpha(
         C.byref(d), p(means3D), p(cov3D), p(shs), p(colors), p(opacities), p(rs.bg), p(rs.view), p(rs.proj),
         p(rs.campos), p(rs.tanfov), p(rs.scale), p(rs.geom), p(rs.binning), p(rs.image), p(rs.counters), p(g_color),
-        p(g_depth), p(g_alpha), p(scratch),
-        p(out["means3D"]), p(out["means2D"]), p(out["cov3D"]), p(out["shs"]), p(out["colors"]),
+        p(g_depth), p(g_alpha), p(scratch), p(out["means3D"]), p(out["means2D"]), p(out["cov3D"]), p(out["shs"]), p(out["colors"]),
         p(out["opacities"]), 1 if accumulate else 0, _lib.current_stream()), "fs_raster_backward_alpha")
+    return out
+
+
+def rasterize_backward_views(buf: ViewBuffers, means3D, cov3D, shs, colors, opacities, g_color, g_depth, g_alpha=None,
+                             row_chunks=None, chunk_ready=None, n_streams: Optional[int] = None, dims=None) -> dict:
+    """The backward of all views of a rasterize_forward_views call in one library call: the blend backward of the views
+    alternates over the side streams, then ONE pass over the Gaussians sums the parameter gradients of all views
+    (fs_raster_backward_views; with a `g_alpha` [v,H,W] its _alpha form).  `row_chunks` = [(row0, row1), ...]: the per-Gaussian
+    pass runs chunk by chunk of the rows instead (fs_raster_backward_views_rows: the blend backward with the first chunk only)
+    and `chunk_ready(row0, row1, grads)` is called after each chunk is queued.  `dims`: the dims to launch with (default
+    backward_dims(buf.dims)).  Returns the gradient dict of rasterize_backward."""
+    dev, v = means3D.device, buf.v
+    d = backward_dims(buf.dims) if dims is None else dims           # (+ FS_RASTER_DETERMINISTIC: slabs sized by the forward's capacity)
+    ns, handles = _side_streams(dev, v, n_streams)
+    g_color, g_depth, g_alpha = _cotangents(g_color, g_depth, g_alpha, (v, 3, d.H, d.W), dev)
+    out = _alloc_grads(d.N, cov3D, shs, colors, dev)
+    scratch = torch.empty(backward_scratch_bytes(d, v, ns, buf.cap), dtype=torch.uint8, device=dev)
+    p = _lib.ptr
+    args = [C.byref(d), v, p(means3D), p(cov3D), p(shs), p(colors), p(opacities), p(buf.bgs), p(buf.views), p(buf.fulls),
+            p(buf.campos), p(buf.tanfov), p(buf.scale), p(buf.geom), p(buf.binning), p(buf.image), p(buf.counters),
+            (C.c_size_t * 3)(*buf.sz[:3]), p(g_color), p(g_depth)] + ([] if g_alpha is None else [p(g_alpha)]) + [
+            p(scratch), p(out["means3D"]), p(out["means2D"]), p(out["cov3D"]), p(out["shs"]), p(out["colors"]),
+            p(out["opacities"]), 0, ns, handles, _lib.current_stream()]
+    name = "fs_raster_backward_views" + ("" if row_chunks is None else "_rows") + ("" if g_alpha is None else "_alpha")
+    if row_chunks is None:
+        _lib.check(getattr(_lib.lib(), name)(*args), name)
+    for ci, (c0, c1) in enumerate(row_chunks or ()):
+        _lib.check(getattr(_lib.lib(), name)(*args, c0, c1 - c0, 1 if ci == 0 else 0), name)
+        if chunk_ready is not None:
+            chunk_ready(c0, c1, out)
     return out
 
 
@@ -386,10 +483,13 @@ def debug_state(rs: RasterState) -> dict:
     """Copy the forward's internal state to host numpy arrays (test helper)."""
     import numpy as np
     d = rs.dims
+    L = _lib.lib()
     T = ((d.W + 15) // 16) * ((d.H + 15) // 16)
-    off_bytes = ((T + 1) * 4 + 255) // 256 * 256
+    # where the library keeps the parts of its buffers: its own accessors, as offsets from a buffer's first byte
+    b0, i0 = rs.binning.data_ptr(), rs.image.data_ptr()
+    off_ranges, off_bytes = L.fs_raster_tile_ranges(b0, d.H, d.W) - b0, L.fs_raster_point_list(b0, d.H, d.W) - b0
     binning = rs.binning.cpu().numpy()
-    offsets = binning[: (T + 1) * 4].view(np.uint32).copy()
+    offsets = binning[off_ranges: off_ranges + (T + 1) * 4].view(np.uint32).copy()
     I = int(offsets[-1])
     words = binning[off_bytes: off_bytes + I * 4].view(np.uint32).copy()
     point_list, quad = words >> 4, words & 15
@@ -402,8 +502,8 @@ def debug_state(rs: RasterState) -> dict:
     clamp = geom[o2: o2 + N].copy()
     P = d.H * d.W
     img = rs.image.cpu().numpy()
-    final_T = img[: P * 4].view(np.float32).reshape(d.H, d.W).copy()
-    o3 = (P * 4 + 255) // 256 * 256
+    oT, o3 = L.fs_raster_final_T(i0) - i0, L.fs_raster_n_contrib(i0, d.H, d.W) - i0
+    final_T = img[oT: oT + P * 4].view(np.float32).reshape(d.H, d.W).copy()
     n_contrib = img[o3: o3 + P * 4].view(np.int32).reshape(d.H, d.W).copy()
     return dict(offsets=offsets, point_list=point_list, quad=quad, rec=rec, rect=rect, clamp=clamp,
                 final_T=final_T, n_contrib=n_contrib, radii=rs.radii.cpu().numpy(),

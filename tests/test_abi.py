@@ -280,6 +280,158 @@ def test_ptf_entry_points_answer_the_recorded_statuses():
     assert n_calls == 331
 
 
+# ---------------------------------------------------------------------------------------------------- rasterizer statuses
+_R_IN = ["means3D", "cov3D", "shs", "colors_precomp", "opacities", "bg", "viewmatrix", "projmatrix", "campos", "tanfov", "scale",
+         "geom", "binning", "image"]
+_R_OUT = ["out_color", "out_depth", "out_alpha", "radii", "counters"]
+_R_GRADS = ["grad_scratch", "dL_dmeans3D", "dL_dmeans2D", "dL_dcov3D", "dL_dshs", "dL_dcolors", "dL_dopacities", "accumulate"]
+RASTER_ARGS = {"fs_raster_forward": ["dims"] + _R_IN + ["scratch", "cap"] + _R_OUT + ["stream"],
+               "fs_raster_forward_views": ["dims", "v"] + _R_IN + ["scratch", "strides", "cap"] + _R_OUT + ["n_streams", "streams", "stream"]}
+for _a in ("", "_alpha"):
+    _cot = ["dL_dcolor", "dL_ddepth"] + (["dL_dalpha"] if _a else [])
+    _views = ["dims", "v"] + _R_IN + ["counters", "strides"] + _cot + _R_GRADS + ["n_streams", "streams", "stream"]
+    RASTER_ARGS["fs_raster_backward" + _a] = ["dims"] + _R_IN + ["counters"] + _cot + _R_GRADS + ["stream"]
+    RASTER_ARGS["fs_raster_backward_views" + _a] = _views
+    RASTER_ARGS["fs_raster_backward_views_rows" + _a] = _views + ["row0", "nrows", "with_blend"]
+FWD = ("fs_raster_forward", "fs_raster_forward_views")
+BWD = tuple(n for n in RASTER_ARGS if "backward" in n)
+VIEWS = tuple(n for n in RASTER_ARGS if "views" in n)
+ROWS = tuple(n for n in RASTER_ARGS if "rows" in n)
+WHOLE = tuple(n for n in BWD if n not in ROWS)       # (the backwards without a row range)
+ALL = FWD + BWD
+# what a call is made of unless a row says otherwise: the SH form (colors_precomp / dL_dcolors NULL), 4 Gaussians, 9 coefficients of
+# degree 2, 40 x 56 pixels, 2 views, no side streams, rows [0, 2); every pointer a dummy that is never dereferenced
+RASTER_DIMS = dict(N=4, M=9, H=40, W=56, sh_degree=2, tanfovx=0.5, tanfovy=0.5, flags=0)
+RASTER_BASE = dict(colors_precomp=None, dL_dcolors=None, stream=None, streams=None, cap=1 << 20, v=2, n_streams=0, accumulate=0,
+                   row0=0, nrows=2, with_blend=1)
+RASTER_OPTIONAL = {"dims", "tanfov", "scale", "dL_ddepth", "dL_dalpha", "colors_precomp", "dL_dcolors", "stream", "streams", "strides"}
+NBS, DET, SR, CF = 32, 64, 128, 8       # FS_RASTER_NO_BACKWARD_STATE, _DETERMINISTIC, _SCALE_ROT, _COV_FULL
+P_ = "dummy"
+EACH, EVERY = "each required pointer NULL in turn", "every pointer but dims and strides NULL at once"
+# (entry points, dims fields, arguments, NULLed pointers, expected status).  Recorded from the library of the revision before the
+# host layer got its one argument check and one backward driver; rows that the recording answered with FS_ERR_LAUNCH (-2: they
+# reach a HIP call, which fails without a device) are not listed.
+RASTER_STATUS_TABLE = [
+    (ALL, {}, dict(dims=None), None, -1), (ALL, dict(N=-1), {}, None, -1), (WHOLE, dict(N=0), {}, None, 0), (WHOLE, dict(N=0), {}, EVERY, 0),
+    (BWD, dict(N=0, flags=NBS), {}, None, -1), (BWD, dict(N=0, flags=SR | CF), {}, None, -1), (BWD, dict(flags=NBS), {}, None, -1),
+    (BWD, dict(flags=NBS | DET), {}, EVERY, -1), (ALL, dict(flags=SR | CF), {}, None, -1), (ALL, dict(flags=SR | CF | NBS), {}, EVERY, -1),
+    (FWD, dict(H=0), {}, None, -1), (FWD, dict(H=-1), {}, None, -1), (FWD, dict(W=0), {}, None, -1), (FWD, dict(W=-5), {}, None, -1),
+    (FWD, {}, dict(cap=0), None, -1), (FWD, {}, dict(cap=-1), None, -1),
+    # the limits: 32767 tiles along a side, 2^28 Gaussians, 2^32 - 1 instances
+    (FWD, dict(W=16 * 32767 + 1), {}, None, -3), (FWD, dict(H=16 * 32767 + 1), {}, None, -3), (FWD, dict(N=(1 << 28) + 1), {}, None, -3),
+    (FWD, {}, dict(cap=1 << 32), None, -3), (FWD, dict(N=(1 << 28) + 1, H=0), {}, None, -1), (FWD, dict(W=16 * 32767 + 1), {}, EACH, -1),
+    # sh_degree against M (forward), M * 3 > 48 (backward); an invalid argument is answered before an unsupported one
+    (FWD, dict(sh_degree=3), {}, None, -3), (FWD, dict(sh_degree=4, M=25), {}, None, -3), (FWD, dict(sh_degree=-1), {}, None, -3),
+    (FWD, dict(sh_degree=3), {}, EACH, -1), (BWD, dict(M=17), {}, None, -3), (BWD, dict(M=17), {}, EACH, -1),
+    (BWD, dict(M=17, flags=NBS), {}, None, -1), (BWD, dict(M=17), dict(colors_precomp=P_), None, -1),
+    # shs and colors_precomp both / neither (EACH NULLs shs), a missing dL_dshs (EACH) / dL_dcolors
+    (ALL, {}, dict(colors_precomp=P_), None, -1), (BWD, {}, dict(colors_precomp=P_, dL_dcolors=P_), None, -1),
+    (BWD, {}, dict(shs=None, colors_precomp=P_), None, -1), (BWD, {}, dict(shs=None, colors_precomp=P_, dL_dshs=None), None, -1),
+    (ALL, {}, {}, EACH, -1), (ALL, {}, {}, EVERY, -1), (ALL, dict(flags=DET), {}, EACH, -1),
+    # the views forms: v, the side streams, the strides
+    (VIEWS, {}, dict(v=-1), None, -1), (VIEWS, {}, dict(v=0), None, 0), (VIEWS, {}, dict(v=0), EVERY, 0),
+    (VIEWS, {}, dict(v=0, strides=None), None, -1), (VIEWS, {}, dict(v=0, dims=None), None, -1), (VIEWS, {}, dict(strides=None), None, -1),
+    (VIEWS, dict(flags=NBS), dict(v=0), None, 0), (tuple(n for n in VIEWS if n not in ROWS), dict(N=-1), dict(v=0), None, 0), (ROWS, dict(N=-1), dict(v=0, nrows=0), None, -1),
+    (("fs_raster_forward_views",), dict(flags=SR | CF), dict(v=0), None, 0),
+    (tuple(n for n in VIEWS if n in BWD), dict(flags=SR | CF), dict(v=0), None, -1),
+    (VIEWS, {}, dict(n_streams=-1), None, -1), (VIEWS, {}, dict(n_streams=9, streams=P_), None, -1),
+    (VIEWS, {}, dict(n_streams=2), None, -1), (VIEWS, {}, dict(n_streams=1), None, -1), (VIEWS, {}, dict(v=0, n_streams=2), None, -1),
+    (VIEWS, {}, dict(n_streams=8, streams=P_), EACH, -1),
+    # the row range of the chunked per-Gaussian pass
+    (ROWS, {}, dict(row0=-1), None, -1), (ROWS, {}, dict(nrows=-1), None, -1), (ROWS, {}, dict(row0=3, nrows=2), None, -1),
+    (ROWS, {}, dict(row0=0, nrows=5), None, -1), (ROWS, {}, dict(row0=5, nrows=0), None, -1), (ROWS, {}, dict(v=0, row0=3, nrows=2), None, -1),
+    (ROWS, dict(N=0), dict(nrows=0), None, 0), (ROWS, dict(N=0), dict(nrows=0), EVERY, 0), (ROWS, dict(N=0), dict(nrows=1), None, -1), (ROWS, {}, dict(with_blend=0), EACH, -1),
+]
+# fs_raster_buffer_sizes (N, H, W, cap) -> status, out[4]; fs_raster_backward_scratch_bytes (N, H, W, flags, v, n_streams, cap);
+# fs_raster_scratch_slots (v, n_streams): recorded the same way
+RASTER_SIZE_TABLE = [
+    ((0, 1, 1, 0), 0, [768, 512, 512, 16640]), ((4, 40, 56, 100), 0, [768, 768, 17920, 196864]),
+    ((320, 40, 56, 1048576), 0, [18432, 4194560, 17920, 50331904]), ((1000, 17, 33, 64), 0, [57344, 512, 4608, 98560]),
+    ((1000000, 968, 1296, 8000000), 0, [57000192, 32019968, 10036224, 323833344]),
+    ((257, 3000, 2999, 268435456), 0, [15360, 1073883392, 71976448, 9265359104]), ((-1, 40, 56, 100), -1, None),
+    ((4, 0, 56, 100), -1, None), ((4, 40, -1, 100), -1, None), ((4, 40, 56, -1), -1, None),
+]
+RASTER_BWD_SCRATCH_TABLE = [
+    ((0, 40, 56, 0, 0, 0, 100), 0), ((0, 40, 56, 0, 3, 0, 100), 0), ((0, 40, 56, 0, 3, 2, 100), 0),
+    ((0, 40, 56, 0, 20, 9, 100), 0), ((0, 40, 56, 64, 0, 0, 100), 27648), ((0, 40, 56, 64, 3, 0, 100), 27648),
+    ((0, 40, 56, 64, 3, 2, 100), 55296), ((0, 40, 56, 64, 20, 9, 100), 221184), ((320, 40, 56, 0, 0, 0, 0), 15360),
+    ((320, 40, 56, 0, 0, 0, 100), 15360), ((320, 40, 56, 0, 0, 0, 1048576), 15360), ((320, 40, 56, 0, 3, 0, 0), 46080),
+    ((320, 40, 56, 0, 3, 0, 100), 46080), ((320, 40, 56, 0, 3, 0, 1048576), 46080), ((320, 40, 56, 0, 3, 2, 0), 46080),
+    ((320, 40, 56, 0, 3, 2, 100), 46080), ((320, 40, 56, 0, 3, 2, 1048576), 46080), ((320, 40, 56, 0, 20, 9, 0), 307200),
+    ((320, 40, 56, 0, 20, 9, 100), 307200), ((320, 40, 56, 0, 20, 9, 1048576), 307200), ((320, 40, 56, 64, 0, 0, 0), 30720),
+    ((320, 40, 56, 64, 0, 0, 100), 44288), ((320, 40, 56, 64, 0, 0, 1048576), 220742656), ((320, 40, 56, 64, 3, 0, 0), 61440),
+    ((320, 40, 56, 64, 3, 0, 100), 75008), ((320, 40, 56, 64, 3, 0, 1048576), 220773376), ((320, 40, 56, 64, 3, 2, 0), 76800),
+    ((320, 40, 56, 64, 3, 2, 100), 103936), ((320, 40, 56, 64, 3, 2, 1048576), 441500672),
+    ((320, 40, 56, 64, 20, 9, 0), 430080), ((320, 40, 56, 64, 20, 9, 100), 538624),
+    ((320, 40, 56, 64, 20, 9, 1048576), 1766125568), ((1000, 17, 33, 0, 0, 0, 100), 48000),
+    ((1000, 17, 33, 0, 0, 0, 1048576), 48000), ((1000, 17, 33, 0, 3, 0, 100), 144384),
+    ((1000, 17, 33, 0, 3, 0, 1048576), 144384), ((1000, 17, 33, 0, 3, 2, 100), 144384),
+    ((1000, 17, 33, 0, 3, 2, 1048576), 144384), ((1000, 17, 33, 0, 20, 9, 100), 962560),
+    ((1000, 17, 33, 0, 20, 9, 1048576), 962560), ((1000, 17, 33, 64, 0, 0, 100), 79616),
+    ((1000, 17, 33, 64, 0, 0, 1048576), 220777984), ((1000, 17, 33, 64, 3, 0, 100), 175872),
+    ((1000, 17, 33, 64, 3, 0, 1048576), 220874240), ((1000, 17, 33, 64, 3, 2, 100), 207360),
+    ((1000, 17, 33, 64, 3, 2, 1048576), 441604096), ((1000, 17, 33, 64, 20, 9, 100), 1214464),
+    ((1000, 17, 33, 64, 20, 9, 1048576), 1766801408), ((-1, 40, 56, 0, 1, 0, 100), 0), ((4, 0, 56, 0, 1, 0, 100), 0),
+    ((4, 40, 0, 64, 1, 0, 100), 0), ((4, 40, 56, 64, -1, 0, 100), 0), ((4, 40, 56, 64, 1, 0, -1), 0),
+    ((4, 40, 56, 64, 1, -1, 100), 27904),
+]
+RASTER_SLOTS_TABLE = [((-1, 0), -1), ((0, -1), -1), ((0, 0), 1), ((1, 0), 1), ((3, 2), 3), ((16, 0), 16), ((17, 8), 16), ((40, 2), 16)]
+
+
+def _raster_variants(name, dims_over, over, nulls):
+    """The argument lists of one RASTER_STATUS_TABLE row for one entry point (None: the row names an argument it lacks)."""
+    import ctypes as C
+    from freesplat_amd import _lib
+    names = RASTER_ARGS[name]
+    assert len(names) == len(_lib.SIGNATURES[name][1])
+    if any(k not in names for k in over):
+        return None
+    dims = _lib.RasterDims(**dict(RASTER_DIMS, **dims_over))
+    n_strides = 4 if "forward" in name else 3
+    base = dict(dims=C.byref(dims), strides=(C.c_size_t * n_strides)(*[1 << 20] * n_strides))
+    at = dict(zip(names, _lib.SIGNATURES[name][1]))
+    pointers = [k for k in names if at[k] in (C.c_void_p, C.POINTER(C.c_void_p))]
+    base.update({k: C.c_void_p(4096) for k in pointers})
+    base["streams"] = (C.c_void_p * 8)(*[4096] * 8)
+    base.update(RASTER_BASE)
+    for k, v in over.items():
+        base[k] = v if v != P_ else (C.c_void_p * 8)(*[4096] * 8) if k == "streams" else C.c_void_p(4096)
+    required = [k for k in pointers if k not in RASTER_OPTIONAL and k not in over and not (k == "counters" and name in BWD)]
+    if nulls == EACH:
+        sets = [[k] for k in required]
+    else:
+        sets = [[k for k in pointers if k not in over and k != "stream"]] if nulls == EVERY else [[]]
+    return [([None if k in drop else base[k] for k in names], (dims, base)) for drop in sets]
+
+
+def test_rasterizer_entry_points_answer_the_recorded_statuses():
+    """The rasterizer's eight int-returning entry points over RASTER_STATUS_TABLE (dims NULL, N negative / 0 / positive, the flag
+    combinations, the image / capacity / tile-grid / Gaussian-count limits, sh_degree against M, the colour pair, each required
+    pointer NULL in turn, v, the side streams, the row range) and its three size queries over a few argument tuples.  Recorded
+    from the revision before the host layer got one argument check and one backward driver and holds for both; no row reaches
+    a launch, so no device is involved."""
+    import ctypes as C
+    from freesplat_amd import _lib
+    L = _lib.lib()
+    n_calls = 0
+    for names, dims_over, over, nulls, want in RASTER_STATUS_TABLE:
+        for name in names:
+            for args, _alive in _raster_variants(name, dims_over, over, nulls) or ():
+                assert getattr(L, name)(*args) == want, (name, dims_over, over, nulls, [i for i, a in enumerate(args) if a is None])
+                n_calls += 1
+    assert n_calls == 817
+    out = (C.c_size_t * 4)()
+    for args, status, sizes in RASTER_SIZE_TABLE:
+        assert L.fs_raster_buffer_sizes(*args, out) == status and (status != 0 or list(out) == sizes), args
+    assert L.fs_raster_buffer_sizes(4, 40, 56, 100, None) == -1
+    for (N, H, W, flags, v, ns, cap), want in RASTER_BWD_SCRATCH_TABLE:
+        d = _lib.RasterDims(**dict(RASTER_DIMS, N=N, H=H, W=W, flags=flags))
+        assert L.fs_raster_backward_scratch_bytes(C.byref(d), v, ns, cap) == want, (N, H, W, flags, v, ns, cap)
+    assert L.fs_raster_backward_scratch_bytes(None, 1, 0, 100) == 0
+    for args, want in RASTER_SLOTS_TABLE:
+        assert L.fs_raster_scratch_slots(*args) == want, args
+
+
 def test_every_entry_point_validates_its_arguments_before_touching_a_device():
     """Error behaviour of the boundary, checked without a GPU: every int-returning entry point called with NULL pointers
     answers FS_ERR_INVALID_ARG (-1) when its sizes are positive, and -1 or FS_OK (an empty job) when they are zero --
@@ -359,6 +511,60 @@ def test_overflow_capacity_is_per_image_size_and_decays():
     st.note_overflow(5_000_000, 50_000, H, W)
     st.retry_cap = 0                                                       # (bench / tests reset the history)
     assert R.default_capacity(N, st, H, W) == base
+
+
+def test_capacity_verdict_keeps_the_three_update_rules():
+    """Host logic of rasterizer.capacity_verdict, the one reading of the instance-capacity counters (no GPU: the counter pairs are
+    lists).  Expected values follow the three code paths it replaced: a single view ASSIGNS last_instances its count,
+    render_views assigns the MAXIMUM over its views, the deferred check never lowers it and withholds note_fit from every pending
+    call after the first overflowed one; an overflowed view is to be re-rendered with retry_capacity of its own counters, never
+    less than the history already asks for; counters are int32 bit patterns of unsigned values."""
+    import torch
+    from freesplat_amd import decoder as D, rasterizer as R
+    H, W, T = 40, 56, 12
+    key = (H, W)
+    st = R._DeviceState()
+    st.last_instances, st.retry_caps[key] = 9_000_000, 4_000_000
+    # a single view that fits: assigned (here: lowered), and the overflow-derived capacity decays
+    assert R.capacity_verdict(st, [[5000, 0]], H, W) == ([5000], {}) and st.last_instances == 5000 and st.retry_caps[key] == 3_600_000
+    # three views that fit: the maximum, another decay step
+    assert R.capacity_verdict(st, [[100, 0], [7000, 0], [300, 0]], H, W) == ([100, 7000, 300], {})
+    assert st.last_instances == 7000 and st.retry_caps[key] == 3_240_000
+    # views 1 and 2 overflowed: each gets the capacity the history asks for after its own overflow, nothing decays
+    want1 = max(5_000_000 + 1024, (4000 * T + 3) // 4 + 1)
+    want2 = max(300 + 1024, (3_000_000 * T + 3) // 4 + 1)
+    assert want1 == R.retry_capacity(5_000_000, 4000, H, W) == 5_001_024 and want2 == R.retry_capacity(300, 3_000_000, H, W) == 9_000_001
+    counts, redo = R.capacity_verdict(st, [[100, 0], [5_000_000, 4000], [300, 3_000_000]], H, W)
+    assert counts == [100, 5_000_000, 300] and redo == {1: want1, 2: want2} and st.last_instances == 5_000_000 and st.retry_caps[key] == want2
+    assert R.capacity_verdict(st, [[50, 7]], H, W) == ([50], {0: want2}) and st.last_instances == 50     # (a smaller overflow never shrinks it)
+    # int32 bit patterns: -1 is 2^32 - 1 instances, a negative tile count an overflow
+    st = R._DeviceState()
+    counts, redo = R.capacity_verdict(st, [[-1, -2147483648]], H, W)
+    assert counts == [0xFFFFFFFF] and redo == {0: (0x80000000 * T + 3) // 4 + 1} and st.last_instances == 0xFFFFFFFF
+    assert R.capacity_verdict(R._DeviceState(), [], H, W) == ([], {})
+    # the deferred rules: never lowered; a call after an overflowed one does not count as a fit
+    st = R._DeviceState()
+    st.last_instances, st.retry_caps[key] = 9_000_000, 4_000_000
+    assert R.capacity_verdict(st, [[10, 0], [20, 0]], H, W, lower=False) == ([10, 20], {}) and st.last_instances == 9_000_000
+    assert st.retry_caps[key] == 3_600_000
+    assert R.capacity_verdict(st, [[9_500_000, 0]], H, W, lower=False, may_fit=False) == ([9_500_000], {})
+    assert st.last_instances == 9_500_000 and st.retry_caps[key] == 3_600_000
+    # ... and decoder.check_deferred over three pending calls (fits / one view overflows / fits), on host tensors
+    dev = torch.device("cuda", 63)
+    st = R._states[63] = R._DeviceState()
+    try:
+        st.last_instances, st.retry_caps[key] = 9_000_000, 4_000_000
+        states = [R.RasterState(*[None] * 13) for _ in range(2)]
+        i32 = lambda rows: torch.tensor(rows, dtype=torch.int32)
+        D._pending_checks[:] = [(i32([[10, 0], [20, 0]]), states, dev, key), (i32([[3_000_000, 5000], [30, 0]]), None, dev, key),
+                                (i32([[40, 0]]), None, dev, key)]
+        with pytest.raises(R._lib.FreeSplatHipError, match="1 deferred view"):
+            D.check_deferred()
+        assert not D._pending_checks and [rs.num_rendered for rs in states] == [10, 20]
+        assert st.last_instances == 9_000_000 and st.retry_caps == {key: 3_600_000}       # one decay (the first call), then withheld
+    finally:
+        del R._states[63]
+        D._pending_checks.clear()
 
 
 def test_traffic_lookup_refuses_kernels_the_library_no_longer_contains():

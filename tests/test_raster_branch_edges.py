@@ -14,8 +14,6 @@ bit-equal) and differ in the order of the sums.  The same bound holds against th
 one convention of the original wrong for the Gaussians it touches the metric reads 5e-3 - 1
 (test_raster_oracle.py::test_edge_scene_and_metric_see_each_convention).
 """
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
@@ -186,51 +184,24 @@ def _views_cov(dev, scene, cams, cot):
 
 
 def _views_scale_rot(dev, scene, cams, rows7, cot):
-    """fs_raster_forward_views + fs_raster_backward_views with FS_RASTER_SCALE_ROT rows [N,7] and shs [N,M,3], launched as
-    decoder._RenderViews launches the 3x3 form (render_views itself has no (scales, rotations) argument)."""
-    from freesplat_amd import _lib, rasterizer as R
+    """rasterizer.rasterize_forward_views + rasterize_backward_views with FS_RASTER_SCALE_ROT rows [N,7] and shs [N,M,3], the
+    launches decoder._RenderViews makes for the 3x3 form (render_views itself has no (scales, rotations) argument)."""
+    from freesplat_amd import rasterizer as R
     from freesplat_amd.decoder import frame_views
     d = lambda t: t.to(dev).contiguous()
     means, rows7, opac = d(scene["means"]), d(rows7), d(scene["opacities"])
     shs = d(scene["harmonics"].transpose(1, 2))
     campos, scale, tanfov, view, full = frame_views(d(cams["extrinsics"]), d(cams["intrinsics"]), d(cams["near"]), d(cams["far"]))
-    v, M = 3, shs.shape[1]
-    bgs = torch.full((v, 3), 0.2, device=dev)
-    st = R._state(dev)
-    cap = R.default_capacity(N, st, H, W)
     s0 = R.GaussianRasterizationSettings(H, W, 0.0, 0.0, None, 1.0, None, None, 2, None, False, False)
-    dims = R.make_dims(N, M, s0, scale_rot=True)
-    n_streams = min(R.NUM_STREAMS, v)
-    while len(st.side_streams) < n_streams:
-        st.side_streams.append(torch.cuda.Stream(device=dev))
-    ns = n_streams if n_streams > 1 else 0
-    sz = R._buffer_sizes(N, H, W, cap)
-    u8 = lambda n: torch.empty(n, dtype=torch.uint8, device=dev)
-    f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
-    geom, binning, image = u8(v * sz[0]), u8(v * sz[1]), u8(v * sz[2])
-    scratch = u8(max(_lib.lib().fs_raster_scratch_slots(v, ns), 1) * sz[3])
-    color, depth, alpha = f32(v, 3, H, W), f32(v, H, W), f32(v, H, W)
-    radii = torch.empty(v, N, dtype=torch.int32, device=dev)
-    counters = torch.empty(v, 2, dtype=torch.int32, device=dev)
-    handles = (C.c_void_p * max(n_streams, 1))(*[s.cuda_stream for s in st.side_streams[:n_streams]])
-    p = _lib.ptr
-    _lib.check(_lib.lib().fs_raster_forward_views(
-        C.byref(dims), v, p(means), p(rows7), p(shs), None, p(opac), p(bgs), p(view), p(full), p(campos), p(tanfov), p(scale),
-        p(geom), p(binning), p(image), p(scratch), (C.c_size_t * 4)(*sz), cap, p(color), p(depth), p(alpha), p(radii),
-        p(counters), ns, handles, _lib.current_stream()), "fs_raster_forward_views")
-    assert not any(o for _, o in counters.tolist()), "instance capacity overflow"
-    g_color, g_depth = torch.from_numpy(cot[0]).to(dev), torch.from_numpy(cot[1]).to(dev)
-    out = dict(means3D=f32(N, 3), means2D=f32(N, 3), cov3D=f32(N, 7), shs=f32(N, M, 3), opacities=f32(N))
-    bdims = R.backward_dims(dims)
-    bscratch = u8(R.backward_scratch_bytes(bdims, v, ns, cap))
-    _lib.check(_lib.lib().fs_raster_backward_views(
-        C.byref(bdims), v, p(means), p(rows7), p(shs), None, p(opac), p(bgs), p(view), p(full), p(campos), p(tanfov), p(scale),
-        p(geom), p(binning), p(image), p(counters), (C.c_size_t * 3)(*sz[:3]), p(g_color), p(g_depth), p(bscratch),
-        p(out["means3D"]), p(out["means2D"]), p(out["cov3D"]), p(out["shs"]), None, p(out["opacities"]), 0, ns, handles,
-        _lib.current_stream()), "fs_raster_backward_views")
+    dims = R.make_dims(N, shs.shape[1], s0, scale_rot=True)
+    buf, _, _, _ = R.rasterize_forward_views(dims, means, rows7, shs, None, opac, torch.full((3, 3), 0.2, device=dev), view, full,
+                                             campos, tanfov, scale, R.default_capacity(N, R._state(dev), H, W))
+    assert not any(o for _, o in buf.counters.tolist()), "instance capacity overflow"
+    out = R.rasterize_backward_views(buf, means, rows7, shs, None, opac, torch.from_numpy(cot[0]).to(dev),
+                                     torch.from_numpy(cot[1]).to(dev))
     torch.cuda.synchronize()
     return dict(means=out["means3D"], scales=out["cov3D"][:, :3], rotations=out["cov3D"][:, 3:],
-                harmonics=out["shs"].transpose(1, 2), opacities=out["opacities"], radii=radii)
+                harmonics=out["shs"].transpose(1, 2), opacities=out["opacities"], radii=buf.radii)
 
 
 _VIEW_NAMES = dict(cov3D=[("means3D", "means"), ("cov3D", "covariances"), ("opacities", "opacities"), ("colour", "harmonics")],

@@ -279,28 +279,14 @@ def test_combined_loss_is_the_sum_of_the_separate_backwards(hip_device, form):
 
 
 def _views_call(color, dims, g_color, g_alpha, n_streams):
-    """fs_raster_backward_views_alpha on the buffers a render_views forward left behind (its autograd node's batch)."""
+    """rasterizer.rasterize_backward_views (fs_raster_backward_views_alpha; fs_raster_backward_views without g_alpha) on the
+    buffers a render_views forward left behind (its autograd node's batch)."""
     from freesplat_amd import rasterizer as R
     ctx = color.grad_fn
-    b = ctx.batch
     means, cov6, shs, opac = ctx.saved_tensors
-    v, N, dev = len(ctx.states), means.shape[0], means.device
-    st = R._state(dev)
-    while len(st.side_streams) < n_streams:
-        st.side_streams.append(torch.cuda.Stream(device=dev))
-    f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
-    out = dict(means3D=f32(N, 3), means2D=f32(N, 3), cov3D=f32(*cov6.shape), shs=f32(*shs.shape), opacities=f32(N))
-    scratch = torch.empty(R.backward_scratch_bytes(dims, v, n_streams if n_streams > 1 else 0, b["cap"]), dtype=torch.uint8,
-                          device=dev)
-    strides = (C.c_size_t * 3)(*b["sz"][:3])
-    handles = (C.c_void_p * max(n_streams, 1))(*[s.cuda_stream for s in st.side_streams[:n_streams]])
-    p = _lib.ptr
-    _lib.check(_lib.lib().fs_raster_backward_views_alpha(
-        C.byref(dims), v, p(means), p(cov6), p(shs), None, p(opac), p(b["bgs"]), p(b["views"]), p(b["fulls"]), p(b["campos"]),
-        p(b["tanfov"]), p(b["scale"]), p(b["geom"]), p(b["binning"]), p(b["image"]), p(b["counters"]), strides, p(g_color), None,
-        p(g_alpha), p(scratch), p(out["means3D"]), p(out["means2D"]), p(out["cov3D"]), p(out["shs"]), None, p(out["opacities"]), 0,
-        n_streams if n_streams > 1 else 0, handles, _lib.current_stream()), "fs_raster_backward_views_alpha")
-    return out
+    out = R.rasterize_backward_views(ctx.batch, means, cov6, shs, None, opac, g_color, None, g_alpha=g_alpha, n_streams=n_streams,
+                                     dims=dims)
+    return {k: t for k, t in out.items() if t is not None}
 
 
 def _views_setup(dev, seed):
@@ -323,7 +309,7 @@ def test_views_alpha_equals_the_single_view_backwards_summed(hip_device):
     color, g_color, g_alpha = _views_setup(hip_device, 51)
     ctx = color.grad_fn
     means, cov6, shs, opac = ctx.saved_tensors
-    got = _views_call(color, ctx.batch["dims"], g_color, g_alpha, 2)
+    got = _views_call(color, ctx.batch.dims, g_color, g_alpha, 2)
     want = None
     for i, rs in enumerate(ctx.states):
         want = R.rasterize_backward(rs, means, cov6, shs, None, opac, g_color[i], None, out=want, accumulate=i > 0,
@@ -332,7 +318,7 @@ def test_views_alpha_equals_the_single_view_backwards_summed(hip_device):
         err = float((got[k] - want[k]).abs().max()) / (float(want[k].abs().max()) + 1e-30)
         assert err < 1e-5, f"{k}: {err:.3e} of max-abs"
     # and the alpha term changed something: the same call without it differs
-    plain = _views_call(color, ctx.batch["dims"], g_color, None, 2)
+    plain = _views_call(color, ctx.batch.dims, g_color, None, 2)
     assert not torch.equal(plain["opacities"], got["opacities"])
 
 
@@ -342,7 +328,7 @@ def test_deterministic_mode_repeats_both_paths_bitwise(hip_device, monkeypatch):
     monkeypatch.setattr(R, "DETERMINISTIC", True)
     # alpha through the views entry point: two runs, one and two streams
     color, g_color, g_alpha = _views_setup(hip_device, 52)
-    dims = R.backward_dims(color.grad_fn.batch["dims"])
+    dims = R.backward_dims(color.grad_fn.batch.dims)
     runs = [_views_call(color, dims, g_color, g_alpha, ns) for ns in (2, 2, 1)]
     for r in runs[1:]:
         for k in r:
