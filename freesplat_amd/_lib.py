@@ -1,5 +1,5 @@
 """ctypes binding of libfreesplat_hip.so (C ABI: include/freesplat_amd.h, include/freesplat_amd_loss.h,
-include/freesplat_amd_optim.h).
+include/freesplat_amd_optim.h, include/freesplat_amd_density.h, include/freesplat_amd_depthloss.h).
 
 The product path has NO fallback: if the HIP library is missing or a call fails this module
 raises.  `build()` compiles the library in-tree with hipcc for gfx950.
@@ -30,6 +30,7 @@ ABI_VERSION = 9          # include/freesplat_amd.h FS_ABI_VERSION
 LOSS_API_VERSION = 1     # include/freesplat_amd_loss.h FS_LOSS_API_VERSION
 OPTIM_API_VERSION = 1    # include/freesplat_amd_optim.h FS_OPTIM_API_VERSION
 DENSITY_API_VERSION = 1  # include/freesplat_amd_density.h FS_DENSITY_API_VERSION
+DEPTHLOSS_API_VERSION = 1  # include/freesplat_amd_depthloss.h FS_DEPTHLOSS_API_VERSION
 
 RASTER_TILE_CULL = 1
 RASTER_SH_FP16 = 2
@@ -42,6 +43,10 @@ RASTER_SCALE_ROT = 128
 
 SSIM_SKIMAGE = 1
 SSIM_3DGS = 2
+
+DEPTH_LOSS_LOG_L1 = 1
+DEPTH_LOSS_L1 = 2
+DEPTH_LOSS_MAX_SCALES = 6
 
 
 def build(force: bool = False) -> str:
@@ -192,6 +197,15 @@ DENSITY_SIGNATURES = {
     "fs_density_reset_opacity": (C.c_int, [C.c_int32, C.c_double] + [_VP] * 5),
 }
 
+# name -> (restype, argtypes); must list every symbol include/freesplat_amd_depthloss.h declares (a fifth header, a fifth table)
+DEPTHLOSS_SIGNATURES = {
+    "fs_depthloss_api_version": (C.c_int, []),
+    "fs_depth_loss_saved_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "fs_depth_loss_scratch_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "fs_depth_loss_forward": (C.c_int, [C.c_int32] * 5 + [_VP] * 3 + [C.c_float] * 3 + [_VP] * 7),
+    "fs_depth_loss_backward": (C.c_int, [C.c_int32] * 5 + [_VP] * 3 + [C.c_float] * 3 + [_VP] * 7),
+}
+
 
 def lib():
     global _lib
@@ -206,7 +220,7 @@ def lib():
         # device is detected"
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
-        for table in (SIGNATURES, LOSS_SIGNATURES, OPTIM_SIGNATURES, DENSITY_SIGNATURES):
+        for table in (SIGNATURES, LOSS_SIGNATURES, OPTIM_SIGNATURES, DENSITY_SIGNATURES, DEPTHLOSS_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)  # AttributeError if the library lacks a declared symbol
                 fn.restype = res
@@ -223,6 +237,9 @@ def lib():
         if L.fs_density_api_version() != DENSITY_API_VERSION:
             raise FreeSplatHipError(f"{LIB_PATH} has density API revision {L.fs_density_api_version()}, this binding expects "
                                     f"{DENSITY_API_VERSION} (include/freesplat_amd_density.h FS_DENSITY_API_VERSION): rebuild the library")
+        if L.fs_depthloss_api_version() != DEPTHLOSS_API_VERSION:
+            raise FreeSplatHipError(f"{LIB_PATH} has depth-loss API revision {L.fs_depthloss_api_version()}, this binding expects "
+                                    f"{DEPTHLOSS_API_VERSION} (include/freesplat_amd_depthloss.h FS_DEPTHLOSS_API_VERSION): rebuild the library")
         _lib = L
     return _lib
 
