@@ -7,6 +7,7 @@ include/freesplat_amd.h), and the host-side mirrors of the reference's operator 
   decoder.py      frame_views / render_cuda / render_views / DecoderSplattingCUDA (src/model/decoder/)
   metrics.py      compute_ssim / compute_psnr / depth_render_metrics on the device (src/evaluation/metrics.py)
   ssim_loss.py    differentiable SSIM and the (1 - lambda) L1 + lambda (1 - SSIM) photometric loss (no reference counterpart)
+  normals_loss.py depth -> surface normals and the cosine normals loss (src/loss/losses.py NormalsLoss, restated)
   compat/         importable `diff_gaussian_rasterization_depth` module for an unmodified reference tree
 
 There is no CPU or eager fallback: the ops raise if libfreesplat_hip.so is missing.

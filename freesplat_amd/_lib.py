@@ -1,5 +1,6 @@
 """ctypes binding of libfreesplat_hip.so (C ABI: include/freesplat_amd.h, include/freesplat_amd_loss.h,
-include/freesplat_amd_optim.h, include/freesplat_amd_density.h, include/freesplat_amd_depthloss.h).
+include/freesplat_amd_optim.h, include/freesplat_amd_density.h, include/freesplat_amd_depthloss.h,
+include/freesplat_amd_normals.h).
 
 The product path has NO fallback: if the HIP library is missing or a call fails this module
 raises.  `build()` compiles the library in-tree with hipcc for gfx950.
@@ -31,6 +32,7 @@ LOSS_API_VERSION = 1     # include/freesplat_amd_loss.h FS_LOSS_API_VERSION
 OPTIM_API_VERSION = 1    # include/freesplat_amd_optim.h FS_OPTIM_API_VERSION
 DENSITY_API_VERSION = 1  # include/freesplat_amd_density.h FS_DENSITY_API_VERSION
 DEPTHLOSS_API_VERSION = 1  # include/freesplat_amd_depthloss.h FS_DEPTHLOSS_API_VERSION
+NORMALS_API_VERSION = 1  # include/freesplat_amd_normals.h FS_NORMALS_API_VERSION
 
 RASTER_TILE_CULL = 1
 RASTER_SH_FP16 = 2
@@ -206,6 +208,16 @@ DEPTHLOSS_SIGNATURES = {
     "fs_depth_loss_backward": (C.c_int, [C.c_int32] * 5 + [_VP] * 3 + [C.c_float] * 3 + [_VP] * 7),
 }
 
+# name -> (restype, argtypes); must list every symbol include/freesplat_amd_normals.h declares (a sixth header, a sixth table)
+NORMALS_SIGNATURES = {
+    "fs_normals_api_version": (C.c_int, []),
+    "fs_normals_scratch_bytes": (C.c_size_t, [C.c_int32] * 3),
+    "fs_depth_normals_forward": (C.c_int, [C.c_int32] * 3 + [_VP] * 3 + [C.c_float] * 4 + [_VP] * 2),
+    "fs_depth_normals_backward": (C.c_int, [C.c_int32] * 3 + [_VP] * 3 + [C.c_float] * 4 + [_VP] * 4),
+    "fs_normals_loss_forward": (C.c_int, [C.c_int32] * 3 + [_VP] * 5 + [C.c_float] * 4 + [_VP] * 4),
+    "fs_normals_loss_backward": (C.c_int, [C.c_int32] * 3 + [_VP] * 5 + [C.c_float] * 4 + [_VP] * 4),
+}
+
 
 def lib():
     global _lib
@@ -220,7 +232,8 @@ def lib():
         # device is detected"
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
-        for table in (SIGNATURES, LOSS_SIGNATURES, OPTIM_SIGNATURES, DENSITY_SIGNATURES, DEPTHLOSS_SIGNATURES):
+        for table in (SIGNATURES, LOSS_SIGNATURES, OPTIM_SIGNATURES, DENSITY_SIGNATURES, DEPTHLOSS_SIGNATURES,
+                      NORMALS_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)  # AttributeError if the library lacks a declared symbol
                 fn.restype = res
@@ -240,6 +253,9 @@ def lib():
         if L.fs_depthloss_api_version() != DEPTHLOSS_API_VERSION:
             raise FreeSplatHipError(f"{LIB_PATH} has depth-loss API revision {L.fs_depthloss_api_version()}, this binding expects "
                                     f"{DEPTHLOSS_API_VERSION} (include/freesplat_amd_depthloss.h FS_DEPTHLOSS_API_VERSION): rebuild the library")
+        if L.fs_normals_api_version() != NORMALS_API_VERSION:
+            raise FreeSplatHipError(f"{LIB_PATH} has normals API revision {L.fs_normals_api_version()}, this binding expects "
+                                    f"{NORMALS_API_VERSION} (include/freesplat_amd_normals.h FS_NORMALS_API_VERSION): rebuild the library")
         _lib = L
     return _lib
 
