@@ -8,8 +8,20 @@ include/freesplat_amd.h), and the host-side mirrors of the reference's operator 
   metrics.py      compute_ssim / compute_psnr / depth_render_metrics on the device (src/evaluation/metrics.py)
   ssim_loss.py    differentiable SSIM and the (1 - lambda) L1 + lambda (1 - SSIM) photometric loss (no reference counterpart)
   normals_loss.py depth -> surface normals and the cosine normals loss (src/loss/losses.py NormalsLoss, restated)
+  exposure.py     per-view affine exposure compensation: apply_exposure, fit_exposure, color_corrected, Exposure (no reference
+                  counterpart; exported here)
   compat/         importable `diff_gaussian_rasterization_depth` module for an unmodified reference tree
 
 There is no CPU or eager fallback: the ops raise if libfreesplat_hip.so is missing.
 """
 __version__ = "0.1.0"
+
+_EXPOSURE = ("apply_exposure", "fit_exposure", "color_corrected", "Exposure")
+
+
+def __getattr__(name):
+    # resolved on first use: importing the package itself stays free of torch
+    if name in _EXPOSURE:
+        from . import exposure
+        return getattr(exposure, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1,6 +1,6 @@
 """ctypes binding of libfreesplat_hip.so (C ABI: include/freesplat_amd.h, include/freesplat_amd_loss.h,
 include/freesplat_amd_optim.h, include/freesplat_amd_density.h, include/freesplat_amd_depthloss.h,
-include/freesplat_amd_normals.h).
+include/freesplat_amd_normals.h, include/freesplat_amd_exposure.h).
 
 The product path has NO fallback: if the HIP library is missing or a call fails this module
 raises.  `build()` compiles the library in-tree with hipcc for gfx950.
@@ -33,6 +33,7 @@ OPTIM_API_VERSION = 1    # include/freesplat_amd_optim.h FS_OPTIM_API_VERSION
 DENSITY_API_VERSION = 1  # include/freesplat_amd_density.h FS_DENSITY_API_VERSION
 DEPTHLOSS_API_VERSION = 1  # include/freesplat_amd_depthloss.h FS_DEPTHLOSS_API_VERSION
 NORMALS_API_VERSION = 1  # include/freesplat_amd_normals.h FS_NORMALS_API_VERSION
+EXPOSURE_API_VERSION = 1  # include/freesplat_amd_exposure.h FS_EXPOSURE_API_VERSION
 
 RASTER_TILE_CULL = 1
 RASTER_SH_FP16 = 2
@@ -218,6 +219,15 @@ NORMALS_SIGNATURES = {
     "fs_normals_loss_backward": (C.c_int, [C.c_int32] * 3 + [_VP] * 5 + [C.c_float] * 4 + [_VP] * 4),
 }
 
+# name -> (restype, argtypes); must list every symbol include/freesplat_amd_exposure.h declares (a seventh header, a seventh table)
+EXPOSURE_SIGNATURES = {
+    "fs_exposure_api_version": (C.c_int, []),
+    "fs_exposure_scratch_bytes": (C.c_size_t, [C.c_int32] * 3),
+    "fs_exposure_apply_forward": (C.c_int, [C.c_int32] * 4 + [_VP] * 5),
+    "fs_exposure_apply_backward": (C.c_int, [C.c_int32] * 4 + [_VP] * 8),
+    "fs_exposure_fit": (C.c_int, [C.c_int32] * 4 + [_VP] * 4 + [C.c_double] + [_VP] * 5),
+}
+
 
 def lib():
     global _lib
@@ -233,7 +243,7 @@ def lib():
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
         for table in (SIGNATURES, LOSS_SIGNATURES, OPTIM_SIGNATURES, DENSITY_SIGNATURES, DEPTHLOSS_SIGNATURES,
-                      NORMALS_SIGNATURES):
+                      NORMALS_SIGNATURES, EXPOSURE_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)  # AttributeError if the library lacks a declared symbol
                 fn.restype = res
@@ -256,6 +266,9 @@ def lib():
         if L.fs_normals_api_version() != NORMALS_API_VERSION:
             raise FreeSplatHipError(f"{LIB_PATH} has normals API revision {L.fs_normals_api_version()}, this binding expects "
                                     f"{NORMALS_API_VERSION} (include/freesplat_amd_normals.h FS_NORMALS_API_VERSION): rebuild the library")
+        if L.fs_exposure_api_version() != EXPOSURE_API_VERSION:
+            raise FreeSplatHipError(f"{LIB_PATH} has exposure API revision {L.fs_exposure_api_version()}, this binding expects "
+                                    f"{EXPOSURE_API_VERSION} (include/freesplat_amd_exposure.h FS_EXPOSURE_API_VERSION): rebuild the library")
         _lib = L
     return _lib
 
