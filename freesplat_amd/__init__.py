@@ -8,6 +8,8 @@ include/freesplat_amd.h), and the host-side mirrors of the reference's operator 
   metrics.py      compute_ssim / compute_psnr / depth_render_metrics on the device (src/evaluation/metrics.py)
   ssim_loss.py    differentiable SSIM and the (1 - lambda) L1 + lambda (1 - SSIM) photometric loss (no reference counterpart)
   normals_loss.py depth -> surface normals and the cosine normals loss (src/loss/losses.py NormalsLoss, restated)
+  mv_depth_loss.py multi-view depth consistency and scale-invariant depth losses (src/loss/losses.py MVDepthLoss and
+                  ScaleInvariantLoss, restated)
   exposure.py     per-view affine exposure compensation: apply_exposure, fit_exposure, color_corrected, Exposure (no reference
                   counterpart; exported here)
   compat/         importable `diff_gaussian_rasterization_depth` module for an unmodified reference tree

@@ -1,6 +1,6 @@
 """ctypes binding of libfreesplat_hip.so (C ABI: include/freesplat_amd.h, include/freesplat_amd_loss.h,
 include/freesplat_amd_optim.h, include/freesplat_amd_density.h, include/freesplat_amd_depthloss.h,
-include/freesplat_amd_normals.h, include/freesplat_amd_exposure.h).
+include/freesplat_amd_normals.h, include/freesplat_amd_exposure.h, include/freesplat_amd_mvdepth.h).
 
 The product path has NO fallback: if the HIP library is missing or a call fails this module
 raises.  `build()` compiles the library in-tree with hipcc for gfx950.
@@ -34,6 +34,7 @@ DENSITY_API_VERSION = 1  # include/freesplat_amd_density.h FS_DENSITY_API_VERSIO
 DEPTHLOSS_API_VERSION = 1  # include/freesplat_amd_depthloss.h FS_DEPTHLOSS_API_VERSION
 NORMALS_API_VERSION = 1  # include/freesplat_amd_normals.h FS_NORMALS_API_VERSION
 EXPOSURE_API_VERSION = 1  # include/freesplat_amd_exposure.h FS_EXPOSURE_API_VERSION
+MVDEPTH_API_VERSION = 1  # include/freesplat_amd_mvdepth.h FS_MVDEPTH_API_VERSION
 
 RASTER_TILE_CULL = 1
 RASTER_SH_FP16 = 2
@@ -50,6 +51,8 @@ SSIM_3DGS = 2
 DEPTH_LOSS_LOG_L1 = 1
 DEPTH_LOSS_L1 = 2
 DEPTH_LOSS_MAX_SCALES = 6
+
+MVDEPTH_MAX_SOURCES = 16
 
 
 def build(force: bool = False) -> str:
@@ -228,6 +231,16 @@ EXPOSURE_SIGNATURES = {
     "fs_exposure_fit": (C.c_int, [C.c_int32] * 4 + [_VP] * 4 + [C.c_double] + [_VP] * 5),
 }
 
+# name -> (restype, argtypes); must list every symbol include/freesplat_amd_mvdepth.h declares (an eighth header, an eighth table)
+MVDEPTH_SIGNATURES = {
+    "fs_mvdepth_api_version": (C.c_int, []),
+    "fs_mvdepth_scratch_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "fs_mv_depth_forward": (C.c_int, [C.c_int32] * 7 + [_VP] * 6 + [C.c_float] * 4 + [_VP] * 5),
+    "fs_mv_depth_backward": (C.c_int, [C.c_int32] * 7 + [_VP] * 6 + [C.c_float] * 4 + [_VP] * 4),
+    "fs_si_depth_forward": (C.c_int, [C.c_int32] * 3 + [_VP] * 3 + [C.c_float] * 3 + [_VP] * 5),
+    "fs_si_depth_backward": (C.c_int, [C.c_int32] * 3 + [_VP] * 3 + [C.c_float] * 3 + [_VP] * 5),
+}
+
 
 def lib():
     global _lib
@@ -243,7 +256,7 @@ def lib():
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
         for table in (SIGNATURES, LOSS_SIGNATURES, OPTIM_SIGNATURES, DENSITY_SIGNATURES, DEPTHLOSS_SIGNATURES,
-                      NORMALS_SIGNATURES, EXPOSURE_SIGNATURES):
+                      NORMALS_SIGNATURES, EXPOSURE_SIGNATURES, MVDEPTH_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)  # AttributeError if the library lacks a declared symbol
                 fn.restype = res
@@ -269,6 +282,9 @@ def lib():
         if L.fs_exposure_api_version() != EXPOSURE_API_VERSION:
             raise FreeSplatHipError(f"{LIB_PATH} has exposure API revision {L.fs_exposure_api_version()}, this binding expects "
                                     f"{EXPOSURE_API_VERSION} (include/freesplat_amd_exposure.h FS_EXPOSURE_API_VERSION): rebuild the library")
+        if L.fs_mvdepth_api_version() != MVDEPTH_API_VERSION:
+            raise FreeSplatHipError(f"{LIB_PATH} has multi-view depth API revision {L.fs_mvdepth_api_version()}, this binding expects "
+                                    f"{MVDEPTH_API_VERSION} (include/freesplat_amd_mvdepth.h FS_MVDEPTH_API_VERSION): rebuild the library")
         _lib = L
     return _lib
 
