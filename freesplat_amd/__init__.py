@@ -12,6 +12,9 @@ include/freesplat_amd.h), and the host-side mirrors of the reference's operator 
                   ScaleInvariantLoss, restated)
   exposure.py     per-view affine exposure compensation: apply_exposure, fit_exposure, color_corrected, Exposure (no reference
                   counterpart; exported here)
+  transform.py    similarity transforms of Gaussian scenes: transform_gaussians, rotate_sh, sh_rotation_matrices,
+                  transform_cameras, similarity_inverse, compose (the reference's src/misc/sh_rotation.py rotate_sh, restated
+                  in the rasterizer's own basis; exported here)
   compat/         importable `diff_gaussian_rasterization_depth` module for an unmodified reference tree
 
 There is no CPU or eager fallback: the ops raise if libfreesplat_hip.so is missing.
@@ -19,6 +22,8 @@ There is no CPU or eager fallback: the ops raise if libfreesplat_hip.so is missi
 __version__ = "0.1.0"
 
 _EXPOSURE = ("apply_exposure", "fit_exposure", "color_corrected", "Exposure")
+_TRANSFORM = ("transform_gaussians", "rotate_sh", "sh_rotation_matrices", "transform_cameras", "similarity_inverse", "compose",
+              "similarity_matrix")
 
 
 def __getattr__(name):
@@ -26,4 +31,7 @@ def __getattr__(name):
     if name in _EXPOSURE:
         from . import exposure
         return getattr(exposure, name)
+    if name in _TRANSFORM:
+        from . import transform
+        return getattr(transform, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

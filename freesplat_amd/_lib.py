@@ -1,6 +1,7 @@
 """ctypes binding of libfreesplat_hip.so (C ABI: include/freesplat_amd.h, include/freesplat_amd_loss.h,
 include/freesplat_amd_optim.h, include/freesplat_amd_density.h, include/freesplat_amd_depthloss.h,
-include/freesplat_amd_normals.h, include/freesplat_amd_exposure.h, include/freesplat_amd_mvdepth.h).
+include/freesplat_amd_normals.h, include/freesplat_amd_exposure.h, include/freesplat_amd_mvdepth.h,
+include/freesplat_amd_transform.h).
 
 The product path has NO fallback: if the HIP library is missing or a call fails this module
 raises.  `build()` compiles the library in-tree with hipcc for gfx950.
@@ -35,6 +36,7 @@ DEPTHLOSS_API_VERSION = 1  # include/freesplat_amd_depthloss.h FS_DEPTHLOSS_API_
 NORMALS_API_VERSION = 1  # include/freesplat_amd_normals.h FS_NORMALS_API_VERSION
 EXPOSURE_API_VERSION = 1  # include/freesplat_amd_exposure.h FS_EXPOSURE_API_VERSION
 MVDEPTH_API_VERSION = 1  # include/freesplat_amd_mvdepth.h FS_MVDEPTH_API_VERSION
+TRANSFORM_API_VERSION = 1  # include/freesplat_amd_transform.h FS_TRANSFORM_API_VERSION
 
 RASTER_TILE_CULL = 1
 RASTER_SH_FP16 = 2
@@ -53,6 +55,13 @@ DEPTH_LOSS_L1 = 2
 DEPTH_LOSS_MAX_SCALES = 6
 
 MVDEPTH_MAX_SOURCES = 16
+
+TRANSFORM_TABLE_FLOATS = 100
+TRANSFORM_S, TRANSFORM_R, TRANSFORM_T, TRANSFORM_Q, TRANSFORM_D1, TRANSFORM_D2, TRANSFORM_D3 = 0, 1, 10, 13, 17, 26, 51
+TRANSFORM_SH_CHANNEL_MAJOR = 1
+TRANSFORM_SH_TRANSPOSE = 2
+TRANSFORM_QUAT_XYZW = 4
+TRANSFORM_COV_FULL = 8
 
 
 def build(force: bool = False) -> str:
@@ -241,6 +250,15 @@ MVDEPTH_SIGNATURES = {
     "fs_si_depth_backward": (C.c_int, [C.c_int32] * 3 + [_VP] * 3 + [C.c_float] * 3 + [_VP] * 5),
 }
 
+# name -> (restype, argtypes); must list every symbol include/freesplat_amd_transform.h declares (a ninth header, a ninth table)
+TRANSFORM_SIGNATURES = {
+    "fs_transform_api_version": (C.c_int, []),
+    "fs_transform_prepare": (C.c_int, [C.c_int32] + [_VP] * 3),
+    "fs_sh_rotate": (C.c_int, [C.c_int32] * 4 + [_VP] * 5),
+    "fs_gaussians_transform_forward": (C.c_int, [C.c_int32] * 4 + [_VP] * 13),
+    "fs_gaussians_transform_backward": (C.c_int, [C.c_int32] * 4 + [_VP] * 13),
+}
+
 
 def lib():
     global _lib
@@ -256,7 +274,7 @@ def lib():
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
         for table in (SIGNATURES, LOSS_SIGNATURES, OPTIM_SIGNATURES, DENSITY_SIGNATURES, DEPTHLOSS_SIGNATURES,
-                      NORMALS_SIGNATURES, EXPOSURE_SIGNATURES, MVDEPTH_SIGNATURES):
+                      NORMALS_SIGNATURES, EXPOSURE_SIGNATURES, MVDEPTH_SIGNATURES, TRANSFORM_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)  # AttributeError if the library lacks a declared symbol
                 fn.restype = res
@@ -285,6 +303,9 @@ def lib():
         if L.fs_mvdepth_api_version() != MVDEPTH_API_VERSION:
             raise FreeSplatHipError(f"{LIB_PATH} has multi-view depth API revision {L.fs_mvdepth_api_version()}, this binding expects "
                                     f"{MVDEPTH_API_VERSION} (include/freesplat_amd_mvdepth.h FS_MVDEPTH_API_VERSION): rebuild the library")
+        if L.fs_transform_api_version() != TRANSFORM_API_VERSION:
+            raise FreeSplatHipError(f"{LIB_PATH} has transform API revision {L.fs_transform_api_version()}, this binding expects "
+                                    f"{TRANSFORM_API_VERSION} (include/freesplat_amd_transform.h FS_TRANSFORM_API_VERSION): rebuild the library")
         _lib = L
     return _lib
 

@@ -8,8 +8,9 @@ with the same argument shapes as encoder_freesplat.py:317-326 (fusion=True -> wo
 buffer and `get_scale_multiplier`.  Compute = fs_unproject_* / fs_gaussian_head_* in
 libfreesplat_hip.so (forward and backward kernels; differentiable w.r.t. depths, raw channels and
 the blended extrinsics).  sh_degree 0 - 3 (d_sh 1 / 4 / 9 / 16, the degrees the rasterizer evaluates); a
-higher degree raises.  The pixelSplat-only branch (fusion=False without coords: per-ray means +
-SH rotation) is not on FreeSplat's path and raises.
+higher degree raises.  The pixelSplat branch (fusion=False without coords, gaussian_adapter.py:174-192) takes its means from
+the same unprojection and rotates the harmonics into the world frame with freesplat_amd.transform.rotate_sh: one table row
+per view, the Gaussians' view ids on the device (no gradient reaches the extrinsics through the SH rotation).
 """
 from __future__ import annotations
 
@@ -245,24 +246,40 @@ class GaussianAdapter(nn.Module):
         xy = multiplier * torch.einsum("...ij,j->...i", torch.linalg.inv_ex(K).inverse, pixel_size)
         return xy.sum(dim=-1)
 
+    @staticmethod
+    def _world_means(extrinsics, intrinsics, depths, h, w):
+        """extrinsics [b,v,1,1,1,4,4], intrinsics [b,v,1,1,1,3,3], depths [b,v,h*w,1,1] -> [b,v,h*w,1,1,3]"""
+        b, v = intrinsics.shape[:2]
+        out = []
+        for i in range(b):
+            K = intrinsics[i, 0].reshape(3, 3)
+            k0 = torch.stack([K[0, 0] * w, K[1, 1] * h, K[0, 2] * w, K[1, 2] * h])
+            xyz = _Unproject.apply(_chk(depths[i].reshape(v, h * w), "depths"),
+                                   _chk(extrinsics[i].reshape(v, 4, 4), "extrinsics"), _chk(k0, "intrinsics"), h, w)
+            out.append(xyz)
+        return torch.stack(out)[:, :, :, None, None, :]
+
+    @staticmethod
+    def _view_rotations(extrinsics, lead, M):
+        """(rotations [V,3,3], ids [M] int64 on the device) for rotate_sh: one row per distinct camera when the extrinsics
+        broadcast over trailing dimensions of `lead` (the usual [b,v,1,1,1,4,4]), else one row per Gaussian."""
+        el = tuple(extrinsics.shape[:-2])
+        el = (1,) * (len(lead) - len(el)) + el
+        k = len(el)
+        while k > 0 and el[k - 1] == 1:
+            k -= 1
+        if tuple(el[:k]) == tuple(lead[:k]):
+            E = extrinsics.reshape(-1, 4, 4)
+        else:
+            E = extrinsics.expand(*lead, 4, 4).reshape(M, 4, 4)
+        ids = torch.arange(M, device=extrinsics.device).div(M // E.shape[0], rounding_mode="floor")
+        return E[:, :3, :3], ids
+
     def forward(self, extrinsics, intrinsics, coordinates, depths, opacities, raw_gaussians, image_shape,
                 eps: float = 1e-8, fusion: bool = False, coords=None):
         h, w = image_shape
         if fusion:
-            # extrinsics [b,v,1,1,1,4,4], intrinsics [b,v,1,1,1,3,3], depths [b,v,h*w,1,1] -> [b,v,h*w,1,1,3]
-            b, v = intrinsics.shape[:2]
-            out = []
-            for i in range(b):
-                K = intrinsics[i, 0].reshape(3, 3)
-                k0 = torch.stack([K[0, 0] * w, K[1, 1] * h, K[0, 2] * w, K[1, 2] * h])
-                xyz = _Unproject.apply(_chk(depths[i].reshape(v, h * w), "depths"),
-                                       _chk(extrinsics[i].reshape(v, 4, 4), "extrinsics"), _chk(k0, "intrinsics"), h, w)
-                out.append(xyz)
-            return torch.stack(out)[:, :, :, None, None, :]
-        if coords is None:
-            raise NotImplementedError("GaussianAdapter.forward(fusion=False, coords=None) is pixelSplat's per-ray path "
-                                      "(get_world_rays + rotate_sh); FreeSplat never takes it "
-                                      "(gaussian_adapter.py:174-192)")
+            return self._world_means(extrinsics, intrinsics, depths, h, w)
         if not 0 <= self.cfg.sh_degree <= 3:
             raise NotImplementedError(f"sh_degree {self.cfg.sh_degree}: the HIP rasterizer evaluates spherical harmonics of "
                                       "degree 0 - 3 only, so the Gaussian head stops there too")
@@ -276,5 +293,15 @@ class GaussianAdapter(nn.Module):
         cov, sh, scales, rot = _Head.apply(_chk(raw, "raw_gaussians"), _chk(depths.expand(lead).reshape(M), "depths"),
                                            _chk(E, "extrinsics"), _chk(mult, "multiplier"), self.sh_mask,
                                            float(self.cfg.gaussian_scale_min), float(self.cfg.gaussian_scale_max))
+        if coords is None:
+            # gaussian_adapter.py:174-192: per-pixel world means, and the camera-frame harmonics rotated by c2w[:3, :3]
+            coords = self._world_means(extrinsics, intrinsics, depths, h, w)
+            if tuple(coords.shape[:-1]) != tuple(lead):
+                raise RuntimeError(f"gaussian adapter: without coords the Gaussians are one per pixel and view; opacities "
+                                   f"{tuple(lead)} do not match the unprojected means {tuple(coords.shape)}")
+            if self.cfg.sh_degree > 0:
+                from .transform import rotate_sh
+                c2w_rotations, ids = self._view_rotations(extrinsics, lead, M)
+                sh = rotate_sh(sh, _chk(c2w_rotations, "extrinsics"), ids)
         return Gaussians(means=coords, covariances=cov.reshape(*lead, 3, 3), harmonics=sh.reshape(*lead, 3, self.d_sh),
                          opacities=opacities, scales=scales.reshape(*lead, 3), rotations=rot.reshape(*lead, 4))

@@ -271,6 +271,32 @@ class GaussianAdam:
                                                            p(self.exp_avg_sq[3]), p(self._opacities), _lib.current_stream()),
                        "fs_density_reset_opacity")
 
+    def transform_(self, transform) -> None:
+        """Move the scene by the similarity `transform` (a 4 x 4 [s R | t] or a tuple (s, R, t), as
+        freesplat_amd.transform.transform_gaussians takes it) in place: means = s R means + t, log-scales + log s, rotations =
+        q_R (x) rotations, every SH band rotated, opacity logits untouched; `.scales` / `.opacities` are rewritten.  The leaves
+        stay the same tensors.  Both moments, the step counter, the density statistics and pending gradients are reset, as a
+        fresh optimizer built from the transformed values would have them: moments of the old frame do not point anywhere
+        in the new one.  lr, betas and eps are kept.  One table launch and two kernels; a host transform is validated
+        (ValueError), a device transform is taken as given without synchronisation."""
+        from . import transform as X
+        xf, _ = X._xf(transform, self.lr.device)
+        if xf.shape[0] != 1:
+            raise ValueError(f"freesplat_amd.refine: transform_() takes one transform, got {xf.shape[0]}")
+        table = X.prepare_table(xf)
+        p = _lib.ptr
+        means, rot, shs = self._raw[0], self._raw[2], self._raw[4]
+        with torch.no_grad():
+            _lib.check(_lib.lib().fs_gaussians_transform_forward(self.N, self.M, 1, 0, p(table), None, p(means), None, p(rot), None,
+                                                                 p(shs), p(means), None, p(rot), None, p(shs),
+                                                                 _lib.current_stream()), "fs_gaussians_transform_forward")
+            self._raw[1].add_(torch.log(table[0, _lib.TRANSFORM_S]))
+            for t in self.exp_avg + self.exp_avg_sq + [self.step_count, self.grad_accum, self.denom, self.max_radii]:
+                t.zero_()
+            self._activate()
+        self.zero_grad()
+        self.viewspace.grad = None
+
     def state_dict(self) -> dict:
         """Copies of the raw parameters, both moments, the density statistics, the step counter and the rates (device tensors)
         and the scalars."""
