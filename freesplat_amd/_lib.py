@@ -1,7 +1,7 @@
 """ctypes binding of libfreesplat_hip.so (C ABI: include/freesplat_amd.h, include/freesplat_amd_loss.h,
 include/freesplat_amd_optim.h, include/freesplat_amd_density.h, include/freesplat_amd_depthloss.h,
 include/freesplat_amd_normals.h, include/freesplat_amd_exposure.h, include/freesplat_amd_mvdepth.h,
-include/freesplat_amd_transform.h).
+include/freesplat_amd_transform.h, include/freesplat_amd_pose.h).
 
 The product path has NO fallback: if the HIP library is missing or a call fails this module
 raises.  `build()` compiles the library in-tree with hipcc for gfx950.
@@ -37,6 +37,7 @@ NORMALS_API_VERSION = 1  # include/freesplat_amd_normals.h FS_NORMALS_API_VERSIO
 EXPOSURE_API_VERSION = 1  # include/freesplat_amd_exposure.h FS_EXPOSURE_API_VERSION
 MVDEPTH_API_VERSION = 1  # include/freesplat_amd_mvdepth.h FS_MVDEPTH_API_VERSION
 TRANSFORM_API_VERSION = 1  # include/freesplat_amd_transform.h FS_TRANSFORM_API_VERSION
+POSE_API_VERSION = 1     # include/freesplat_amd_pose.h FS_POSE_API_VERSION
 
 RASTER_TILE_CULL = 1
 RASTER_SH_FP16 = 2
@@ -62,6 +63,10 @@ TRANSFORM_SH_CHANNEL_MAJOR = 1
 TRANSFORM_SH_TRANSPOSE = 2
 TRANSFORM_QUAT_XYZW = 4
 TRANSFORM_COV_FULL = 8
+
+SIM3_MAX_ROWS = 64
+SIM3_TANGENT_DIM = 7
+SIM3_SH_GENERATOR_DOUBLES = 83
 
 
 def build(force: bool = False) -> str:
@@ -259,6 +264,14 @@ TRANSFORM_SIGNATURES = {
     "fs_gaussians_transform_backward": (C.c_int, [C.c_int32] * 4 + [_VP] * 13),
 }
 
+# name -> (restype, argtypes); must list every symbol include/freesplat_amd_pose.h declares (a tenth header, a tenth table)
+POSE_SIGNATURES = {
+    "fs_pose_api_version": (C.c_int, []),
+    "fs_sim3_tangent_scratch_bytes": (C.c_size_t, [C.c_int32] * 2),
+    "fs_sim3_sh_generators": (C.c_int, [C.POINTER(C.c_double)]),
+    "fs_sim3_tangent": (C.c_int, [C.c_int32] * 4 + [_VP] * 13 + [C.c_size_t, _VP]),
+}
+
 
 def lib():
     global _lib
@@ -274,7 +287,7 @@ def lib():
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
         for table in (SIGNATURES, LOSS_SIGNATURES, OPTIM_SIGNATURES, DENSITY_SIGNATURES, DEPTHLOSS_SIGNATURES,
-                      NORMALS_SIGNATURES, EXPOSURE_SIGNATURES, MVDEPTH_SIGNATURES, TRANSFORM_SIGNATURES):
+                      NORMALS_SIGNATURES, EXPOSURE_SIGNATURES, MVDEPTH_SIGNATURES, TRANSFORM_SIGNATURES, POSE_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)  # AttributeError if the library lacks a declared symbol
                 fn.restype = res
@@ -306,6 +319,9 @@ def lib():
         if L.fs_transform_api_version() != TRANSFORM_API_VERSION:
             raise FreeSplatHipError(f"{LIB_PATH} has transform API revision {L.fs_transform_api_version()}, this binding expects "
                                     f"{TRANSFORM_API_VERSION} (include/freesplat_amd_transform.h FS_TRANSFORM_API_VERSION): rebuild the library")
+        if L.fs_pose_api_version() != POSE_API_VERSION:
+            raise FreeSplatHipError(f"{LIB_PATH} has pose API revision {L.fs_pose_api_version()}, this binding expects "
+                                    f"{POSE_API_VERSION} (include/freesplat_amd_pose.h FS_POSE_API_VERSION): rebuild the library")
         _lib = L
     return _lib
 

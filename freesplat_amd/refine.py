@@ -297,6 +297,16 @@ class GaussianAdam:
         self.zero_grad()
         self.viewspace.grad = None
 
+    def observed(self, extrinsics):
+        """The five leaves for ONE rendered view whose camera is to receive a gradient: (means, scales, rotations, opacities,
+        shs) with means, scales, rotations and shs routed through freesplat_amd.pose.observe(extrinsics, ...) -- the identity
+        forward; backward, the leaves get their gradients bit for bit and `extrinsics` (a device [4, 4] camera-to-world matrix
+        that requires grad) gets the camera's.  Opacities do not move with a pose and are the leaf itself."""
+        from .pose import observe
+        means, scales, rotations, _, shs = observe(extrinsics, means=self.means, scales=self.scales, rotations=self.rotations,
+                                                   harmonics=self.shs, quat_order="wxyz", sh_layout="coeff_major")
+        return means, scales, rotations, self.opacities, shs
+
     def state_dict(self) -> dict:
         """Copies of the raw parameters, both moments, the density statistics, the step counter and the rates (device tensors)
         and the scalars."""

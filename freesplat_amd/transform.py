@@ -15,7 +15,13 @@ Wigner matrices of another library's basis order.
 A transform is a 4 x 4 matrix [s R | t; 0 0 0 1] (or its first three rows) or a tuple (s, R, t); [V, 4, 4] / (s [V], R [V,3,3], t [V,3]) with `view_ids`
 gives every Gaussian its own transform.  A HOST transform (CPU tensor, array, numbers) is checked in float64 -- R^T R = I,
 det > 0, s > 0 -- and raises ValueError; a DEVICE tensor is taken as given, without synchronisation (capturable in a graph).
-Gradients reach the Gaussians, never the transform.  Device tensors only: there is no CPU / eager path.
+
+Gradients reach the Gaussians and, in `transform_gaussians`, a DEVICE transform that requires grad (a matrix, or the tensors of
+(s, R, t); with `view_ids` up to 64 rows): the backward then also runs the tangent reduction of pose.py over the inputs and
+their gradients and hands autograd the ambient gradient of the rows (s R | t) (DESIGN.md "Pose and transform gradients").  The
+gradient is that of a similarity: it is exact along T Exp(xi) and has no component that would shear the matrix.  A transform
+that does not require grad costs what it did, and a host transform never receives a gradient.  Device tensors only: there is
+no CPU / eager path.
 """
 from __future__ import annotations
 
@@ -131,7 +137,13 @@ def _is_device(x) -> bool:
 
 
 def _xf(T, device) -> tuple:
-    """transform -> (xf [V, 3, 4] float32 on `device`, rows (s R | t); batched?)."""
+    """transform -> (xf [V, 3, 4] float32 on `device`, rows (s R | t), detached; batched?)."""
+    xf, batched, _ = _xf_live(T, device)
+    return xf, batched
+
+
+def _xf_live(T, device) -> tuple:
+    """As _xf, and third the same rows attached to the autograd graph of a device transform that requires grad (else None)."""
     parts = T if isinstance(T, (tuple, list)) and len(T) == 3 else (T,)
     if any(_is_device(x) for x in parts):
         if len(parts) == 3:
@@ -153,10 +165,11 @@ def _xf(T, device) -> tuple:
             xf = M.reshape(-1, M.shape[-2], 4)[:, :3, :]
         if xf.device != device:
             raise ValueError(f"{_P}tensors on different devices")
-        return xf.detach().float().contiguous(), batched
+        live = xf.float().contiguous() if torch.is_grad_enabled() and xf.requires_grad else None
+        return xf.detach().float().contiguous(), batched, live
     s, R, t, batched = _split_host(T)
     xf = torch.cat([s[:, None, None] * R, t[:, :, None]], 2)
-    return xf.float().to(device), batched
+    return xf.float().to(device), batched, None
 
 
 def prepare_table(xf: Tensor) -> Tensor:
@@ -215,36 +228,48 @@ def _sh_dims(sh: Tensor, layout: str):
 
 
 class _Transform(torch.autograd.Function):
-    """(table, ids, flags, M, N, means, scales, rotations, cov, shs) -> the five transformed arrays (None where None went in)."""
+    """(xf, table, ids, flags, M, N, means, scales, rotations, cov, shs) -> the five transformed arrays (None where None went
+    in).  xf: None, or the rows (s R | t) the table was made of when they require grad; the inputs are then kept (by reference)
+    for the tangent reduction of the backward."""
 
     @staticmethod
-    def forward(ctx, table, ids, flags, M, N, *arrays):
+    def forward(ctx, xf, table, ids, flags, M, N, *arrays):
         ins = [None if a is None else a.contiguous() for a in arrays]
         outs = [None if a is None else torch.empty_like(a) for a in ins]
         p = _lib.ptr
         _lib.check(_lib.lib().fs_gaussians_transform_forward(N, M, table.shape[0], flags, p(table), p(ids), *[p(a) for a in ins],
                                                              *[p(a) for a in outs], _lib.current_stream()),
                    "fs_gaussians_transform_forward")
-        ctx.save_for_backward(table, *([ids] if ids is not None else []))
-        ctx.cfg = (flags, M, N, ids is not None, [None if a is None else a.shape for a in ins])
+        ctx.save_for_backward(table, *([ids] if ids is not None else []), *([a for a in ins if a is not None] if xf is not None else []))
+        ctx.cfg = (flags, M, N, ids is not None, [a is not None for a in ins], xf is not None)
         ctx.set_materialize_grads(False)
         return tuple(outs)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, *grads):
-        flags, M, N, has_ids, shapes = ctx.cfg
+        flags, M, N, has_ids, present, has_xf = ctx.cfg
         table = ctx.saved_tensors[0]
         ids = ctx.saved_tensors[1] if has_ids else None
-        gs = [None if (g is None or not need) else g.float().contiguous() for g, need in zip(grads, ctx.needs_input_grad[5:])]
+        need_xf = has_xf and ctx.needs_input_grad[0]              # the transform's gradient needs every array's input gradient
+        needs = ctx.needs_input_grad[6:]
+        gs = [None if (g is None or not (need or need_xf)) else g.float().contiguous() for g, need in zip(grads, needs)]
         if all(g is None for g in gs):
-            return (None,) * 10
+            return (None,) * 11
         outs = [None if g is None else torch.empty_like(g) for g in gs]
         p = _lib.ptr
         _lib.check(_lib.lib().fs_gaussians_transform_backward(N, M, table.shape[0], flags, p(table), p(ids), *[p(g) for g in gs],
                                                               *[p(o) for o in outs], _lib.current_stream()),
                    "fs_gaussians_transform_backward")
-        return (None,) * 5 + tuple(outs)
+        g_xf = None
+        if need_xf:
+            from . import pose
+            it = iter(ctx.saved_tensors[2 if has_ids else 1:])
+            ins = [next(it) if has else None for has in present]
+            ins = [None if o is None else a for a, o in zip(ins, outs)]
+            tau = pose._tangent(N, M, table.shape[0], flags, ids, ins, outs)
+            g_xf = pose.transform_ambient(table, tau).float()
+        return (g_xf,) + (None,) * 5 + tuple(o if need else None for o, need in zip(outs, needs))
 
 
 class _RotateSH(torch.autograd.Function):
@@ -310,7 +335,8 @@ def transform_gaussians(gaussians=None, transform=None, *, means=None, scales=No
     quaternions in `quat_order` ("wxyz" as GaussianAdam and the rasterizer, or "xyzw"); covariances [..., 3, 3] or the six
     entries [..., 6]; harmonics in `sh_layout`.  All arrays share their leading shape.
 
-    One or two library launches after the table's; differentiable with respect to every array given."""
+    One or two library launches after the table's; differentiable with respect to every array given and to a device transform
+    that requires grad (the module docstring; its backward adds the two launches of the tangent reduction)."""
     if transform is None:
         raise ValueError(f"{_P}transform_gaussians needs a transform")
     if gaussians is not None:
@@ -327,6 +353,18 @@ def _apply(transform, means, scales, rotations, covariances, harmonics, view_ids
         raise ValueError(f"{_P}quat_order must be one of {QUAT_ORDERS}, got {quat_order!r}")
     if not any(_is_device(x) for x in (transform if isinstance(transform, (tuple, list)) else (transform,))):
         _split_host(transform)                # a host transform is judged first: its errors need no device
+    flags, M, N, device = _array_layout(means, scales, rotations, covariances, harmonics, quat_order, sh_layout)
+    xf, batched, live = _xf_live(transform, device)
+    if live is not None and xf.shape[0] > _lib.SIM3_MAX_ROWS:
+        raise ValueError(f"{_P}a transform that requires grad may have up to {_lib.SIM3_MAX_ROWS} rows, got {xf.shape[0]}")
+    ids = _ids(view_ids, N, xf.shape[0], batched, device)
+    return _Transform.apply(live, prepare_table(xf), ids, flags, M, N, means, scales, rotations, covariances, harmonics)
+
+
+def _array_layout(means, scales, rotations, covariances, harmonics, quat_order, sh_layout) -> tuple:
+    """(layout flags, M, N, device) of the arrays given (any subset; float32 device tensors that agree on N), after the checks."""
+    if quat_order not in QUAT_ORDERS:
+        raise ValueError(f"{_P}quat_order must be one of {QUAT_ORDERS}, got {quat_order!r}")
     given = [(n, t) for n, t in (("means", means), ("scales", scales), ("rotations", rotations), ("covariances", covariances),
                                  ("harmonics", harmonics)) if t is not None]
     if not given:
@@ -355,12 +393,9 @@ def _apply(transform, means, scales, rotations, covariances, harmonics, view_ids
         flags |= _lib.TRANSFORM_SH_CHANNEL_MAJOR if sh_layout == "channel_major" else 0
     if len(set(counts.values())) != 1:
         raise ValueError(f"{_P}the arrays disagree on the number of Gaussians: {counts}")
-    N = next(iter(counts.values()))
     if quat_order == "xyzw":
         flags |= _lib.TRANSFORM_QUAT_XYZW
-    xf, batched = _xf(transform, device)
-    ids = _ids(view_ids, N, xf.shape[0], batched, device)
-    return _Transform.apply(prepare_table(xf), ids, flags, M, N, means, scales, rotations, covariances, harmonics)
+    return flags, M, next(iter(counts.values())), device
 
 
 # ---- helpers on transforms and cameras ----------------------------------------------------------------------------------------

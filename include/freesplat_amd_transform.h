@@ -98,8 +98,9 @@ int fs_transform_prepare(int32_t V, const float* xf /*[V,3,4]*/, float* table /*
  * maps -- s R^T g, s g, conj(q) (x) g, s^2 R^T G R, D^T g -- through the same chains with E = R^T, p = conj(q) = (q_w, -q_x,
  * -q_y, -q_z), D[j][i], and out_i = s * r_i for the means.  For the six-entry covariance the result is the derivative with
  * respect to the six stored entries: the chains run on K = (g_xx, g_xy / 2, g_xz / 2, g_yy, g_yz / 2, g_zz) and the
- * off-diagonal results are doubled (both steps exact).  Gradients with respect to the transform itself (s, R, t) are out of
- * scope: no entry point computes them.
+ * off-diagonal results are doubled (both steps exact).  The gradient with respect to the transform itself (s, R, t) is not
+ * computed here: fs_sim3_tangent (freesplat_amd_pose.h) contracts the inputs of the forward and the input gradients of this
+ * backward with the generators of Sim(3), which is that gradient in the tangent space at the transform.
  *
  * Each array is optional: a NULL *_in skips it, and its *_out is then neither read nor written.  A non-NULL *_in needs a
  * non-NULL *_out.  All five NULL is FS_ERR_INVALID_ARG.
