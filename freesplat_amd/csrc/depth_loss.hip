@@ -20,11 +20,9 @@
 // residual from depth, gt and alpha and applies dE/d depth, dE/d alpha and the point term.  Every output element is written
 // by exactly one thread; nothing is accumulated in memory.
 //
-// Deterministic: per-thread sums in a fixed order, a fixed fp64 tree per workgroup, one partial row per workgroup, a finalize
-// workgroup per (view, level).  The partition depends only on (H, W, S).  No atomics.
-#include "fs_common.h"
-
-#include <math.h>
+// Deterministic: per-thread sums in a fixed order, block_sum_tree (fs_reduce.h) per workgroup, one partial row per workgroup, a
+// finalize workgroup per (view, level).  The partition depends only on (H, W, S).  No atomics.
+#include "fs_reduce.h"
 
 #include "../../include/freesplat_amd_depthloss.h"
 
@@ -60,38 +58,15 @@ struct Row {                                  // one workgroup's partial sums
     double point_sum, point_cnt, grad_sum, grad_cnt;
 };
 
-// fixed-order fp64 tree over the 256 threads of a workgroup; the totals end up in v[] of every thread
-template <int F>
-__device__ __forceinline__ void block_sum(double (&v)[F], double* s_red /* [F][kThreads] */)
-{
-    const int t = threadIdx.x;
-#pragma unroll
-    for (int f = 0; f < F; ++f) s_red[f * kThreads + t] = v[f];
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (t < s)
-#pragma unroll
-            for (int f = 0; f < F; ++f) s_red[f * kThreads + t] += s_red[f * kThreads + t + s];
-        __syncthreads();
-    }
-#pragma unroll
-    for (int f = 0; f < F; ++f) v[f] = s_red[f * kThreads];
-}
-
-__device__ __forceinline__ bool gt_valid(float g, const Params& P)
-{
-    return fabsf(g) < INFINITY && g > P.min_depth && g < P.max_depth;    // (NaN fails every comparison)
-}
-
 __device__ __forceinline__ float sgn(float v) { return v > 0.0f ? 1.0f : (v < 0.0f ? -1.0f : 0.0f); }
 
 // level-0 pixel from its raw values: expected depth E, the gt value (0 when invalid) and the residual (NaN when invalid)
 __device__ __forceinline__ float residual0(float d, float graw, float al, bool has_alpha, const Params& P, float& E, float& g,
                                            bool& valid)
 {
-    valid = gt_valid(graw, P);
+    valid = valid_depth(graw, P.min_depth, P.max_depth);
     g = valid ? graw : 0.0f;
-    E = has_alpha ? d / fmaxf(al, P.alpha_floor) : d;
+    E = expected_depth<float>(d, al, has_alpha, P.alpha_floor);
     return valid ? E - g : __builtin_nanf("");
 }
 
@@ -207,7 +182,7 @@ __global__ __launch_bounds__(kThreads) void depth_loss_fwd_kernel(int Hs, int Ws
     }
 
     double v[4] = {p_sum, (double)p_cnt, g_sum, (double)g_cnt};
-    block_sum<4>(v, s_red);
+    block_sum_tree<4>(v, s_red);
     if (t == 0) rows[blockIdx.x] = Row{v[0], v[1], v[2], v[3]};
 }
 
@@ -234,7 +209,7 @@ __global__ __launch_bounds__(kThreads) void depth_loss_finalize_kernel(int S, Le
         v[2] += r[k].grad_sum;
         v[3] += r[k].grad_cnt;
     }
-    block_sum<4>(v, s_red);
+    block_sum_tree<4>(v, s_red);
     if (threadIdx.x == 0) {
         grad_sum[blockIdx.x] = v[2];
         grad_cnt[blockIdx.x] = v[3];

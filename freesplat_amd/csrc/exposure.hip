@@ -13,14 +13,12 @@
 // the 12 parameters of that view are wave-uniform and are read once per workgroup with scalar loads, not per pixel.  An id
 // outside [0, V) turns the workgroup into a copy and keeps it away from the parameter array.
 //
-// Sums (g_params: 12, fit: 22) follow depth_loss.hip / normals_loss.hip: products of fp32 values formed in fp64 (exact), each
-// thread's fp64 sums in a fixed order, a fixed fp64 tree per workgroup, one row of partials per workgroup in the caller's
-// scratch, and one finalize workgroup per VIEW that walks the entries in index order, takes those whose id equals its view and
+// Sums (g_params: 12, fit: 22): products of fp32 values formed in fp64 (exact), each thread's fp64 sums in a fixed order,
+// block_sum_waves (fs_reduce.h) per workgroup, one row of partials per workgroup in the caller's scratch, and one finalize
+// workgroup per VIEW that walks the entries in index order, takes those whose id equals its view and
 // adds their rows in row order (in the fit, one thread of it then does the 4 x 4 Cholesky solve).  The partition depends on
 // (H, W) only.  No float atomics, no workgroup waits on another.
-#include "fs_common.h"
-
-#include <math.h>
+#include "fs_reduce.h"
 
 #include "../../include/freesplat_amd_exposure.h"
 
@@ -29,7 +27,7 @@ namespace fs {
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / kWave;
+constexpr int kWaves = kSumWaves;
 constexpr int kVec = 4;                              // pixels of a group: one 16-byte access per plane
 constexpr int kIters = 4;                            // groups per thread
 constexpr int kGroups = kThreads * kIters;           // groups per workgroup
@@ -38,35 +36,6 @@ constexpr int kGradSums = 12, kFitSums = 22;         // doubles per partial row
 
 // fit sums: M = sum X X^T as {x0x0, x0x1, x0x2, x0, x1x1, x1x2, x1, x2x2, x2, 1}, then R = sum X y^T as [k][c], k = 3 being y itself
 constexpr int kCnt = 9, kR = 10;
-
-struct Px4 {
-    float v[kVec];
-};
-
-// the four pixels p0 .. p0 + 3 of a plane; a pixel at or beyond P reads nothing and is 0
-__device__ __forceinline__ Px4 load4(const float* __restrict__ plane, long long p0, long long P, bool aligned)
-{
-    Px4 r;
-    if (aligned && p0 + kVec <= P) {
-        const float4 q = *reinterpret_cast<const float4*>(plane + p0);
-        r.v[0] = q.x; r.v[1] = q.y; r.v[2] = q.z; r.v[3] = q.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < kVec; ++j) r.v[j] = p0 + j < P ? plane[p0 + j] : 0.0f;
-    }
-    return r;
-}
-
-__device__ __forceinline__ void store4(float* __restrict__ plane, long long p0, long long P, bool aligned, const Px4& r)
-{
-    if (aligned && p0 + kVec <= P) {
-        *reinterpret_cast<float4*>(plane + p0) = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
-    } else {
-#pragma unroll
-        for (int j = 0; j < kVec; ++j)
-            if (p0 + j < P) plane[p0 + j] = r.v[j];
-    }
-}
 
 // the mask bytes of the four pixels (nonzero = use); a pixel at or beyond P is 0
 __device__ __forceinline__ uint32_t load_mask4(const uint8_t* __restrict__ m, long long p0, long long P, bool aligned)
@@ -77,28 +46,6 @@ __device__ __forceinline__ uint32_t load_mask4(const uint8_t* __restrict__ m, lo
     for (int j = 0; j < kVec; ++j)
         if (p0 + j < P) r |= (uint32_t)m[p0 + j] << (8 * j);
     return r;
-}
-
-__device__ __forceinline__ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// fixed-order fp64 tree over the 256 threads of a workgroup: six shuffle steps inside each wavefront, then the four wavefronts
-// in order.  The totals are valid in thread 0 only.
-template <int F>
-__device__ __forceinline__ void block_sum(double (&v)[F], double* s_red /* [kWaves][F] */)
-{
-    const int t = threadIdx.x;
-#pragma unroll
-    for (int f = 0; f < F; ++f)
-#pragma unroll
-        for (int off = kWave / 2; off > 0; off >>= 1) v[f] += __shfl_down(v[f], off, kWave);
-    if ((t & (kWave - 1)) == 0)
-#pragma unroll
-        for (int f = 0; f < F; ++f) s_red[(t / kWave) * F + f] = v[f];
-    __syncthreads();
-    if (t == 0)
-#pragma unroll
-        for (int f = 0; f < F; ++f) v[f] = ((s_red[f] + s_red[F + f]) + s_red[2 * F + f]) + s_red[3 * F + f];
-    static_assert(kWaves == 4, "the last step adds four wavefronts");
 }
 
 // what a workgroup knows of its batch entry: all of it wave-uniform
@@ -242,7 +189,7 @@ __global__ __launch_bounds__(kThreads) void exposure_bwd_kernel(int V, long long
         }
     }
     if constexpr (GP) {
-        block_sum<kGradSums>(s, s_red);
+        block_sum_waves<kGradSums>(s, s_red);
         if (threadIdx.x == 0 && e.on) {
             double* row = rows + (size_t)blockIdx.x * kGradSums;
 #pragma unroll
@@ -251,7 +198,7 @@ __global__ __launch_bounds__(kThreads) void exposure_bwd_kernel(int V, long long
     }
 }
 
-// the rows of view blockIdx.x: entries in index order, an entry's rows strided over the threads, then the fixed tree.  The
+// the rows of view blockIdx.x: entries in index order, an entry's rows strided over the threads, then block_sum_waves.  The
 // totals are valid in thread 0.
 template <int F>
 __device__ __forceinline__ void view_sum(int B, int chunks, const long long* __restrict__ view_ids, const double* __restrict__ rows,
@@ -268,7 +215,7 @@ __device__ __forceinline__ void view_sum(int B, int chunks, const long long* __r
 #pragma unroll
             for (int f = 0; f < F; ++f) s[f] += r[(size_t)k * F + f];
     }
-    block_sum<F>(s, s_red);
+    block_sum_waves<F>(s, s_red);
 }
 
 // one workgroup per view: g_params [V,3,4], written in full (exactly 0 for a view without an entry)
@@ -363,7 +310,7 @@ __global__ __launch_bounds__(kThreads) void exposure_fit_kernel(int V, long long
             }
         }
     }
-    block_sum<kFitSums>(s, s_red);
+    block_sum_waves<kFitSums>(s, s_red);
     if (threadIdx.x == 0) {
         double* row = rows + (size_t)blockIdx.x * kFitSums;
 #pragma unroll

@@ -8,9 +8,9 @@
 // (12, 27 or 48 floats of values and as many of gradients; at M = 9 through the 16-byte words that cover the 27), so that no
 // more than one Gaussian's coefficients are live.  Which path loaded a value changes nothing about the arithmetic.
 //
-// Sums follow exposure.hip: products of fp32 values formed in fp64 (exact), each thread's seven fp64 sums in a fixed order, a
-// fixed fp64 tree per workgroup, one row of partials per (id, workgroup) in the caller's scratch, and one finalize workgroup
-// per id that adds the rows in a fixed order.  The grid's second dimension runs over the ids: workgroup (b, v) takes the
+// Sums: products of fp32 values formed in fp64 (exact), each thread's seven fp64 sums in a fixed order, block_sum_waves
+// (fs_reduce.h) per workgroup, one row of partials per (id, workgroup) in the caller's scratch, and finalize_rows_kernel per
+// id.  The grid's second dimension runs over the ids: workgroup (b, v) takes the
 // Gaussians of chunk b whose id is v.  Ids come in long runs (one view after another), so all but one or two of a chunk's V
 // workgroups find no Gaussian of theirs, write a row of zeros after reading 8 KB of ids and leave; a thread none of whose
 // four Gaussians match loads nothing.  What workgroup (b, v) adds up depends on nothing but the positions and values of the
@@ -21,9 +21,7 @@
 // 24 entries above the diagonals of the nine matrices, with the closed forms 1, 2, 3, sqrt(3), sqrt(3/2), sqrt(5/2), sqrt(6).
 // They are compile-time constants here (kGen); the contraction g^T G c runs over those entries only, as
 // G[i][j] (g_i c_j - g_j c_i) summed over the three colour channels first.
-#include "fs_common.h"
-
-#include <math.h>
+#include "fs_reduce.h"
 
 #include <utility>
 
@@ -34,7 +32,7 @@ namespace fs {
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / kWave;
+constexpr int kWaves = kSumWaves;
 constexpr int kGroup = 4;                            // Gaussians of a thread
 constexpr int kChunk = kThreads * kGroup;            // Gaussians of a workgroup
 constexpr int kSums = FS_SIM3_TANGENT_DIM;           // (u, omega, sigma)
@@ -60,26 +58,6 @@ __device__ __forceinline__ void static_for(std::integer_sequence<int, Is...>, F&
     (f(std::integral_constant<int, Is>{}), ...);
 }
 
-__device__ __forceinline__ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// the S floats (S a multiple of four) at float offset `off` of an array of `total` floats; a float at or beyond `total` reads
-// nothing and is 0
-template <int S>
-__device__ __forceinline__ void load_run(const float* __restrict__ base, size_t off, size_t total, bool aligned, float (&r)[S])
-{
-    static_assert(S % 4 == 0, "a run is whole 16-byte words");
-    if (aligned && off + S <= total) {
-#pragma unroll
-        for (int k = 0; k < S / 4; ++k) {
-            const float4 q = *reinterpret_cast<const float4*>(base + off + 4 * k);
-            r[4 * k] = q.x; r[4 * k + 1] = q.y; r[4 * k + 2] = q.z; r[4 * k + 3] = q.w;
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < S; ++k) r[k] = off + k < total ? base[off + k] : 0.0f;
-    }
-}
-
 // the W floats of Gaussian J of the run that starts at float offset `off` (a multiple of four): floats [J W, J W + W) of the
 // run, through the 16-byte words that cover them when the array is aligned and those words lie inside it, else one by one.
 // The Gaussian exists (the caller checked), so its own floats are inside the array on either path.
@@ -100,25 +78,6 @@ __device__ __forceinline__ void load_gaussian(const float* __restrict__ base, si
 #pragma unroll
         for (int e = 0; e < W; ++e) r[e] = base[off + first + e];
     }
-}
-
-// fixed-order fp64 tree over the 256 threads of a workgroup: six shuffle steps inside each wavefront, then the four wavefronts
-// in order.  The totals are valid in thread 0 only.
-__device__ __forceinline__ void block_sum(double (&v)[kSums], double* s_red /* [kWaves][kSums] */)
-{
-    const int t = threadIdx.x;
-#pragma unroll
-    for (int f = 0; f < kSums; ++f)
-#pragma unroll
-        for (int off = kWave / 2; off > 0; off >>= 1) v[f] += __shfl_down(v[f], off, kWave);
-    if ((t & (kWave - 1)) == 0)
-#pragma unroll
-        for (int f = 0; f < kSums; ++f) s_red[(t / kWave) * kSums + f] = v[f];
-    __syncthreads();
-    if (t == 0)
-#pragma unroll
-        for (int f = 0; f < kSums; ++f) v[f] = ((s_red[f] + s_red[kSums + f]) + s_red[2 * kSums + f]) + s_red[3 * kSums + f];
-    static_assert(kWaves == 4, "the last step adds four wavefronts");
 }
 
 // ---- the terms of one Gaussian; s = (u, omega, sigma) -------------------------------------------------------------------------
@@ -286,27 +245,10 @@ __global__ __launch_bounds__(kThreads) void tangent_kernel(int N, int xyzw_, con
             }
         }
     }
-    block_sum(s, s_red);
+    block_sum_waves<kSums>(s, s_red);
     if (threadIdx.x == 0)
 #pragma unroll
         for (int f = 0; f < kSums; ++f) row[f] = s[f];
-}
-
-// one workgroup per id: its rows strided over the threads in row order, then the fixed tree
-__global__ __launch_bounds__(kThreads) void tangent_finalize_kernel(int blocks, const double* __restrict__ rows, double* __restrict__ out)
-{
-    __shared__ double s_red[kWaves * kSums];
-    const double* __restrict__ r = rows + (size_t)blockIdx.x * blocks * kSums;
-    double s[kSums];
-#pragma unroll
-    for (int f = 0; f < kSums; ++f) s[f] = 0.0;
-    for (int b = threadIdx.x; b < blocks; b += kThreads)
-#pragma unroll
-        for (int f = 0; f < kSums; ++f) s[f] += r[(size_t)b * kSums + f];
-    block_sum(s, s_red);
-    if (threadIdx.x == 0)
-#pragma unroll
-        for (int f = 0; f < kSums; ++f) out[(size_t)blockIdx.x * kSums + f] = s[f];
 }
 
 bool valid_m(int32_t M) { return M == 1 || M == 4 || M == 9 || M == 16; }
@@ -390,7 +332,11 @@ FS_API int fs_sim3_tangent(int32_t N, int32_t M, int32_t V, int32_t flags, const
         case 9: launch_m<9>(cm, cov_full, grid, st, a); break;
         default: launch_m<16>(cm, cov_full, grid, st, a); break;
     }
-    hipLaunchKernelGGL(tangent_finalize_kernel, dim3((unsigned)V), dim3(kThreads), 0, st, blocks, (const double*)scratch, out);
+    RowOuts<kSums> outs = {};                               // out [V][kSums]
+    for (int f = 0; f < kSums; ++f) outs.out[f] = out + f;
+    outs.stride = kSums;
+    hipLaunchKernelGGL((finalize_rows_kernel<kSums, BlockSum::kWaves, false>), dim3((unsigned)V), dim3(kThreads), 0, st, blocks, 1,
+                       (const double*)scratch, outs);
     FS_CHECK_LAUNCH("sim3_tangent");
     return FS_OK;
 }

@@ -18,9 +18,7 @@
 //
 // The forward and the backward are one kernel: the backward loads R transposed, the conjugate quaternion and D transposed from
 // the table (an address choice, not a register shuffle) and drops the translation.  No atomics, no scratch, no LDS.
-#include "fs_common.h"
-
-#include <math.h>
+#include "fs_reduce.h"
 
 #include "../../include/freesplat_amd_transform.h"
 
@@ -32,26 +30,6 @@ constexpr int kThreads = 256;
 constexpr int kRow = FS_TRANSFORM_TABLE_FLOATS;
 constexpr int kGeomGroup = 4;                        // Gaussians of a thread in the geometry arrays
 constexpr int kFlagMask = FS_TRANSFORM_SH_CHANNEL_MAJOR | FS_TRANSFORM_SH_TRANSPOSE | FS_TRANSFORM_QUAT_XYZW | FS_TRANSFORM_COV_FULL;
-
-__device__ __forceinline__ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// the S floats (S a multiple of four) at float offset `off` of an array of `total` floats; a float at or beyond `total` reads
-// nothing and is 0
-template <int S>
-__device__ __forceinline__ void load_run(const float* base, size_t off, size_t total, bool aligned, float (&r)[S])
-{
-    static_assert(S % 4 == 0, "a run is whole 16-byte words");
-    if (aligned && off + S <= total) {
-#pragma unroll
-        for (int k = 0; k < S / 4; ++k) {
-            const float4 q = *reinterpret_cast<const float4*>(base + off + 4 * k);
-            r[4 * k] = q.x; r[4 * k + 1] = q.y; r[4 * k + 2] = q.z; r[4 * k + 3] = q.w;
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < S; ++k) r[k] = off + k < total ? base[off + k] : 0.0f;
-    }
-}
 
 template <int S>
 __device__ __forceinline__ void store_run(float* base, size_t off, size_t total, bool aligned, const float (&r)[S])

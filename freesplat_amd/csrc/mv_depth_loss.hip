@@ -17,16 +17,13 @@
 // logarithm as logf of the ratio rounded to fp32 plus the first-order term of what the rounding dropped (log_of()): the fp32
 // chain would put its 1e-7 on a residual of a few 1e-2.  These are some ten fp64 operations per pixel and source.
 //
-// Sums follow exposure.hip: a thread's pixels in index order in fp64, a fixed shuffle tree per wavefront, the four wavefronts
-// in order, one row of partials per workgroup and source in the caller's scratch, and a second launch with one workgroup per
-// (view, source) that adds the rows in index order.  Counts are integers.  The partition depends on (H, W) only.  No float
+// Sums: a thread's pixels in index order in fp64, the block_sum_waves order of fs_reduce.h per workgroup, one row of partials
+// per workgroup and source in the caller's scratch, and finalize_rows_kernel with one workgroup per (view, source).  Counts are integers.  The partition depends on (H, W) only.  No float
 // atomics, no workgroup waits on another.
 //
 // Backward: a gather per pixel that recomputes S and the selection from the inputs; every pixel of g_depth / g_alpha is
 // written by exactly one thread.  The forward saves nothing.
-#include "fs_common.h"
-
-#include <math.h>
+#include "fs_reduce.h"
 
 #include "../../include/freesplat_amd_mvdepth.h"
 
@@ -35,7 +32,7 @@ namespace fs {
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / kWave;
+constexpr int kWaves = kSumWaves;
 constexpr int kVec = 4;                              // pixels of a group: one 16-byte access per plane
 constexpr int kChunk = kThreads * kVec;              // pixels per workgroup (freesplat_amd/mv_depth_loss.py CHUNK)
 constexpr int kMaxK = FS_MVDEPTH_MAX_SOURCES;
@@ -44,42 +41,6 @@ constexpr float kEps = 1e-8f;                        // the projection's epsilon
 struct Params {
     float occlusion, min_depth, max_depth, alpha_floor;
 };
-
-struct Px4 {
-    float v[kVec];
-};
-
-// the four pixels p0 .. p0 + 3 of a plane; a pixel at or beyond P reads nothing and is 0
-__device__ __forceinline__ Px4 load4(const float* __restrict__ plane, long long p0, long long P, bool aligned)
-{
-    Px4 r;
-    if (aligned && p0 + kVec <= P) {
-        const float4 q = *reinterpret_cast<const float4*>(plane + p0);
-        r.v[0] = q.x; r.v[1] = q.y; r.v[2] = q.z; r.v[3] = q.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < kVec; ++j) r.v[j] = p0 + j < P ? plane[p0 + j] : 0.0f;
-    }
-    return r;
-}
-
-__device__ __forceinline__ void store4(float* __restrict__ plane, long long p0, long long P, bool aligned, const Px4& r)
-{
-    if (aligned && p0 + kVec <= P) {
-        *reinterpret_cast<float4*>(plane + p0) = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
-    } else {
-#pragma unroll
-        for (int j = 0; j < kVec; ++j)
-            if (p0 + j < P) plane[p0 + j] = r.v[j];
-    }
-}
-
-__device__ __forceinline__ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-__device__ __forceinline__ bool valid_depth(float g, const Params& P)
-{
-    return fabsf(g) < INFINITY && g > P.min_depth && g < P.max_depth;       // (NaN fails every comparison)
-}
 
 // log of a positive finite double in the fp32 range: logf of the value rounded to fp32 (its error is relative to the RESULT)
 // plus the first-order term of the 6e-8 the rounding dropped (the second-order term is 2e-15).  A value near the ends of the
@@ -121,8 +82,8 @@ __device__ __forceinline__ Group load_group(long long p0, long long P, int W, co
         G.g[j] = g.v[j];
         G.al[j] = a.v[j];
         G.m[j] = alpha ? fmaxf(a.v[j], Q.alpha_floor) : 1.0f;
-        G.v0[j] = p0 + j < P && valid_depth(g.v[j], Q);
-        G.E[j] = alpha ? (double)d.v[j] / (double)G.m[j] : (double)d.v[j];
+        G.v0[j] = p0 + j < P && valid_depth(g.v[j], Q.min_depth, Q.max_depth);
+        G.E[j] = expected_depth<double>(d.v[j], a.v[j], alpha != nullptr, Q.alpha_floor);
         G.xf[j] = (float)x;
         G.yf[j] = (float)y;
         if (++x == W) {
@@ -179,25 +140,10 @@ __device__ __forceinline__ bool select(const Pair& M, const Group& G, int j, int
     const int ix = (int)u, iy = (int)v;
     if (ix >= Ws || iy >= Hs) return false;            // ((float)Ws may have rounded up)
     S = M.src[(size_t)iy * Ws + ix];
-    if (!(valid_depth(S, Q) && zq > 0.0f && zq < Q.occlusion * S)) return false;
+    if (!(valid_depth(S, Q.min_depth, Q.max_depth) && zq > 0.0f && zq < Q.occlusion * S)) return false;
     a2 = fma((double)M.a[6], (double)x, fma((double)M.a[7], (double)y, (double)M.a[8]));
     zp = fma(G.E[j], a2, (double)M.t[2]) + (double)kEps;
     return fabs(zp) < (double)INFINITY && zp > 0.0;
-}
-
-// fixed-order sum over the 64 lanes of a wavefront; the total is valid in lane 0
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
-    return v;
-}
-
-__device__ __forceinline__ int wave_sum(int v)
-{
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
-    return v;
 }
 
 // rows [blockIdx.x][K][2]: the workgroup's sum and count per source.  RES: residual [B,K,H,W] is written too.
@@ -252,10 +198,10 @@ __global__ __launch_bounds__(kThreads) void mv_fwd_kernel(int K, int H, int W, i
     __syncthreads();
     if (t < K) {
         double* row = rows + ((size_t)blockIdx.x * K + t) * 2;
-        row[0] = ((s_sum[0][t] + s_sum[1][t]) + s_sum[2][t]) + s_sum[3][t];
-        row[1] = (double)(((s_cnt[0][t] + s_cnt[1][t]) + s_cnt[2][t]) + s_cnt[3][t]);
+        row[0] = waves_total(&s_sum[0][t], kMaxK);
+        row[1] = (double)waves_total(&s_cnt[0][t], kMaxK);
     }
-    static_assert(kWaves == 4 && kMaxK <= kThreads, "the last step adds four wavefronts, one thread per source");
+    static_assert(kMaxK <= kThreads, "the last step takes one thread per source");
 }
 
 // g_E = sum over the sources that select the pixel of g_sum[b,k] sgn(r) a[2] / z_p', then the chain through alpha
@@ -335,20 +281,15 @@ __global__ __launch_bounds__(kThreads) void si_fwd_kernel(int H, int W, int chun
             ++n;
         }
     }
-    s1 = wave_sum(s1);
-    s2 = wave_sum(s2);
     n = wave_sum(n);
-    if ((t & (kWave - 1)) == 0) {
-        s_sum[t / kWave][0] = s1;
-        s_sum[t / kWave][1] = s2;
-        s_cnt[t / kWave] = n;
-    }
-    __syncthreads();
+    if ((t & (kWave - 1)) == 0) s_cnt[t / kWave] = n;
+    double s[2] = {s1, s2};
+    block_sum_waves<2>(s, &s_sum[0][0]);                   // (its barrier publishes s_cnt too)
     if (t == 0) {
         double* row = rows + (size_t)blockIdx.x * 3;
-        row[0] = ((s_sum[0][0] + s_sum[1][0]) + s_sum[2][0]) + s_sum[3][0];
-        row[1] = ((s_sum[0][1] + s_sum[1][1]) + s_sum[2][1]) + s_sum[3][1];
-        row[2] = (double)(((s_cnt[0] + s_cnt[1]) + s_cnt[2]) + s_cnt[3]);
+        row[0] = s[0];
+        row[1] = s[1];
+        row[2] = (double)waves_total(s_cnt, 1);
     }
 }
 
@@ -381,38 +322,6 @@ __global__ __launch_bounds__(kThreads) void si_bwd_kernel(int H, int W, int chun
     }
     store4(g_depth + base, G.p0, P, aligned16(g_depth + base), gd);
     if (alpha) store4(g_alpha + base, G.p0, P, aligned16(g_alpha + base), ga);
-}
-
-// One workgroup per (view, group g of G): rows [view][chunk][G][F] -> out_f[view * G + g], the chunks strided over the threads
-// in index order, then the fixed tree.
-template <int F>
-struct Outs {
-    double* p[F];
-};
-
-template <int F>
-__global__ __launch_bounds__(kThreads) void finalize_kernel(int chunks, int G, const double* __restrict__ rows, Outs<F> out)
-{
-    __shared__ double s_red[kWaves][F];
-    const int t = threadIdx.x;
-    const long long view = blockIdx.x / G;
-    const int g = (int)(blockIdx.x - view * G);
-    const double* r = rows + ((size_t)view * chunks * G + g) * F;
-    double v[F];
-#pragma unroll
-    for (int f = 0; f < F; ++f) v[f] = 0.0;
-    for (int c = t; c < chunks; c += kThreads)
-#pragma unroll
-        for (int f = 0; f < F; ++f) v[f] += r[(size_t)c * G * F + f];
-#pragma unroll
-    for (int f = 0; f < F; ++f) v[f] = wave_sum(v[f]);
-    if ((t & (kWave - 1)) == 0)
-#pragma unroll
-        for (int f = 0; f < F; ++f) s_red[t / kWave][f] = v[f];
-    __syncthreads();
-    if (t == 0)
-#pragma unroll
-        for (int f = 0; f < F; ++f) out.p[f][blockIdx.x] = ((s_red[0][f] + s_red[1][f]) + s_red[2][f]) + s_red[3][f];
 }
 
 struct Grid {
@@ -485,8 +394,8 @@ FS_API int fs_mv_depth_forward(int32_t B, int32_t K, int32_t H, int32_t W, int32
     else
         hipLaunchKernelGGL((mv_fwd_kernel<false>), dim3(g.blocks), dim3(kThreads), 0, st, K, H, W, Hs, Ws, S_pool, g.chunks, depth, gt,
                            alpha, src_depth, (const int*)src_index, pairs, Q, rows, residual);
-    hipLaunchKernelGGL((finalize_kernel<2>), dim3((unsigned)(B * K)), dim3(kThreads), 0, st, g.chunks, K, (const double*)rows,
-                       Outs<2>{{sum, cnt}});
+    hipLaunchKernelGGL((finalize_rows_kernel<2, BlockSum::kWaves, false>), dim3((unsigned)(B * K)), dim3(kThreads), 0, st, g.chunks, K,
+                       (const double*)rows, RowOuts<2>{{sum, cnt}, {}, 1});
     FS_CHECK_LAUNCH("mv_depth_forward");
     return FS_OK;
 }
@@ -519,8 +428,8 @@ FS_API int fs_si_depth_forward(int32_t B, int32_t H, int32_t W, const float* dep
     hipStream_t st = (hipStream_t)stream_;
     double* rows = static_cast<double*>(scratch);
     hipLaunchKernelGGL(si_fwd_kernel, dim3(g.blocks), dim3(kThreads), 0, st, H, W, g.chunks, depth, gt, alpha, Q, rows);
-    hipLaunchKernelGGL((finalize_kernel<3>), dim3((unsigned)B), dim3(kThreads), 0, st, g.chunks, 1, (const double*)rows,
-                       Outs<3>{{s1, s2, n}});
+    hipLaunchKernelGGL((finalize_rows_kernel<3, BlockSum::kWaves, false>), dim3((unsigned)B), dim3(kThreads), 0, st, g.chunks, 1,
+                       (const double*)rows, RowOuts<3>{{s1, s2, n}, {}, 1});
     FS_CHECK_LAUNCH("si_depth_forward");
     return FS_OK;
 }

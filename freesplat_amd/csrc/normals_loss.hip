@@ -9,9 +9,9 @@
 //
 // Forward: a workgroup owns kTileW x kTileH pixels, loads the depth (and the target depth) with a halo of 3 (blur 2 + Sobel 1;
 // 1 without smoothing) into LDS, runs the blur separably and forms its pixels' normals from LDS.  The loss form never writes a
-// normal: the pixel's 0.5 (1 - n . t) goes into the thread's fp64 sum, a fixed fp64 tree gives one partial row per workgroup, a
-// finalize workgroup per view adds the rows in a fixed order.  The partition depends only on (H, W).  No float atomics (the
-// one LDS atomic is an integer min, whose result does not depend on the order).
+// normal: the pixel's 0.5 (1 - n . t) goes into the thread's fp64 sum, block_sum_tree (fs_reduce.h) gives one partial row per
+// workgroup, finalize_rows_kernel adds a view's rows.  The partition depends only on (H, W).  No float atomics (the one LDS
+// atomic is an integer min, whose result does not depend on the order).
 //
 // Arithmetic: fp32 up to the two Sobel vectors, with the depth patch carried relative to its smallest valid depth
 // (build_map()), fp64 from the cross product on (normal_at()): both because the quantities cancel.
@@ -23,9 +23,7 @@
 // with its own ray: the cotangent of S; every tile pixel then collects the (at most 25) blur outputs that read it, the clamp
 // again folded into 1-D weights, and applies dE / d depth and dE / d alpha.  Without smoothing the halos are 2 / 1 / 0 and
 // the last step falls away (an instantiation of its own).  Every output element is written by exactly one thread.
-#include "fs_common.h"
-
-#include <math.h>
+#include "fs_reduce.h"
 
 #include "../../include/freesplat_amd_normals.h"
 
@@ -61,34 +59,16 @@ struct Params {
     double wsum2;                             // (sum of the five rounded weights)^2: what the blur makes of a constant 1
 };
 
-struct Row {                                  // one workgroup's partial sums
+struct Row {                                  // one workgroup's partial sums: finalize_rows_kernel reads them as double[2]
     double sum, cnt;
 };
-
-// fixed-order fp64 tree over the 256 threads of a workgroup; the totals end up in v[] of every thread
-template <int F>
-__device__ __forceinline__ void block_sum(double (&v)[F], double* s_red /* [F][kThreads] */)
-{
-    const int t = threadIdx.x;
-#pragma unroll
-    for (int f = 0; f < F; ++f) s_red[f * kThreads + t] = v[f];
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (t < s)
-#pragma unroll
-            for (int f = 0; f < F; ++f) s_red[f * kThreads + t] += s_red[f * kThreads + t + s];
-        __syncthreads();
-    }
-#pragma unroll
-    for (int f = 0; f < F; ++f) v[f] = s_red[f * kThreads];
-}
 
 __device__ __forceinline__ float nanf32() { return __builtin_nanf(""); }
 
 // expected depth of a pixel, NaN when invalid; `thresholds`: min_depth / max_depth apply too (the normal-map form)
-__device__ __forceinline__ float expected_depth(float d, float al, bool has_alpha, bool thresholds, const Params& P)
+__device__ __forceinline__ float checked_depth(float d, float al, bool has_alpha, bool thresholds, const Params& P)
 {
-    const float E = has_alpha ? d / fmaxf(al, P.alpha_floor) : d;
+    const float E = expected_depth<float>(d, al, has_alpha, P.alpha_floor);
     bool ok = fabsf(E) < INFINITY && E > 0.0f;                                  // (NaN fails every comparison)
     if (thresholds) ok = ok && E > P.min_depth && E < P.max_depth;
     return ok ? E : nanf32();
@@ -96,7 +76,7 @@ __device__ __forceinline__ float expected_depth(float d, float al, bool has_alph
 
 __device__ __forceinline__ float target_depth(float g, const Params& P)
 {
-    return (fabsf(g) < INFINITY && g > P.min_depth && g < P.max_depth) ? g : nanf32();
+    return valid_depth(g, P.min_depth, P.max_depth) ? g : nanf32();
 }
 
 // v[k]: the depth (NaN = invalid) of patch element t + k * kThreads at its clamped coordinate.  Leaves the smoothed patch in
@@ -272,7 +252,7 @@ __global__ __launch_bounds__(kThreads) void normals_fwd_kernel(int H, int W, int
     }
 #pragma unroll
     for (int k = 0; k < G::kEIters; ++k) {
-        v_d[k] = expected_depth(v_d[k], v_a[k], alpha != nullptr, MODE == kMap, P);
+        v_d[k] = checked_depth(v_d[k], v_a[k], alpha != nullptr, MODE == kMap, P);
         v_g[k] = target_depth(v_g[k], P);
     }
     const float c_s = build_map<SMOOTH, 0>(v_d, P, x0, y0, H, W, s_e, s_h, s_s, &s_min);
@@ -310,26 +290,8 @@ __global__ __launch_bounds__(kThreads) void normals_fwd_kernel(int H, int W, int
     }
     if constexpr (MODE != kMap) {
         double v[2] = {sum, (double)cnt};
-        block_sum<2>(v, s_red);
+        block_sum_tree<2>(v, s_red);
         if (t == 0) rows[blockIdx.x] = Row{v[0], v[1]};
-    }
-}
-
-// one workgroup per view: the view's partial rows in a fixed order
-__global__ __launch_bounds__(kThreads) void normals_finalize_kernel(int tiles, const Row* __restrict__ rows, double* __restrict__ sum,
-                                                                    double* __restrict__ cnt)
-{
-    __shared__ double s_red[2 * kThreads];
-    const Row* r = rows + (long long)blockIdx.x * tiles;
-    double v[2] = {0.0, 0.0};
-    for (int k = threadIdx.x; k < tiles; k += kThreads) {
-        v[0] += r[k].sum;
-        v[1] += r[k].cnt;
-    }
-    block_sum<2>(v, s_red);
-    if (threadIdx.x == 0) {
-        sum[blockIdx.x] = v[0];
-        cnt[blockIdx.x] = v[1];
     }
 }
 
@@ -405,7 +367,7 @@ __global__ __launch_bounds__(kThreads) void normals_bwd_kernel(int H, int W, int
     }
 #pragma unroll
     for (int k = 0; k < G::kEIters; ++k) {
-        v_d[k] = expected_depth(v_d[k], v_a[k], alpha != nullptr, MODE == kMap, P);
+        v_d[k] = checked_depth(v_d[k], v_a[k], alpha != nullptr, MODE == kMap, P);
         v_g[k] = target_depth(v_g[k], P);
     }
     const float c_s = build_map<SMOOTH, RN>(v_d, P, x0, y0, H, W, s_e, s_h, s_s, &s_min);
@@ -529,7 +491,7 @@ __global__ __launch_bounds__(kThreads) void normals_bwd_kernel(int H, int W, int
             dE = cot_S(y, x, ly + RN, lx + RN);
         }
         const float al = own_a[k];
-        const float E = expected_depth(own_d[k], al, alpha != nullptr, MODE == kMap, P);
+        const float E = checked_depth(own_d[k], al, alpha != nullptr, MODE == kMap, P);
         float gd = 0.0f, ga = 0.0f;
         if (E == E) {                                            // an invalid pixel receives exactly 0
             if (alpha) {
@@ -668,7 +630,8 @@ FS_API int fs_normals_loss_forward(int32_t B, int32_t H, int32_t W, const float*
         launch_fwd<kGtDepth>(sigma > 0.0f, grid, st, H, W, g, depth, alpha, intrinsics, gt_depth, nullptr, P, nullptr, rows);
     else
         launch_fwd<kGtNormals>(sigma > 0.0f, grid, st, H, W, g, depth, alpha, intrinsics, nullptr, gt_normals, P, nullptr, rows);
-    hipLaunchKernelGGL(normals_finalize_kernel, dim3((unsigned)B), dim3(kThreads), 0, st, g.tiles, (const Row*)rows, sum, cnt);
+    hipLaunchKernelGGL((finalize_rows_kernel<2, BlockSum::kTree, false>), dim3((unsigned)B), dim3(kThreads), 0, st, g.tiles, 1,
+                       reinterpret_cast<const double*>(rows), RowOuts<2>{{sum, cnt}, {}, 1});
     FS_CHECK_LAUNCH("normals_loss_forward");
     return FS_OK;
 }

@@ -1,24 +1,18 @@
 // ssim_loss.hip -- differentiable SSIM + L1 photometric loss (include/freesplat_amd_loss.h), forward and backward.
 //
-// The forward is the tiled pass of metrics.hip's ssim_tile_kernel with two conventions behind one template parameter
-// (PAD = false: skimage's cropped SSIM; PAD = true: the zero-padded `same` form of 3DGS-style training code): a workgroup
-// owns kTileW x kTileH pixels of one (view, channel) plane,
-//   vertical 11-tap pass: one thread per patch column (kTileW + 10 = 256) sliding down the rows with the inputs of the last
-//     10 + kRows rows in registers, the five moments of kRows rows go to LDS;
-//   horizontal 11-tap pass: a thread takes 4 consecutive outputs of a row (16-byte LDS reads), forms S, adds it to its
-//     partial when the output is one the convention averages and, when a backward will follow, stores the three
-//     partial-derivative maps of that output (12 bytes).
-// |pred - gt| of a pixel is added once, by the thread of its column, while the row passes through registers.
+// The forward is the tiled pass of metrics.hip's ssim_tile_kernel, built from the same pieces (ssim_pass.h), with two
+// conventions behind one template parameter (PAD = false: skimage's cropped SSIM; PAD = true: the zero-padded `same` form of
+// 3DGS-style training code) and |pred - gt| in place of the squared error; when a backward will follow it stores the three
+// partial-derivative maps of every averaged output (12 bytes).  The two kernel bodies stay apart: merged into one inlined
+// function template they compile to 14 - 17 more VGPRs each (DESIGN.md "Helper headers").
 //
 // The backward is a gather: a workgroup owns kTileW x kTileH pixels of g_pred, runs the same two passes over the three
 // saved maps (zero outside the averaged outputs) and combines them with pred and gt of the pixel.  Every pixel of g_pred is
 // written by exactly one thread; nothing is accumulated in memory.
 //
-// Deterministic as metrics.hip: per-thread fp32 sums in a fixed order (|pred - gt| in fp64), a fixed fp64 tree per
-// workgroup, one partial row per workgroup, a finalize kernel per view.  The partition depends only on (C, H, W).  No atomics.
-#include "fs_common.h"
-
-#include <math.h>
+// Deterministic as metrics.hip: per-thread fp32 sums in a fixed order (|pred - gt| in fp64), then block_sum_tree and
+// finalize_rows_kernel of fs_reduce.h.  The partition depends only on (C, H, W).  No atomics.
+#include "ssim_pass.h"
 
 #include "../../include/freesplat_amd_loss.h"
 
@@ -26,65 +20,9 @@ namespace fs {
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kRad = 5;                       // sigma 1.5, truncate 3.5
-constexpr int kTaps = 2 * kRad + 1;
-constexpr int kTileW = kThreads - 2 * kRad;   // 246 columns per workgroup: patch column = thread
-constexpr int kTileH = 64;                    // rows per workgroup
-constexpr int kRows = 8;                      // rows per LDS round
-constexpr int kGroups = (kTileW + 3) / 4;     // 62 groups of 4 columns in the horizontal pass
-constexpr int kLdsRow = 260;                  // >= 4 * (kGroups - 1) + 16: the last group's 16-byte reads stay in the row
-constexpr float kC1 = 0.01f * 0.01f, kC2 = 0.03f * 0.03f;
-constexpr float kMid = 0.5f;                  // the saved G*y map and the backward's pred / gt factors are taken about this
+using namespace ssim;
 
-struct Weights {
-    float w[kTaps];
-};
-
-// Gaussian weights as scipy.ndimage builds them: exp(-k^2 / (2 sigma^2)) normalised in double, k = -5..5
-Weights make_weights()
-{
-    Weights wt;
-    double e[kTaps], sum = 0.0;
-    for (int k = 0; k < kTaps; ++k) {
-        const double d = k - kRad;
-        e[k] = exp(-0.5 * d * d / (1.5 * 1.5));
-        sum += e[k];
-    }
-    for (int k = 0; k < kTaps; ++k) wt.w[k] = (float)(e[k] / sum);
-    return wt;
-}
-
-// fixed-order fp64 tree over the 256 threads of a workgroup; the totals end up in v[] of every thread
-template <int F>
-__device__ __forceinline__ void block_sum(double (&v)[F], double* s_red /* [F][kThreads] */)
-{
-    const int t = threadIdx.x;
-#pragma unroll
-    for (int f = 0; f < F; ++f) s_red[f * kThreads + t] = v[f];
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (t < s)
-#pragma unroll
-            for (int f = 0; f < F; ++f) s_red[f * kThreads + t] += s_red[f * kThreads + t + s];
-        __syncthreads();
-    }
-#pragma unroll
-    for (int f = 0; f < F; ++f) v[f] = s_red[f * kThreads];
-}
-
-// 4 consecutive floats of a row: one 16-byte store where the address allows it and all four belong to the row
-__device__ __forceinline__ void store4(float* __restrict__ row, int col, int n_cols, const float (&v)[4])
-{
-    float* p = row + col;
-    if (col + 3 < n_cols && (reinterpret_cast<uintptr_t>(p) & 15u) == 0) {
-        *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (col + q < n_cols) p[q] = v[q];
-    }
-}
+constexpr int kThreads = kSumThreads;
 
 // One (view, channel) plane tile.  blockIdx.x = plane * tiles + tile; rows[blockIdx.x] = (sum of S, sum of |pred - gt|).
 // x = gt, y = pred (the side that gets the gradient).  saved: NULL or [planes][3][Hm][Wm] with (Hm, Wm) the averaged
@@ -114,21 +52,18 @@ __global__ __launch_bounds__(kThreads) void ssim_loss_fwd_kernel(int H, int W, i
     for (int k = 0; k < kTaps; ++k) w[k] = wt.w[k];
     constexpr float kF = PAD ? 1.0f : 121.0f / 120.0f;       // population / sample covariance (NP / (NP - 1), NP = 11^2)
 
-    // The moments are taken about a per-tile pivot: metrics.hip's remedy for the cancellation in u_xx - u_x^2.  A tile whose
-    // patch lies inside the image takes the value of its first pixel in each image (0.5 where that is not finite or lies
-    // outside [-1, 2]), as the metric kernel does.  A pixel outside the image is the raw value 0 (the zero padding of PAD;
-    // never part of a kept window otherwise), i.e. -pivot here: the weights sum to 1 over the whole window, so the shift
-    // stays exact under padding.  A tile whose patch reaches into the padding takes HALF that value, midway between the
-    // padding and the image, so that neither side's centred magnitude exceeds the raw one (about the pixel value itself
-    // the padding of a bright image is as far from the pivot as it can be: 4x the gradient error at 11 x 11 with values
-    // up to 1.4).  An image smaller than the window keeps its raw values (pivot 0): there a window is mostly padding and
-    // u = pivot + (mean of the centred values) would cancel down to the small in-image weight (1 x 1: 0.07); with an
-    // image of at least 11 in both axes a window keeps >= 0.4 of its weight inside.
+    // The per-tile pivot (pivot_of) under padding.  A pixel outside the image is the raw value 0 (the zero padding of PAD; never
+    // part of a kept window otherwise), i.e. -pivot here: the weights sum to 1 over the whole window, so the shift stays exact
+    // under padding.  A tile whose patch reaches into the padding takes HALF the pivot, midway between the padding and the
+    // image, so that neither side's centred magnitude exceeds the raw one (about the pixel value itself the padding of a bright
+    // image is as far from the pivot as it can be: 4x the gradient error at 11 x 11 with values up to 1.4).  An image smaller
+    // than the window keeps its raw values (pivot 0): there a window is mostly padding and u = pivot + (mean of the centred
+    // values) would cancel down to the small in-image weight (1 x 1: 0.07); with an image of at least 11 in both axes a window
+    // keeps >= 0.4 of its weight inside.
     const bool raw = PAD && (H < kTaps || W < kTaps);
     const bool edge = PAD && (x0 < kRad || y0 < kRad || x0 + kTileW + kRad > W || y0 + kTileH + kRad > H);
     const float pivot_scale = raw ? 0.0f : (edge ? 0.5f : 1.0f);
-    auto offset = [](float v) { return v >= -1.0f && v <= 2.0f ? v : 0.5f; };
-    const float ox = pivot_scale * offset(gx_[(size_t)y0 * W + x0]), oy = pivot_scale * offset(gy_[(size_t)y0 * W + x0]);
+    const float ox = pivot_scale * pivot_of(gx_[(size_t)y0 * W + x0]), oy = pivot_scale * pivot_of(gy_[(size_t)y0 * W + x0]);
     const int y_end = min(y0 + kTileH, H);
     float xr[kRows + 2 * kRad], yr[kRows + 2 * kRad];
     float s_sum = 0.0f;
@@ -148,21 +83,13 @@ __global__ __launch_bounds__(kThreads) void ssim_loss_fwd_kernel(int H, int W, i
         if (y0 + r0 >= H) break;                             // (workgroup-uniform; every row < H is loaded by now)
 #pragma unroll
         for (int i = 0; i < kRows; ++i) load(y0 + r0 + kRad + i, xr[2 * kRad + i], yr[2 * kRad + i]);
-        // vertical pass: the x- and y-terms take identical operation sequences (identical images give S = 1 exactly)
+        // vertical pass
 #pragma unroll
         for (int o = 0; o < kRows; ++o) {
-            float ux = 0.0f, uy = 0.0f, uxx = 0.0f, uyy = 0.0f, uxy = 0.0f;
+            float m[5];
+            column_moments(xr + o, yr + o, w, m);
 #pragma unroll
-            for (int k = 0; k < kTaps; ++k) {
-                const float x = xr[o + k], y = yr[o + k];
-                const float wx = w[k] * x, wy = w[k] * y;
-                ux += wx;
-                uy += wy;
-                uxx = fmaf(wx, x, uxx);
-                uyy = fmaf(wy, y, uyy);
-                uxy = fmaf(wx, y, uxy);
-            }
-            s_m[o][0][t] = ux; s_m[o][1][t] = uy; s_m[o][2][t] = uxx; s_m[o][3][t] = uyy; s_m[o][4][t] = uxy;
+            for (int k = 0; k < 5; ++k) s_m[o][k][t] = m[k];
         }
         __syncthreads();
         // horizontal pass + S (+ the three maps)
@@ -171,21 +98,7 @@ __global__ __launch_bounds__(kThreads) void ssim_loss_fwd_kernel(int H, int W, i
             const int yy = y0 + r0 + o;
             float u[5][4];
 #pragma unroll
-            for (int m = 0; m < 5; ++m) {
-                float v[16];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float4 f = *reinterpret_cast<const float4*>(&s_m[o][m][c0 + 4 * q]);
-                    v[4 * q] = f.x; v[4 * q + 1] = f.y; v[4 * q + 2] = f.z; v[4 * q + 3] = f.w;
-                }
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    float a = 0.0f;
-#pragma unroll
-                    for (int k = 0; k < kTaps; ++k) a = fmaf(w[k], v[q + k], a);
-                    u[m][q] = a;
-                }
-            }
+            for (int m = 0; m < 5; ++m) row_taps4(&s_m[o][m][c0], w, u[m]);
             const bool row_out = PAD ? yy < H : (yy >= kRad && yy < H - kRad);
             // columns of this group that are averaged outputs form one run [lo, hi) of q (the tile, the image and, without
             // padding, the crop each cut an interval)
@@ -195,33 +108,26 @@ __global__ __launch_bounds__(kThreads) void ssim_loss_fwd_kernel(int H, int W, i
             float p_yy[4], p_xy[4], p_y[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const float cx = u[0][q], cy = u[1][q];       // (means of the centred values)
-                const float vx = kF * (u[2][q] - cx * cx);
-                const float vy = kF * (u[3][q] - cy * cy);
-                const float vxy = kF * (u[4][q] - cx * cy);
-                const float ux = cx + ox, uy = cy + oy;
-                const float a1 = 2.0f * (ux * uy) + kC1, a2 = 2.0f * vxy + kC2;
-                const float b1 = (ux * ux + uy * uy) + kC1, b2 = (vx + vy) + kC2;
-                const float S = (a1 * a2) / (b1 * b2);
-                if (q >= lo && q < hi) s_sum += S;
+                const Terms T = ssim_terms(u[0][q], u[1][q], u[2][q], u[3][q], u[4][q], ox, oy, kF);
+                if (q >= lo && q < hi) s_sum += T.S;
                 if constexpr (!SAVE) continue;
                 // dS/d(G*y^2), dS/d(G*xy) and dS/d(G*y) with the two products' 0.5 moved into the last one.  Written so that
                 // identical images (a1 == b1, a2 == b2, S == 1 bit for bit) give P_xy == -2 P_yy and P_y == 0 exactly: the
                 // two ratios that must be 1 there are true divisions, the common factors 1-ulp reciprocals.
-                const float inv_b2 = kF * __builtin_amdgcn_rcpf(b2);
-                p_yy[q] = -(S * inv_b2);
-                p_xy[q] = 2.0f * ((a1 / b1) * inv_b2);
-                const float dx = cx + (ox - kMid), dy = cy + (oy - kMid);
-                p_y[q] = (2.0f * __builtin_amdgcn_rcpf(b1)) * (ux * (a2 / b2) - uy * S) - ((2.0f * dy) * p_yy[q] + dx * p_xy[q]);
+                const float inv_b2 = kF * __builtin_amdgcn_rcpf(T.b2);
+                p_yy[q] = -(T.S * inv_b2);
+                p_xy[q] = 2.0f * ((T.a1 / T.b1) * inv_b2);
+                const float dx = T.cx + (ox - kMid), dy = T.cy + (oy - kMid);
+                p_y[q] = (2.0f * __builtin_amdgcn_rcpf(T.b1)) * (T.ux * (T.a2 / T.b2) - T.uy * T.S) - ((2.0f * dy) * p_yy[q] + dx * p_xy[q]);
             }
             if (SAVE && hi > lo) {
                 const size_t ro = (size_t)(yy - off) * Wm;
                 const size_t mp = (size_t)Hm * Wm;
                 if (lo == 0) {
-                    const int n = xx0 - off + hi;             // store4 writes columns [xx0 - off, n)
-                    store4(sv + ro, xx0 - off, n, p_yy);
-                    store4(sv + mp + ro, xx0 - off, n, p_xy);
-                    store4(sv + 2 * mp + ro, xx0 - off, n, p_y);
+                    const int n = xx0 - off + hi;             // store_row4 writes columns [xx0 - off, n)
+                    store_row4(sv + ro, xx0 - off, n, p_yy);
+                    store_row4(sv + mp + ro, xx0 - off, n, p_xy);
+                    store_row4(sv + 2 * mp + ro, xx0 - off, n, p_y);
                 } else {
 #pragma unroll
                     for (int q = 0; q < 4; ++q)
@@ -237,7 +143,7 @@ __global__ __launch_bounds__(kThreads) void ssim_loss_fwd_kernel(int H, int W, i
         for (int i = 0; i < 2 * kRad; ++i) { xr[i] = xr[kRows + i]; yr[i] = yr[kRows + i]; }
     }
     double v[2] = {(double)s_sum, l_sum};
-    block_sum<2>(v, reinterpret_cast<double*>(&s_m[0][0][0]));   // (the moments are dead after the last barrier)
+    block_sum_tree<2>(v, reinterpret_cast<double*>(&s_m[0][0][0]));   // (the moments are dead after the last barrier)
     if (t == 0) rows[blockIdx.x] = make_double2(v[0], v[1]);
 }
 
@@ -313,21 +219,7 @@ __global__ __launch_bounds__(kThreads) void ssim_loss_bwd_kernel(int C, int H, i
             float u[3][4];
             if (has_ssim) {
 #pragma unroll
-                for (int m = 0; m < 3; ++m) {
-                    float v[16];
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const float4 f = *reinterpret_cast<const float4*>(&s_m[o][m][c0 + 4 * q]);
-                        v[4 * q] = f.x; v[4 * q + 1] = f.y; v[4 * q + 2] = f.z; v[4 * q + 3] = f.w;
-                    }
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        float a = 0.0f;
-#pragma unroll
-                        for (int k = 0; k < kTaps; ++k) a = fmaf(w[k], v[q + k], a);
-                        u[m][q] = a;
-                    }
-                }
+                for (int m = 0; m < 3; ++m) row_taps4(&s_m[o][m][c0], w, u[m]);
             }
             const size_t ro = base + (size_t)yy * W;
             float g[4];
@@ -346,7 +238,7 @@ __global__ __launch_bounds__(kThreads) void ssim_loss_bwd_kernel(int C, int H, i
                     g[q] = val;
                 }
             }
-            store4(g_pred + ro, xx0, xx0 + n, g);
+            store_row4(g_pred + ro, xx0, xx0 + n, g);
         }
         if (has_ssim) {
             __syncthreads();
@@ -354,32 +246,6 @@ __global__ __launch_bounds__(kThreads) void ssim_loss_bwd_kernel(int C, int H, i
             for (int i = 0; i < 2 * kRad; ++i) { m0[i] = m0[kRows + i]; m1[i] = m1[kRows + i]; m2[i] = m2[kRows + i]; }
         }
     }
-}
-
-// one workgroup per view: ssim[view], l1_mean[view] = scale * (sum of the view's K partial rows, in a fixed order)
-__global__ __launch_bounds__(kThreads) void ssim_loss_finalize_kernel(int K, const double2* __restrict__ rows, double scale_ssim,
-                                                                      double scale_l1, double* __restrict__ ssim,
-                                                                      double* __restrict__ l1_mean)
-{
-    __shared__ double s_red[2 * kThreads];
-    const int view = blockIdx.x;
-    const double2* r = rows + (size_t)view * K;
-    double v[2] = {0.0, 0.0};
-    for (int k = threadIdx.x; k < K; k += kThreads) {
-        v[0] += r[k].x;
-        v[1] += r[k].y;
-    }
-    block_sum<2>(v, s_red);
-    if (threadIdx.x == 0) {
-        ssim[view] = v[0] * scale_ssim;
-        l1_mean[view] = v[1] * scale_l1;
-    }
-}
-
-void plane_tiles(int H, int W, int& tiles_x, int& tiles)
-{
-    tiles_x = (W + kTileW - 1) / kTileW;
-    tiles = tiles_x * ((H + kTileH - 1) / kTileH);
 }
 
 bool args_ok(int32_t B, int32_t C, int32_t H, int32_t W, int32_t flags)
@@ -428,15 +294,16 @@ FS_API int fs_ssim_loss_forward(int32_t B, int32_t C, int32_t H, int32_t W, int3
     hipStream_t st = (hipStream_t)stream_;
     int tiles_x, tiles;
     plane_tiles(H, W, tiles_x, tiles);
-    const Weights wt = make_weights();
+    const Weights wt = Weights::make();
     double2* rows = static_cast<double2*>(scratch);
     const dim3 grid((unsigned)(B * C * tiles));
     const bool pad = flags == FS_SSIM_3DGS;
     auto kernel = pad ? (saved ? ssim_loss_fwd_kernel<true, true> : ssim_loss_fwd_kernel<true, false>)
                       : (saved ? ssim_loss_fwd_kernel<false, true> : ssim_loss_fwd_kernel<false, false>);
     hipLaunchKernelGGL(kernel, grid, dim3(kThreads), 0, st, H, W, tiles_x, tiles, pred, gt, wt, static_cast<float*>(saved), rows);
-    hipLaunchKernelGGL(ssim_loss_finalize_kernel, dim3((unsigned)B), dim3(kThreads), 0, st, C * tiles, rows,
-                       1.0 / ((double)C * (double)outputs(H, W, flags)), 1.0 / ((double)C * H * W), ssim, l1_mean);
+    const RowOuts<2> outs = {{ssim, l1_mean}, {1.0 / ((double)C * (double)outputs(H, W, flags)), 1.0 / ((double)C * H * W)}, 1};
+    hipLaunchKernelGGL((finalize_rows_kernel<2, BlockSum::kTree, true>), dim3((unsigned)B), dim3(kThreads), 0, st, C * tiles, 1,
+                       reinterpret_cast<const double*>(rows), outs);
     FS_CHECK_LAUNCH("ssim_loss_forward");
     return FS_OK;
 }
@@ -451,7 +318,7 @@ FS_API int fs_ssim_loss_backward(int32_t B, int32_t C, int32_t H, int32_t W, int
     hipStream_t st = (hipStream_t)stream_;
     int tiles_x, tiles;
     plane_tiles(H, W, tiles_x, tiles);
-    const Weights wt = make_weights();
+    const Weights wt = Weights::make();
     const float scale_ssim = (float)(1.0 / ((double)C * (double)outputs(H, W, flags)));
     const float scale_l1 = (float)(1.0 / ((double)C * H * W));
     const dim3 grid((unsigned)(B * C * tiles));

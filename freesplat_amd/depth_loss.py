@@ -21,12 +21,13 @@ import math
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _args, _lib
 
 TILE_W, TILE_H = 64, 32   # pixels of level 0 one workgroup owns (csrc/depth_loss.hip kTileW, kTileH); tests place shapes by it
 UPPER_TILE_H = 8          # ... and TILE_W x UPPER_TILE_H elements of a level above (kUpperTileH)
 MAX_SCALES = _lib.DEPTH_LOSS_MAX_SCALES
 MODES = {"log_l1": _lib.DEPTH_LOSS_LOG_L1, "l1": _lib.DEPTH_LOSS_L1}
+_NAME = "freesplat_amd.depth_loss"
 
 
 def _mode(mode: str) -> int:
@@ -41,34 +42,12 @@ def _scales(num_scales) -> int:
     return num_scales
 
 
-def _device_f32(t: Tensor, what: str) -> Tensor:
-    if not isinstance(t, Tensor) or t.device.type != "cuda":
-        raise ValueError(f"freesplat_amd.depth_loss: {what} must be a tensor on a HIP device (got "
-                         f"{getattr(t, 'device', type(t))}); there is no CPU path")
-    return t.float().contiguous()
-
-
 def _maps(depth: Tensor, gt: Tensor, alpha, mode: str, num_scales, min_depth, max_depth, alpha_floor):
     flags, S = _mode(mode), _scales(num_scales)
-    min_depth, max_depth, alpha_floor = float(min_depth), float(max_depth), float(alpha_floor)
-    if math.isnan(min_depth) or math.isnan(max_depth):
-        raise ValueError("freesplat_amd.depth_loss: min_depth / max_depth must not be NaN")
-    if not (alpha_floor > 0.0 and math.isfinite(alpha_floor)):
-        raise ValueError(f"freesplat_amd.depth_loss: alpha_floor must be a positive finite number, got {alpha_floor!r}")
-    if isinstance(gt, Tensor) and gt.requires_grad and torch.is_grad_enabled():
-        raise RuntimeError("freesplat_amd.depth_loss: gt gets no gradient from the fused loss; detach it (only `depth` and "
-                           "`alpha` are differentiated)")
-    d = _device_f32(depth, "depth")
-    g = _device_f32(gt, "gt").detach()
-    a = None if alpha is None else _device_f32(alpha, "alpha")
-    if d.dim() != 3 or d.shape != g.shape or (a is not None and a.shape != d.shape):
-        raise ValueError(f"freesplat_amd.depth_loss: expected [B, H, W] tensors of one shape, got {tuple(d.shape)}, "
-                         f"{tuple(g.shape)}" + ("" if a is None else f" and {tuple(a.shape)}"))
-    if d.device != g.device or (a is not None and a.device != d.device):
-        raise ValueError("freesplat_amd.depth_loss: tensors on different devices")
-    if d.numel() == 0:
-        raise ValueError("freesplat_amd.depth_loss: empty batch")
-    return d, g, a, flags, S, (min_depth, max_depth, alpha_floor)
+    scalars = _args.depth_scalars(min_depth, max_depth, alpha_floor, _NAME)
+    _args.no_grad_to(gt, "gt", _NAME)
+    d, a, g = _args.depth_maps(_NAME, depth, alpha, gt)
+    return d, g, a, flags, S, scalars
 
 
 def saved_bytes(B: int, H: int, W: int, num_scales: int = 4) -> int:
@@ -106,15 +85,11 @@ class _DepthLoss(torch.autograd.Function):
         if g_point is None and g_grad is None:
             return (None,) * 7
         depth, gt, saved = ctx.saved_tensors[:3]
-        alpha = ctx.saved_tensors[3] if ctx.has_alpha else None
+        alpha, (g_point, g_grad), g_depth, g_alpha = _args.backward_buffers(ctx, 3, g_point, g_grad)
         flags, S, scalars = ctx.args
         B, H, W = depth.shape
         L = _lib.lib()
-        g_point = None if g_point is None else g_point.float().contiguous()
-        g_grad = None if g_grad is None else g_grad.float().contiguous()
         scratch = torch.empty(L.fs_depth_loss_scratch_bytes(B, H, W, S), dtype=torch.uint8, device=depth.device)
-        g_depth = torch.empty(B, H, W, device=depth.device)
-        g_alpha = None if alpha is None else torch.empty(B, H, W, device=depth.device)
         p = _lib.ptr
         _lib.check(L.fs_depth_loss_backward(B, H, W, S, flags, p(depth), p(gt), p(alpha), *scalars, p(g_point), p(g_grad), p(saved),
                                             p(g_depth), p(g_alpha), p(scratch), _lib.current_stream()), "fs_depth_loss_backward")
@@ -127,7 +102,7 @@ def depth_loss_terms(depth: Tensor, gt: Tensor, alpha: Tensor | None = None, *, 
     differentiable with respect to `depth` and `alpha`."""
     d, g, a, flags, S, scalars = _maps(depth, gt, alpha, mode, num_scales, min_depth, max_depth, alpha_floor)
     saved = None
-    if torch.is_grad_enabled() and (d.requires_grad or (a is not None and a.requires_grad)):
+    if _args.pending(d, a):
         B, H, W = d.shape
         saved = torch.empty(_lib.lib().fs_depth_loss_saved_bytes(B, H, W, S) // 4, device=d.device)
     return _DepthLoss.apply(d, g, a, saved, flags, S, scalars)

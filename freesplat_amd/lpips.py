@@ -18,6 +18,7 @@ reference tree does not vendor it -- so a key that does not fit is a loud error 
 """
 from __future__ import annotations
 
+import functools
 import math
 import os
 from typing import Optional
@@ -25,7 +26,9 @@ from typing import Optional
 import torch
 from torch import Tensor, nn
 
-from . import _lib
+from . import _args, _lib
+
+_device_f32 = functools.partial(_args.device_f32, name="freesplat_amd.lpips")
 
 # VGG-16 `features`: (torchvision index, in, out) of every convolution of slice k; taps after relu1_2, relu2_2, relu3_3,
 # relu4_3, relu5_3.  Slices 2-5 open with a 2x2 max-pool (torchvision indices 4, 9, 16, 23).  [3P-from-memory]
@@ -52,13 +55,6 @@ def set_default_weights(weights) -> None:
     global _default_weights
     _default_weights = weights
     _modules.clear()
-
-
-def _device_f32(t: Tensor, what: str) -> Tensor:
-    if not isinstance(t, Tensor) or t.device.type != "cuda":
-        raise ValueError(f"freesplat_amd.lpips: {what} must be a tensor on a HIP device (got "
-                         f"{getattr(t, 'device', type(t))}); there is no CPU path")
-    return t.float().contiguous()
 
 
 # ---- the two library-backed autograd functions ----

@@ -12,17 +12,14 @@ from __future__ import annotations
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _args, _lib
 
 WIN = 11                # skimage raises "win_size exceeds image extent" below this
 DEPTH_THRESHOLD = 0.5   # model_wrapper.py:95 `gt_bN > 0.5`
 
 
 def _device_f32(t: Tensor, what: str) -> Tensor:
-    if not isinstance(t, Tensor) or t.device.type != "cuda":
-        raise ValueError(f"freesplat_amd.metrics: {what} must be a tensor on a HIP device (got "
-                         f"{getattr(t, 'device', type(t))}); there is no CPU path")
-    return t.detach().float().contiguous()
+    return _args.device_f32(t, what, "freesplat_amd.metrics").detach()
 
 
 def _images(ground_truth: Tensor, predicted: Tensor):

@@ -39,61 +39,35 @@ import math
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _args, _lib
 
 CHUNK = 1024              # pixels one workgroup owns (csrc/mv_depth_loss.hip kChunk); tests place shapes by it
 MAX_SOURCES = _lib.MVDEPTH_MAX_SOURCES
 _NAME = "freesplat_amd.mv_depth_loss"
 
 
-def _device_f32(t, what: str) -> Tensor:
-    if not isinstance(t, Tensor) or t.device.type != "cuda":
-        raise ValueError(f"{_NAME}: {what} must be a tensor on a HIP device (got {getattr(t, 'device', type(t))}); "
-                         "there is no CPU path")
-    return t.float().contiguous()
-
-
 def _scalars(min_depth, max_depth, alpha_floor, occlusion=None):
-    min_depth, max_depth, alpha_floor = float(min_depth), float(max_depth), float(alpha_floor)
-    if math.isnan(min_depth) or math.isnan(max_depth):
-        raise ValueError(f"{_NAME}: min_depth / max_depth must not be NaN")
-    if not (alpha_floor > 0.0 and math.isfinite(alpha_floor)):
-        raise ValueError(f"{_NAME}: alpha_floor must be a positive finite number, got {alpha_floor!r}")
+    scalars = _args.depth_scalars(min_depth, max_depth, alpha_floor, _NAME)
     if occlusion is None:
-        return min_depth, max_depth, alpha_floor
+        return scalars
     occlusion = float(occlusion)
     if not (occlusion > 0.0 and math.isfinite(occlusion)):
         raise ValueError(f"{_NAME}: occlusion must be a positive finite factor, got {occlusion!r}")
-    return occlusion, min_depth, max_depth, alpha_floor
-
-
-def _no_grad_to(t, what: str) -> None:
-    if isinstance(t, Tensor) and t.requires_grad and torch.is_grad_enabled():
-        raise RuntimeError(f"{_NAME}: {what} gets no gradient from the fused loss; detach it (only `depth` and `alpha` are "
-                           "differentiated)")
+    return (occlusion, *scalars)
 
 
 def _maps(depth, gt, alpha):
-    _no_grad_to(gt, "gt")
-    d = _device_f32(depth, "depth")
-    g = _device_f32(gt, "gt").detach()
-    a = None if alpha is None else _device_f32(alpha, "alpha")
-    if d.dim() != 3 or d.shape != g.shape or (a is not None and a.shape != d.shape):
-        raise ValueError(f"{_NAME}: expected [B, H, W] tensors of one shape, got {tuple(d.shape)}, {tuple(g.shape)}"
-                         + ("" if a is None else f" and {tuple(a.shape)}"))
-    if d.device != g.device or (a is not None and a.device != d.device):
-        raise ValueError(f"{_NAME}: tensors on different devices")
-    if d.numel() == 0:
-        raise ValueError(f"{_NAME}: empty batch")
+    _args.no_grad_to(gt, "gt", _NAME)
+    d, a, g = _args.depth_maps(_NAME, depth, alpha, gt)
     return d, g, a
 
 
 def _sources(d: Tensor, src_depth, pairs, src_index):
     """-> (src [B, K, Hs, Ws] | [S, Hs, Ws], pairs [B, K, 3, 4], src_index [B, K] int32 | None, K, S_pool)."""
-    _no_grad_to(src_depth, "src_depth")
+    _args.no_grad_to(src_depth, "src_depth", _NAME)
     B = d.shape[0]
-    s = _device_f32(src_depth, "src_depth").detach()
-    q = _device_f32(pairs, "pairs").detach()
+    s = _args.device_f32(src_depth, "src_depth", _NAME).detach()
+    q = _args.device_f32(pairs, "pairs", _NAME).detach()
     if q.dim() != 4 or q.shape[0] != B or tuple(q.shape[2:]) != (3, 4):
         raise ValueError(f"{_NAME}: pairs must be [{B}, K, 3, 4] (pair_transforms), got {tuple(q.shape)}")
     K = q.shape[1]
@@ -118,10 +92,6 @@ def _sources(d: Tensor, src_depth, pairs, src_index):
     if s.device != d.device or q.device != d.device:
         raise ValueError(f"{_NAME}: tensors on different devices")
     return s, q, idx, K, S_pool
-
-
-def _pending(d: Tensor, a) -> bool:
-    return torch.is_grad_enabled() and (d.requires_grad or (a is not None and a.requires_grad))
 
 
 def _intr(k, lead, what: str, dtype, device) -> Tensor:
@@ -206,15 +176,11 @@ class _MVDepth(torch.autograd.Function):
         if g_sum is None:
             return (None,) * 10
         depth, gt, src, pairs = ctx.saved_tensors[:4]
-        rest = list(ctx.saved_tensors[4:])
-        alpha = rest.pop(0) if ctx.has_alpha else None
-        idx = rest.pop(0) if ctx.has_index else None
+        alpha, (g_sum,), g_depth, g_alpha = _args.backward_buffers(ctx, 4, g_sum)
+        idx = ctx.saved_tensors[-1] if ctx.has_index else None
         K, S_pool, scalars = ctx.args
         B, H, W = depth.shape
         Hs, Ws = src.shape[-2:]
-        g_sum = g_sum.float().contiguous()
-        g_depth = torch.empty(B, H, W, device=depth.device)
-        g_alpha = None if alpha is None else torch.empty(B, H, W, device=depth.device)
         p = _lib.ptr
         _lib.check(_lib.lib().fs_mv_depth_backward(B, K, H, W, Hs, Ws, S_pool, p(depth), p(gt), p(alpha), p(src), p(idx), p(pairs),
                                                    *scalars, p(g_sum), p(g_depth), p(g_alpha), _lib.current_stream()),
@@ -249,11 +215,9 @@ class _SIDepth(torch.autograd.Function):
         if g_s1 is None and g_s2 is None:
             return (None,) * 5
         depth, gt = ctx.saved_tensors[:2]
-        alpha = ctx.saved_tensors[2] if ctx.has_alpha else None
+        alpha, cots, g_depth, g_alpha = _args.backward_buffers(ctx, 2, g_s1, g_s2)
         B, H, W = depth.shape
-        g_s1, g_s2 = (torch.zeros(B, device=depth.device) if g is None else g.float().contiguous() for g in (g_s1, g_s2))
-        g_depth = torch.empty(B, H, W, device=depth.device)
-        g_alpha = None if alpha is None else torch.empty(B, H, W, device=depth.device)
+        g_s1, g_s2 = (torch.zeros(B, device=depth.device) if g is None else g for g in cots)
         p = _lib.ptr
         _lib.check(_lib.lib().fs_si_depth_backward(B, H, W, p(depth), p(gt), p(alpha), *ctx.scalars, p(g_s1), p(g_s2), p(g_depth),
                                                    p(g_alpha), _lib.current_stream()), "fs_si_depth_backward")
@@ -267,7 +231,7 @@ def mv_depth_terms(depth: Tensor, gt: Tensor, src_depth: Tensor, pairs: Tensor, 
     scalars = _scalars(min_depth, max_depth, alpha_floor, occlusion)
     d, g, a = _maps(depth, gt, alpha)
     s, q, idx, K, S_pool = _sources(d, src_depth, pairs, src_index)
-    return _MVDepth.apply(d, g, a, s, idx, q, K, S_pool, scalars, _pending(d, a))
+    return _MVDepth.apply(d, g, a, s, idx, q, K, S_pool, scalars, _args.pending(d, a))
 
 
 def combine(total: Tensor, cnt: Tensor) -> Tensor:
@@ -303,7 +267,7 @@ def si_depth_terms(depth: Tensor, gt: Tensor, alpha: Tensor | None = None, *, mi
     """(s1 [B], s2 [B], n [B]) float64 from one library call; s1 and s2 are differentiable with respect to `depth` and `alpha`."""
     scalars = _scalars(min_depth, max_depth, alpha_floor)
     d, g, a = _maps(depth, gt, alpha)
-    return _SIDepth.apply(d, g, a, scalars, _pending(d, a))
+    return _SIDepth.apply(d, g, a, scalars, _args.pending(d, a))
 
 
 def combine_si(s1: Tensor, s2: Tensor, n: Tensor, si_lambda: float = 0.85) -> Tensor:

@@ -30,22 +30,16 @@ import math
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _args, _lib
 
 TILE_W, TILE_H = 32, 16   # pixels one workgroup owns (csrc/normals_loss.hip kTileW, kTileH); tests place shapes by it
 HALO = 6                  # the backward's reach around a tile with smoothing (2 without)
+_NAME = "freesplat_amd.normals_loss"
 
 
 def intrinsics_from_fov(tanfovx: float, tanfovy: float, H: int, W: int):
     """(fx, fy, cx, cy) of the rasterizer's convention: pixel p is the ray through NDC (2 p + 1) / W - 1."""
     return W / (2.0 * tanfovx), H / (2.0 * tanfovy), (W - 1) / 2.0, (H - 1) / 2.0
-
-
-def _device_f32(t, what: str) -> Tensor:
-    if not isinstance(t, Tensor) or t.device.type != "cuda":
-        raise ValueError(f"freesplat_amd.normals_loss: {what} must be a tensor on a HIP device (got "
-                         f"{getattr(t, 'device', type(t))}); there is no CPU path")
-    return t.float().contiguous()
 
 
 def _intrinsics(intr, B: int, device) -> Tensor:
@@ -74,29 +68,12 @@ def _scalars(smoothing, min_depth, max_depth, alpha_floor):
         sigma = float(smoothing)
         if isinstance(smoothing, bool) or not (sigma > 0.0 and math.isfinite(sigma)):
             raise ValueError(f"freesplat_amd.normals_loss: smoothing must be None or a positive finite sigma, got {smoothing!r}")
-    min_depth, max_depth, alpha_floor = float(min_depth), float(max_depth), float(alpha_floor)
-    if math.isnan(min_depth) or math.isnan(max_depth):
-        raise ValueError("freesplat_amd.normals_loss: min_depth / max_depth must not be NaN")
-    if not (alpha_floor > 0.0 and math.isfinite(alpha_floor)):
-        raise ValueError(f"freesplat_amd.normals_loss: alpha_floor must be a positive finite number, got {alpha_floor!r}")
-    return sigma, min_depth, max_depth, alpha_floor
+    return (sigma, *_args.depth_scalars(min_depth, max_depth, alpha_floor, _NAME))
 
 
 def _maps(depth, alpha, intrinsics):
-    d = _device_f32(depth, "depth")
-    a = None if alpha is None else _device_f32(alpha, "alpha")
-    if d.dim() != 3 or (a is not None and a.shape != d.shape):
-        raise ValueError(f"freesplat_amd.normals_loss: expected [B, H, W] tensors of one shape, got {tuple(d.shape)}"
-                         + ("" if a is None else f" and {tuple(a.shape)}"))
-    if a is not None and a.device != d.device:
-        raise ValueError("freesplat_amd.normals_loss: tensors on different devices")
-    if d.numel() == 0:
-        raise ValueError("freesplat_amd.normals_loss: empty batch")
+    d, a = _args.depth_maps(_NAME, depth, alpha)
     return d, a, _intrinsics(intrinsics, d.shape[0], d.device)
-
-
-def _pending(d: Tensor, a) -> bool:
-    return torch.is_grad_enabled() and (d.requires_grad or (a is not None and a.requires_grad))
 
 
 class _DepthNormals(torch.autograd.Function):
@@ -123,11 +100,8 @@ class _DepthNormals(torch.autograd.Function):
         if g is None:
             return (None,) * 5
         depth, intr = ctx.saved_tensors[:2]
-        alpha = ctx.saved_tensors[2] if ctx.has_alpha else None
+        alpha, (g,), g_depth, g_alpha = _args.backward_buffers(ctx, 2, g)
         B, H, W = depth.shape
-        g = g.float().contiguous()
-        g_depth = torch.empty(B, H, W, device=depth.device)
-        g_alpha = None if alpha is None else torch.empty(B, H, W, device=depth.device)
         p = _lib.ptr
         _lib.check(_lib.lib().fs_depth_normals_backward(B, H, W, p(depth), p(alpha), p(intr), *ctx.scalars, p(g), p(g_depth),
                                                         p(g_alpha), _lib.current_stream()), "fs_depth_normals_backward")
@@ -163,12 +137,9 @@ class _NormalsLoss(torch.autograd.Function):
         if g_sum is None:
             return (None,) * 7
         depth, intr, gt = ctx.saved_tensors[:3]
-        alpha = ctx.saved_tensors[3] if ctx.has_alpha else None
+        alpha, (g_sum,), g_depth, g_alpha = _args.backward_buffers(ctx, 3, g_sum)
         gt_depth, gt_normals = (gt, None) if ctx.from_depth else (None, gt)
         B, H, W = depth.shape
-        g_sum = g_sum.float().contiguous()
-        g_depth = torch.empty(B, H, W, device=depth.device)
-        g_alpha = None if alpha is None else torch.empty(B, H, W, device=depth.device)
         p = _lib.ptr
         _lib.check(_lib.lib().fs_normals_loss_backward(B, H, W, p(depth), p(alpha), p(intr), p(gt_depth), p(gt_normals), *ctx.scalars,
                                                        p(g_sum), p(g_depth), p(g_alpha), _lib.current_stream()),
@@ -183,7 +154,7 @@ def depth_normals(depth: Tensor, intrinsics, alpha: Tensor | None = None, *, smo
     ignored.  Use it under no_grad to precompute a sensor's normals once per view, or to look at a reconstruction."""
     scalars = _scalars(smoothing, min_depth, max_depth, alpha_floor)
     d, a, k = _maps(depth, alpha, intrinsics)
-    return _DepthNormals.apply(d, a, k, scalars, _pending(d, a))
+    return _DepthNormals.apply(d, a, k, scalars, _args.pending(d, a))
 
 
 def normals_loss_terms(depth: Tensor, intrinsics, *, gt_depth: Tensor | None = None, gt_normals: Tensor | None = None,
@@ -196,18 +167,16 @@ def normals_loss_terms(depth: Tensor, intrinsics, *, gt_depth: Tensor | None = N
     if (gt_depth is None) == (gt_normals is None):
         raise ValueError("freesplat_amd.normals_loss: exactly one of gt_depth and gt_normals must be given")
     gt = gt_depth if gt_depth is not None else gt_normals
-    if isinstance(gt, Tensor) and gt.requires_grad and torch.is_grad_enabled():
-        raise RuntimeError("freesplat_amd.normals_loss: the target gets no gradient from the fused loss; detach it (only `depth` "
-                           "and `alpha` are differentiated)")
+    _args.no_grad_to(gt, "the target", _NAME)
     d, a, k = _maps(depth, alpha, intrinsics)
-    g = _device_f32(gt, "gt_depth" if gt_depth is not None else "gt_normals").detach()
+    g = _args.device_f32(gt, "gt_depth" if gt_depth is not None else "gt_normals", _NAME).detach()
     B, H, W = d.shape
     want = (B, H, W) if gt_depth is not None else (B, 3, H, W)
     if tuple(g.shape) != want:
         raise ValueError(f"freesplat_amd.normals_loss: the target must be {want} for a depth of {tuple(d.shape)}, got {tuple(g.shape)}")
     if g.device != d.device:
         raise ValueError("freesplat_amd.normals_loss: tensors on different devices")
-    return _NormalsLoss.apply(d, a, k, g if gt_depth is not None else None, g if gt_depth is None else None, scalars, _pending(d, a))
+    return _NormalsLoss.apply(d, a, k, g if gt_depth is not None else None, g if gt_depth is None else None, scalars, _args.pending(d, a))
 
 
 def combine(total: Tensor, cnt: Tensor) -> Tensor:

@@ -24,7 +24,7 @@ import ctypes as C
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _args, _lib
 
 ARRAYS = ("means", "scales", "rotations", "opacities", "shs")                       # FS_OPTIM_MEANS ... FS_OPTIM_SHS
 GROUPS = ("means", "scales", "rotations", "opacity", "sh_dc", "sh_rest")            # FS_OPTIM_LR_*: the order of `lr`
@@ -34,9 +34,7 @@ _STATS = ("grad_accum", "denom", "max_radii")                                   
 
 
 def _device_f32(t, what: str) -> Tensor:
-    if not isinstance(t, Tensor) or t.device.type != "cuda":
-        raise ValueError(f"freesplat_amd.refine: {what} must be a tensor on a HIP device (got "
-                         f"{getattr(t, 'device', type(t))}); there is no CPU path")
+    _args.device_tensor(t, what, "freesplat_amd.refine")
     if t.dtype != torch.float32:
         raise ValueError(f"freesplat_amd.refine: {what} must be float32, got {t.dtype}")
     return t.detach()

@@ -18,7 +18,7 @@ from __future__ import annotations
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _args, _lib
 
 WIN = 11                 # window of both conventions; the smallest image "skimage" accepts
 TILE_W, TILE_H = 246, 64  # pixels of a plane one workgroup owns (csrc/ssim_loss.hip kTileW, kTileH); tests place shapes by it
@@ -31,20 +31,13 @@ def _flags(convention: str) -> int:
     return CONVENTIONS[convention]
 
 
-def _device_f32(t: Tensor, what: str) -> Tensor:
-    if not isinstance(t, Tensor) or t.device.type != "cuda":
-        raise ValueError(f"freesplat_amd.ssim_loss: {what} must be a tensor on a HIP device (got "
-                         f"{getattr(t, 'device', type(t))}); there is no CPU path")
-    return t.float().contiguous()
-
-
 def _images(predicted: Tensor, ground_truth: Tensor, convention: str):
     flags = _flags(convention)
     if isinstance(ground_truth, Tensor) and ground_truth.requires_grad and torch.is_grad_enabled():
         raise RuntimeError("freesplat_amd.ssim_loss: ground_truth gets no gradient from the fused loss; detach it (only "
                            "`predicted` is differentiated)")
-    pred = _device_f32(predicted, "predicted")
-    gt = _device_f32(ground_truth, "ground_truth").detach()
+    pred = _args.device_f32(predicted, "predicted", "freesplat_amd.ssim_loss")
+    gt = _args.device_f32(ground_truth, "ground_truth", "freesplat_amd.ssim_loss").detach()
     if pred.dim() != 4 or pred.shape != gt.shape:
         raise ValueError(f"freesplat_amd.ssim_loss: expected two [B, C, H, W] tensors of one shape, got "
                          f"{tuple(pred.shape)} and {tuple(gt.shape)}")
