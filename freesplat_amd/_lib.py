@@ -1,7 +1,7 @@
 """ctypes binding of libfreesplat_hip.so (C ABI: include/freesplat_amd.h, include/freesplat_amd_loss.h,
 include/freesplat_amd_optim.h, include/freesplat_amd_density.h, include/freesplat_amd_depthloss.h,
 include/freesplat_amd_normals.h, include/freesplat_amd_exposure.h, include/freesplat_amd_mvdepth.h,
-include/freesplat_amd_transform.h, include/freesplat_amd_pose.h).
+include/freesplat_amd_transform.h, include/freesplat_amd_pose.h, include/freesplat_amd_tsdf.h).
 
 The product path has NO fallback: if the HIP library is missing or a call fails this module
 raises.  `build()` compiles the library in-tree with hipcc for gfx950.
@@ -38,6 +38,7 @@ EXPOSURE_API_VERSION = 1  # include/freesplat_amd_exposure.h FS_EXPOSURE_API_VER
 MVDEPTH_API_VERSION = 1  # include/freesplat_amd_mvdepth.h FS_MVDEPTH_API_VERSION
 TRANSFORM_API_VERSION = 1  # include/freesplat_amd_transform.h FS_TRANSFORM_API_VERSION
 POSE_API_VERSION = 1     # include/freesplat_amd_pose.h FS_POSE_API_VERSION
+TSDF_API_VERSION = 1     # include/freesplat_amd_tsdf.h FS_TSDF_API_VERSION
 
 RASTER_TILE_CULL = 1
 RASTER_SH_FP16 = 2
@@ -67,6 +68,11 @@ TRANSFORM_COV_FULL = 8
 SIM3_MAX_ROWS = 64
 SIM3_TANGENT_DIM = 7
 SIM3_SH_GENERATOR_DOUBLES = 83
+
+TSDF_MAX_VIEWS = 64
+TSDF_BRICK = (32, 8, 4)      # grid points (x, y, z) one workgroup of fs_tsdf_integrate owns
+TSDF_MESH_RUN = 256          # consecutive cubes one workgroup of the extraction owns
+TSDF_NO_BRICK_SKIP = 1
 
 
 def build(force: bool = False) -> str:
@@ -272,6 +278,17 @@ POSE_SIGNATURES = {
     "fs_sim3_tangent": (C.c_int, [C.c_int32] * 4 + [_VP] * 13 + [C.c_size_t, _VP]),
 }
 
+# name -> (restype, argtypes); must list every symbol include/freesplat_amd_tsdf.h declares (an eleventh header, an eleventh table)
+TSDF_SIGNATURES = {
+    "fs_tsdf_api_version": (C.c_int, []),
+    "fs_tsdf_integrate": (C.c_int, [C.c_int32] * 3 + [C.c_float] * 6 + [_VP] * 3 + [C.c_int32] * 3 + [_VP] * 5 + [C.c_float] * 5
+                          + [C.c_int32, _VP]),
+    "fs_tsdf_mt_table": (C.c_int, [C.POINTER(C.c_uint8)]),
+    "fs_tsdf_mesh_scratch_bytes": (C.c_size_t, [C.c_int32] * 3),
+    "fs_tsdf_mesh_plan": (C.c_int, [C.c_int32] * 3 + [_VP] * 2 + [C.c_float] + [_VP] * 3),
+    "fs_tsdf_mesh_emit": (C.c_int, [C.c_int32] * 3 + [C.c_float] * 4 + [_VP] * 3 + [C.c_float, _VP, C.c_int64] + [_VP] * 3),
+}
+
 
 def lib():
     global _lib
@@ -287,7 +304,7 @@ def lib():
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
         for table in (SIGNATURES, LOSS_SIGNATURES, OPTIM_SIGNATURES, DENSITY_SIGNATURES, DEPTHLOSS_SIGNATURES,
-                      NORMALS_SIGNATURES, EXPOSURE_SIGNATURES, MVDEPTH_SIGNATURES, TRANSFORM_SIGNATURES, POSE_SIGNATURES):
+                      NORMALS_SIGNATURES, EXPOSURE_SIGNATURES, MVDEPTH_SIGNATURES, TRANSFORM_SIGNATURES, POSE_SIGNATURES, TSDF_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)  # AttributeError if the library lacks a declared symbol
                 fn.restype = res
@@ -322,6 +339,9 @@ def lib():
         if L.fs_pose_api_version() != POSE_API_VERSION:
             raise FreeSplatHipError(f"{LIB_PATH} has pose API revision {L.fs_pose_api_version()}, this binding expects "
                                     f"{POSE_API_VERSION} (include/freesplat_amd_pose.h FS_POSE_API_VERSION): rebuild the library")
+        if L.fs_tsdf_api_version() != TSDF_API_VERSION:
+            raise FreeSplatHipError(f"{LIB_PATH} has TSDF API revision {L.fs_tsdf_api_version()}, this binding expects "
+                                    f"{TSDF_API_VERSION} (include/freesplat_amd_tsdf.h FS_TSDF_API_VERSION): rebuild the library")
         _lib = L
     return _lib
 
