@@ -1,7 +1,4 @@
-"""ctypes binding of libfreesplat_hip.so (C ABI: include/freesplat_amd.h, include/freesplat_amd_loss.h,
-include/freesplat_amd_optim.h, include/freesplat_amd_density.h, include/freesplat_amd_depthloss.h,
-include/freesplat_amd_normals.h, include/freesplat_amd_exposure.h, include/freesplat_amd_mvdepth.h,
-include/freesplat_amd_transform.h, include/freesplat_amd_pose.h, include/freesplat_amd_tsdf.h).
+"""ctypes binding of libfreesplat_hip.so (C ABI: the headers under include/, one record each in HEADERS below).
 
 The product path has NO fallback: if the HIP library is missing or a call fails this module
 raises.  `build()` compiles the library in-tree with hipcc for gfx950.
@@ -11,6 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import subprocess
+from typing import NamedTuple
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 # FREESPLAT_LIB: an alternative build of the same library (A/B measurements of kernel variants inside one GPU session)
@@ -28,17 +26,17 @@ class RasterDims(C.Structure):
                 ("flags", C.c_int32)]
 
 
-ABI_VERSION = 9          # include/freesplat_amd.h FS_ABI_VERSION
-LOSS_API_VERSION = 1     # include/freesplat_amd_loss.h FS_LOSS_API_VERSION
-OPTIM_API_VERSION = 1    # include/freesplat_amd_optim.h FS_OPTIM_API_VERSION
-DENSITY_API_VERSION = 1  # include/freesplat_amd_density.h FS_DENSITY_API_VERSION
-DEPTHLOSS_API_VERSION = 1  # include/freesplat_amd_depthloss.h FS_DEPTHLOSS_API_VERSION
-NORMALS_API_VERSION = 1  # include/freesplat_amd_normals.h FS_NORMALS_API_VERSION
-EXPOSURE_API_VERSION = 1  # include/freesplat_amd_exposure.h FS_EXPOSURE_API_VERSION
-MVDEPTH_API_VERSION = 1  # include/freesplat_amd_mvdepth.h FS_MVDEPTH_API_VERSION
-TRANSFORM_API_VERSION = 1  # include/freesplat_amd_transform.h FS_TRANSFORM_API_VERSION
-POSE_API_VERSION = 1     # include/freesplat_amd_pose.h FS_POSE_API_VERSION
-TSDF_API_VERSION = 1     # include/freesplat_amd_tsdf.h FS_TSDF_API_VERSION
+ABI_VERSION = 9
+LOSS_API_VERSION = 1
+OPTIM_API_VERSION = 1
+DENSITY_API_VERSION = 1
+DEPTHLOSS_API_VERSION = 1
+NORMALS_API_VERSION = 1
+EXPOSURE_API_VERSION = 1
+MVDEPTH_API_VERSION = 1
+TRANSFORM_API_VERSION = 1
+POSE_API_VERSION = 1
+TSDF_API_VERSION = 1
 
 RASTER_TILE_CULL = 1
 RASTER_SH_FP16 = 2
@@ -87,7 +85,7 @@ def build(force: bool = False) -> str:
 
 _VP = C.c_void_p
 
-# name -> (restype, argtypes); must list every symbol include/freesplat_amd.h declares
+# the tables: name -> (restype, argtypes)
 SIGNATURES = {
     "fs_version": (C.c_char_p, []),
     "fs_abi_version": (C.c_int, []),
@@ -193,8 +191,6 @@ SIGNATURES = {
     "fs_raster_n_contrib": (_VP, [_VP, C.c_int32, C.c_int32]),
 }
 
-# name -> (restype, argtypes); must list every symbol include/freesplat_amd_loss.h declares (a header and a table of its
-# own: the main header's symbol set and FS_ABI_VERSION stay as they are)
 LOSS_SIGNATURES = {
     "fs_loss_api_version": (C.c_int, []),
     "fs_ssim_loss_saved_bytes": (C.c_size_t, [C.c_int32] * 5),
@@ -204,8 +200,6 @@ LOSS_SIGNATURES = {
 }
 
 
-# name -> (restype, argtypes); must list every symbol include/freesplat_amd_optim.h declares (again a header and a table of
-# its own)
 _PP = C.POINTER(C.c_void_p)
 OPTIM_SIGNATURES = {
     "fs_optim_api_version": (C.c_int, []),
@@ -213,7 +207,6 @@ OPTIM_SIGNATURES = {
     "fs_gaussian_adam_step": (C.c_int, [C.c_int32, C.c_int32] + [_PP] * 4 + [_VP] * 3 + [C.c_double] * 3 + [_VP] * 3),
 }
 
-# name -> (restype, argtypes); must list every symbol include/freesplat_amd_density.h declares (a fourth header, a fourth table)
 DENSITY_SIGNATURES = {
     "fs_density_api_version": (C.c_int, []),
     "fs_density_accumulate": (C.c_int, [C.c_int32] + [_VP] * 6),
@@ -223,7 +216,6 @@ DENSITY_SIGNATURES = {
     "fs_density_reset_opacity": (C.c_int, [C.c_int32, C.c_double] + [_VP] * 5),
 }
 
-# name -> (restype, argtypes); must list every symbol include/freesplat_amd_depthloss.h declares (a fifth header, a fifth table)
 DEPTHLOSS_SIGNATURES = {
     "fs_depthloss_api_version": (C.c_int, []),
     "fs_depth_loss_saved_bytes": (C.c_size_t, [C.c_int32] * 4),
@@ -232,7 +224,6 @@ DEPTHLOSS_SIGNATURES = {
     "fs_depth_loss_backward": (C.c_int, [C.c_int32] * 5 + [_VP] * 3 + [C.c_float] * 3 + [_VP] * 7),
 }
 
-# name -> (restype, argtypes); must list every symbol include/freesplat_amd_normals.h declares (a sixth header, a sixth table)
 NORMALS_SIGNATURES = {
     "fs_normals_api_version": (C.c_int, []),
     "fs_normals_scratch_bytes": (C.c_size_t, [C.c_int32] * 3),
@@ -242,7 +233,6 @@ NORMALS_SIGNATURES = {
     "fs_normals_loss_backward": (C.c_int, [C.c_int32] * 3 + [_VP] * 5 + [C.c_float] * 4 + [_VP] * 4),
 }
 
-# name -> (restype, argtypes); must list every symbol include/freesplat_amd_exposure.h declares (a seventh header, a seventh table)
 EXPOSURE_SIGNATURES = {
     "fs_exposure_api_version": (C.c_int, []),
     "fs_exposure_scratch_bytes": (C.c_size_t, [C.c_int32] * 3),
@@ -251,7 +241,6 @@ EXPOSURE_SIGNATURES = {
     "fs_exposure_fit": (C.c_int, [C.c_int32] * 4 + [_VP] * 4 + [C.c_double] + [_VP] * 5),
 }
 
-# name -> (restype, argtypes); must list every symbol include/freesplat_amd_mvdepth.h declares (an eighth header, an eighth table)
 MVDEPTH_SIGNATURES = {
     "fs_mvdepth_api_version": (C.c_int, []),
     "fs_mvdepth_scratch_bytes": (C.c_size_t, [C.c_int32] * 4),
@@ -261,7 +250,6 @@ MVDEPTH_SIGNATURES = {
     "fs_si_depth_backward": (C.c_int, [C.c_int32] * 3 + [_VP] * 3 + [C.c_float] * 3 + [_VP] * 5),
 }
 
-# name -> (restype, argtypes); must list every symbol include/freesplat_amd_transform.h declares (a ninth header, a ninth table)
 TRANSFORM_SIGNATURES = {
     "fs_transform_api_version": (C.c_int, []),
     "fs_transform_prepare": (C.c_int, [C.c_int32] + [_VP] * 3),
@@ -270,7 +258,6 @@ TRANSFORM_SIGNATURES = {
     "fs_gaussians_transform_backward": (C.c_int, [C.c_int32] * 4 + [_VP] * 13),
 }
 
-# name -> (restype, argtypes); must list every symbol include/freesplat_amd_pose.h declares (a tenth header, a tenth table)
 POSE_SIGNATURES = {
     "fs_pose_api_version": (C.c_int, []),
     "fs_sim3_tangent_scratch_bytes": (C.c_size_t, [C.c_int32] * 2),
@@ -278,7 +265,6 @@ POSE_SIGNATURES = {
     "fs_sim3_tangent": (C.c_int, [C.c_int32] * 4 + [_VP] * 13 + [C.c_size_t, _VP]),
 }
 
-# name -> (restype, argtypes); must list every symbol include/freesplat_amd_tsdf.h declares (an eleventh header, an eleventh table)
 TSDF_SIGNATURES = {
     "fs_tsdf_api_version": (C.c_int, []),
     "fs_tsdf_integrate": (C.c_int, [C.c_int32] * 3 + [C.c_float] * 6 + [_VP] * 3 + [C.c_int32] * 3 + [_VP] * 5 + [C.c_float] * 5
@@ -288,6 +274,40 @@ TSDF_SIGNATURES = {
     "fs_tsdf_mesh_plan": (C.c_int, [C.c_int32] * 3 + [_VP] * 2 + [C.c_float] + [_VP] * 3),
     "fs_tsdf_mesh_emit": (C.c_int, [C.c_int32] * 3 + [C.c_float] * 4 + [_VP] * 3 + [C.c_float, _VP, C.c_int64] + [_VP] * 3),
 }
+
+
+class Header(NamedTuple):
+    file: str          # under include/
+    macro: str         # the header's revision macro
+    version_fn: str    # the entry point that returns the library's value of it
+    revision: int      # what this binding expects
+    label: str         # how lib()'s mismatch message names it
+    signatures: dict
+
+
+# One record per header under include/ and nothing else to keep in step: a table lists every symbol its header declares and
+# no other table's, and lib() binds and checks whatever is listed here (tests/test_abi.py holds every record to its header
+# and to the built library).
+HEADERS = (
+    Header("freesplat_amd.h", "FS_ABI_VERSION", "fs_abi_version", ABI_VERSION, "ABI", SIGNATURES),
+    Header("freesplat_amd_loss.h", "FS_LOSS_API_VERSION", "fs_loss_api_version", LOSS_API_VERSION, "loss API", LOSS_SIGNATURES),
+    Header("freesplat_amd_optim.h", "FS_OPTIM_API_VERSION", "fs_optim_api_version", OPTIM_API_VERSION, "optimizer API",
+           OPTIM_SIGNATURES),
+    Header("freesplat_amd_density.h", "FS_DENSITY_API_VERSION", "fs_density_api_version", DENSITY_API_VERSION, "density API",
+           DENSITY_SIGNATURES),
+    Header("freesplat_amd_depthloss.h", "FS_DEPTHLOSS_API_VERSION", "fs_depthloss_api_version", DEPTHLOSS_API_VERSION,
+           "depth-loss API", DEPTHLOSS_SIGNATURES),
+    Header("freesplat_amd_normals.h", "FS_NORMALS_API_VERSION", "fs_normals_api_version", NORMALS_API_VERSION, "normals API",
+           NORMALS_SIGNATURES),
+    Header("freesplat_amd_exposure.h", "FS_EXPOSURE_API_VERSION", "fs_exposure_api_version", EXPOSURE_API_VERSION, "exposure API",
+           EXPOSURE_SIGNATURES),
+    Header("freesplat_amd_mvdepth.h", "FS_MVDEPTH_API_VERSION", "fs_mvdepth_api_version", MVDEPTH_API_VERSION,
+           "multi-view depth API", MVDEPTH_SIGNATURES),
+    Header("freesplat_amd_transform.h", "FS_TRANSFORM_API_VERSION", "fs_transform_api_version", TRANSFORM_API_VERSION,
+           "transform API", TRANSFORM_SIGNATURES),
+    Header("freesplat_amd_pose.h", "FS_POSE_API_VERSION", "fs_pose_api_version", POSE_API_VERSION, "pose API", POSE_SIGNATURES),
+    Header("freesplat_amd_tsdf.h", "FS_TSDF_API_VERSION", "fs_tsdf_api_version", TSDF_API_VERSION, "TSDF API", TSDF_SIGNATURES),
+)
 
 
 def lib():
@@ -303,45 +323,15 @@ def lib():
         # device is detected"
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
-        for table in (SIGNATURES, LOSS_SIGNATURES, OPTIM_SIGNATURES, DENSITY_SIGNATURES, DEPTHLOSS_SIGNATURES,
-                      NORMALS_SIGNATURES, EXPOSURE_SIGNATURES, MVDEPTH_SIGNATURES, TRANSFORM_SIGNATURES, POSE_SIGNATURES, TSDF_SIGNATURES):
-            for name, (res, args) in table.items():
+        for h in HEADERS:
+            for name, (res, args) in h.signatures.items():
                 fn = getattr(L, name)  # AttributeError if the library lacks a declared symbol
                 fn.restype = res
                 fn.argtypes = args
-        if L.fs_abi_version() != ABI_VERSION:
-            raise FreeSplatHipError(f"{LIB_PATH} has ABI revision {L.fs_abi_version()}, this binding expects {ABI_VERSION} "
-                                    "(include/freesplat_amd.h FS_ABI_VERSION): rebuild the library")
-        if L.fs_loss_api_version() != LOSS_API_VERSION:
-            raise FreeSplatHipError(f"{LIB_PATH} has loss API revision {L.fs_loss_api_version()}, this binding expects "
-                                    f"{LOSS_API_VERSION} (include/freesplat_amd_loss.h FS_LOSS_API_VERSION): rebuild the library")
-        if L.fs_optim_api_version() != OPTIM_API_VERSION:
-            raise FreeSplatHipError(f"{LIB_PATH} has optimizer API revision {L.fs_optim_api_version()}, this binding expects "
-                                    f"{OPTIM_API_VERSION} (include/freesplat_amd_optim.h FS_OPTIM_API_VERSION): rebuild the library")
-        if L.fs_density_api_version() != DENSITY_API_VERSION:
-            raise FreeSplatHipError(f"{LIB_PATH} has density API revision {L.fs_density_api_version()}, this binding expects "
-                                    f"{DENSITY_API_VERSION} (include/freesplat_amd_density.h FS_DENSITY_API_VERSION): rebuild the library")
-        if L.fs_depthloss_api_version() != DEPTHLOSS_API_VERSION:
-            raise FreeSplatHipError(f"{LIB_PATH} has depth-loss API revision {L.fs_depthloss_api_version()}, this binding expects "
-                                    f"{DEPTHLOSS_API_VERSION} (include/freesplat_amd_depthloss.h FS_DEPTHLOSS_API_VERSION): rebuild the library")
-        if L.fs_normals_api_version() != NORMALS_API_VERSION:
-            raise FreeSplatHipError(f"{LIB_PATH} has normals API revision {L.fs_normals_api_version()}, this binding expects "
-                                    f"{NORMALS_API_VERSION} (include/freesplat_amd_normals.h FS_NORMALS_API_VERSION): rebuild the library")
-        if L.fs_exposure_api_version() != EXPOSURE_API_VERSION:
-            raise FreeSplatHipError(f"{LIB_PATH} has exposure API revision {L.fs_exposure_api_version()}, this binding expects "
-                                    f"{EXPOSURE_API_VERSION} (include/freesplat_amd_exposure.h FS_EXPOSURE_API_VERSION): rebuild the library")
-        if L.fs_mvdepth_api_version() != MVDEPTH_API_VERSION:
-            raise FreeSplatHipError(f"{LIB_PATH} has multi-view depth API revision {L.fs_mvdepth_api_version()}, this binding expects "
-                                    f"{MVDEPTH_API_VERSION} (include/freesplat_amd_mvdepth.h FS_MVDEPTH_API_VERSION): rebuild the library")
-        if L.fs_transform_api_version() != TRANSFORM_API_VERSION:
-            raise FreeSplatHipError(f"{LIB_PATH} has transform API revision {L.fs_transform_api_version()}, this binding expects "
-                                    f"{TRANSFORM_API_VERSION} (include/freesplat_amd_transform.h FS_TRANSFORM_API_VERSION): rebuild the library")
-        if L.fs_pose_api_version() != POSE_API_VERSION:
-            raise FreeSplatHipError(f"{LIB_PATH} has pose API revision {L.fs_pose_api_version()}, this binding expects "
-                                    f"{POSE_API_VERSION} (include/freesplat_amd_pose.h FS_POSE_API_VERSION): rebuild the library")
-        if L.fs_tsdf_api_version() != TSDF_API_VERSION:
-            raise FreeSplatHipError(f"{LIB_PATH} has TSDF API revision {L.fs_tsdf_api_version()}, this binding expects "
-                                    f"{TSDF_API_VERSION} (include/freesplat_amd_tsdf.h FS_TSDF_API_VERSION): rebuild the library")
+            got = getattr(L, h.version_fn)()
+            if got != h.revision:
+                raise FreeSplatHipError(f"{LIB_PATH} has {h.label} revision {got}, this binding expects {h.revision} "
+                                        f"(include/{h.file} {h.macro}): rebuild the library")
         _lib = L
     return _lib
 
@@ -350,6 +340,16 @@ def check(status: int, what: str) -> None:
     if status != 0:
         msg = lib().fs_last_error().decode(errors="replace")
         raise FreeSplatHipError(f"{what} failed with status {status} {msg}")
+
+
+def call(name: str, *args) -> None:
+    """One status-returning entry point with exactly `args`; a non-zero status raises with the library's last error."""
+    check(getattr(lib(), name)(*args), name)
+
+
+def launch(name: str, *args) -> None:
+    """call() of an entry point whose last argument is the stream: torch's current one."""
+    check(getattr(lib(), name)(*args, current_stream()), name)
 
 
 def ptr(t):
@@ -381,15 +381,14 @@ def profile_enable(on, stages=None) -> None:
     if on:
         names = profile_stage_names()
         mask = -1 if stages is None else sum(1 << names.index(s) for s in stages)
-    check(lib().fs_profile_enable(mask), "fs_profile_enable")
+    call("fs_profile_enable", mask)
 
 
 def profile_collect() -> dict:
     """{stage name: (total ms, launches)} of the launches recorded since the last collect."""
-    L = lib()
     names = profile_stage_names()
     n = len(names)
     ms = (C.c_float * n)()
     cnt = (C.c_int32 * n)()
-    check(L.fs_profile_collect(n, ms, cnt), "fs_profile_collect")
+    call("fs_profile_collect", n, ms, cnt)
     return {names[i]: (float(ms[i]), int(cnt[i])) for i in range(n)}

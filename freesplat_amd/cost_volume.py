@@ -101,7 +101,7 @@ class _CostVolumeFn(torch.autograd.Function):
             name, own = "fs_cost_volume_forward_layout", (layout,)
         else:
             name, own = "fs_cost_volume_forward", ()
-        _lib.check(getattr(L, name)(*common, *own, _lib.current_stream()), name)
+        _lib.launch(name, *common, *own)
         if name == "fs_cost_volume_forward_layout":
             return out
         ctx.save_for_backward(cur_feats, src_feats, src_extrinsics, src_Ks, cur_invK, planes, w1, b1, w2, b2, w3)
@@ -137,7 +137,7 @@ class _CostVolumeFn(torch.autograd.Function):
             name, args = "fs_cost_volume_backward_train", (*common, p(ctx.saved), *grads)
         else:
             name, args = "fs_cost_volume_backward", (*common, *grads)
-        _lib.check(getattr(L, name)(*args, _lib.current_stream()), name)
+        _lib.launch(name, *args)
         ctx.saved = None
         # (every gradient, the MLP's included, comes out of the one kernel: no per-point workspace, no GEMMs here)
         return d_cur, d_src, None, None, None, None, None, d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, None, None
@@ -214,8 +214,7 @@ class AVGFeatureVolumeManager(nn.Module):
             md, Md = _dev32(min_depth.reshape(1), "min_depth"), _dev32(max_depth.reshape(1), "max_depth")
             ramp = _dev32(self.linear_ramp_1d11.reshape(D), "linear_ramp_1d11")
             p = _lib.ptr
-            _lib.check(_lib.lib().fs_cost_volume_depth_planes(D, p(md), p(Md), p(ramp), p(flat), _lib.current_stream()),
-                       "fs_cost_volume_depth_planes")
+            _lib.launch("fs_cost_volume_depth_planes", D, p(md), p(Md), p(ramp), p(flat))
             self.depth_planes_bdhw = flat.view(1, D, 1, 1).expand(B, D, h, w)     # (the attribute the reference leaves, :133)
             strides = (0, 1, 0)
         elif depth_planes_bdhw is None:

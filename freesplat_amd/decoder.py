@@ -60,8 +60,8 @@ def frame_views(extrinsics, intrinsics, near, far, scale_invariant: bool = True)
     # (converted copies must stay referenced until the launch is queued: a temporary freed between two conversions
     # would hand its block to the next one)
     e_, k_, n_, f_ = f(extrinsics), f(intrinsics), f(near), f(far)
-    R._lib.check(R._lib.lib().fs_frame_views(v, p(e_), p(k_), p(n_), p(f_), 1 if scale_invariant else 0, p(view), p(full),
-                                             p(campos), p(tanfov), p(scale), R._lib.current_stream()), "fs_frame_views")
+    R._lib.launch("fs_frame_views", v, p(e_), p(k_), p(n_), p(f_), 1 if scale_invariant else 0, p(view), p(full), p(campos),
+                  p(tanfov), p(scale))
     return campos, scale, tanfov, view.view(v, 4, 4), full.view(v, 4, 4)
 
 

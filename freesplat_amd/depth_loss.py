@@ -68,9 +68,8 @@ class _DepthLoss(torch.autograd.Function):
         point_sum, point_cnt = (torch.empty(B, dtype=torch.float64, device=dev) for _ in range(2))
         grad_sum, grad_cnt = (torch.empty(B, S, dtype=torch.float64, device=dev) for _ in range(2))
         p = _lib.ptr
-        _lib.check(L.fs_depth_loss_forward(B, H, W, S, flags, p(depth), p(gt), p(alpha), *scalars, p(point_sum), p(point_cnt),
-                                           p(grad_sum), p(grad_cnt), p(saved), p(scratch), _lib.current_stream()),
-                   "fs_depth_loss_forward")
+        _lib.launch("fs_depth_loss_forward", B, H, W, S, flags, p(depth), p(gt), p(alpha), *scalars, p(point_sum), p(point_cnt),
+                    p(grad_sum), p(grad_cnt), p(saved), p(scratch))
         ctx.args = (flags, S, scalars)
         ctx.has_alpha = alpha is not None
         ctx.set_materialize_grads(False)
@@ -91,8 +90,8 @@ class _DepthLoss(torch.autograd.Function):
         L = _lib.lib()
         scratch = torch.empty(L.fs_depth_loss_scratch_bytes(B, H, W, S), dtype=torch.uint8, device=depth.device)
         p = _lib.ptr
-        _lib.check(L.fs_depth_loss_backward(B, H, W, S, flags, p(depth), p(gt), p(alpha), *scalars, p(g_point), p(g_grad), p(saved),
-                                            p(g_depth), p(g_alpha), p(scratch), _lib.current_stream()), "fs_depth_loss_backward")
+        _lib.launch("fs_depth_loss_backward", B, H, W, S, flags, p(depth), p(gt), p(alpha), *scalars, p(g_point), p(g_grad),
+                    p(saved), p(g_depth), p(g_alpha), p(scratch))
         return g_depth, None, g_alpha, None, None, None, None
 
 

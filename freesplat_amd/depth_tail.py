@@ -28,9 +28,8 @@ class _DepthTail(torch.autograd.Function):
         dw = torch.empty(B, 1, 2 * h2, 2 * w2, device=dev) if upsample else None
         am = torch.empty(B, 2 * h2, 2 * w2, dtype=torch.int32, device=dev) if upsample else None
         p = _lib.ptr
-        _lib.check(_lib.lib().fs_depth_tail_forward(B, D, h2, w2, p(logits), p(cand), int(log_planes), p(stats), p(coarse),
-                                                    p(depth), p(dmap), p(dw), p(am), _lib.current_stream()),
-                   "fs_depth_tail_forward")
+        _lib.launch("fs_depth_tail_forward", B, D, h2, w2, p(logits), p(cand), int(log_planes), p(stats), p(coarse), p(depth),
+                    p(dmap), p(dw), p(am))
         ctx.save_for_backward(logits, cand, stats, coarse, depth, dmap, am)
         ctx.cfg = (bool(log_planes), bool(upsample))
         ctx.set_materialize_grads(False)
@@ -53,14 +52,11 @@ class _DepthTail(torch.autograd.Function):
         gc_, gd_, gm_, gw_ = c(g_coarse), c(g_depth), c(g_map), c(g_w)   # (kept alive until the launch is queued)
         if deterministic():
             # (bitwise repeatable: the wavefronts add into the LDS gradient in a fixed order; rasterizer.deterministic())
-            _lib.check(_lib.lib().fs_depth_tail_backward_det(B, D, h2, w2, p(logits), p(cand), int(log_planes), p(stats),
-                                                             p(coarse), p(depth), p(dmap), p(am), p(gc_), p(gd_), p(gm_),
-                                                             p(gw_), p(g_logits), _lib.current_stream()),
-                       "fs_depth_tail_backward_det")
+            _lib.launch("fs_depth_tail_backward_det", B, D, h2, w2, p(logits), p(cand), int(log_planes), p(stats), p(coarse),
+                        p(depth), p(dmap), p(am), p(gc_), p(gd_), p(gm_), p(gw_), p(g_logits))
             return g_logits, None, None, None
-        _lib.check(_lib.lib().fs_depth_tail_backward(B, D, h2, w2, p(logits), p(cand), int(log_planes), p(stats), p(coarse),
-                                                     p(depth), p(dmap), p(am), p(gc_), p(gd_), p(gm_), p(gw_), p(sE), p(sP),
-                                                     p(g_logits), _lib.current_stream()), "fs_depth_tail_backward")
+        _lib.launch("fs_depth_tail_backward", B, D, h2, w2, p(logits), p(cand), int(log_planes), p(stats), p(coarse), p(depth),
+                    p(dmap), p(am), p(gc_), p(gd_), p(gm_), p(gw_), p(sE), p(sP), p(g_logits))
         return g_logits, None, None, None
 
 

@@ -96,8 +96,7 @@ class _Apply(torch.autograd.Function):
         B, _, H, W = image.shape
         out = torch.empty(B, 3, H, W, dtype=torch.float32, device=image.device)
         p = _lib.ptr
-        _lib.check(_lib.lib().fs_exposure_apply_forward(B, params.shape[0], H, W, p(image), p(params), p(ids), p(out),
-                                                        _lib.current_stream()), "fs_exposure_apply_forward")
+        _lib.launch("fs_exposure_apply_forward", B, params.shape[0], H, W, p(image), p(params), p(ids), p(out))
         ctx.set_materialize_grads(False)
         ctx.has_ids = ids is not None
         ctx.dims = (B, params.shape[0], H, W)
@@ -126,8 +125,8 @@ class _Apply(torch.autograd.Function):
         g_params = torch.empty(V, 3, 4, dtype=torch.float32, device=dev) if want_params else None
         scratch = torch.empty(L.fs_exposure_scratch_bytes(B, H, W), dtype=torch.uint8, device=dev) if want_params else None
         p = _lib.ptr
-        _lib.check(L.fs_exposure_apply_backward(B, V, H, W, p(image), p(params), p(ids), p(g), p(g_image), p(g_params), p(scratch),
-                                                _lib.current_stream()), "fs_exposure_apply_backward")
+        _lib.launch("fs_exposure_apply_backward", B, V, H, W, p(image), p(params), p(ids), p(g), p(g_image), p(g_params),
+                    p(scratch))
         return g_image, g_params, None, None
 
 
@@ -191,8 +190,7 @@ def fit_exposure(pred: Tensor, target: Tensor, mask: Tensor | None = None, view_
     solved = torch.empty(V, dtype=torch.uint8, device=dev)
     scratch = torch.empty(L.fs_exposure_scratch_bytes(B, H, W), dtype=torch.uint8, device=dev)
     p = _lib.ptr
-    _lib.check(L.fs_exposure_fit(B, V, H, W, p(x), p(y), p(m), p(ids), r, p(params), p(count), p(solved), p(scratch),
-                                 _lib.current_stream()), "fs_exposure_fit")
+    _lib.launch("fs_exposure_fit", B, V, H, W, p(x), p(y), p(m), p(ids), r, p(params), p(count), p(solved), p(scratch))
     return params, count, solved.view(torch.bool)
 
 

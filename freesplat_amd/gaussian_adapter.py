@@ -53,8 +53,7 @@ class _Unproject(torch.autograd.Function):
         V = depths.shape[0]
         xyz = torch.empty(V, h * w, 3, dtype=torch.float32, device=depths.device)
         p = _lib.ptr
-        _lib.check(_lib.lib().fs_unproject_forward(V, h, w, p(depths), p(extrinsics), p(k0), p(xyz),
-                                                   _lib.current_stream()), "fs_unproject_forward")
+        _lib.launch("fs_unproject_forward", V, h, w, p(depths), p(extrinsics), p(k0), p(xyz))
         ctx.save_for_backward(extrinsics, k0)
         ctx.hw = (V, h, w)
         return xyz
@@ -65,8 +64,7 @@ class _Unproject(torch.autograd.Function):
         V, h, w = ctx.hw
         gd = torch.empty(V, h * w, dtype=torch.float32, device=g.device)
         p = _lib.ptr
-        _lib.check(_lib.lib().fs_unproject_backward(V, h, w, p(extrinsics), p(k0), p(g.contiguous()), p(gd),
-                                                    _lib.current_stream()), "fs_unproject_backward")
+        _lib.launch("fs_unproject_backward", V, h, w, p(extrinsics), p(k0), p(g.contiguous()), p(gd))
         return gd, None, None, None, None
 
 
@@ -84,10 +82,8 @@ class _Head(torch.autograd.Function):
         rot = torch.empty(M, 4, device=dev)
         stride = 0 if mult.numel() == 1 else 1
         p = _lib.ptr
-        _lib.check(_lib.lib().fs_gaussian_head_forward_sh(M, d_sh, p(raw), p(depths), p(extrinsics), p(mult), stride,
-                                                          p(sh_mask), C.c_float(smin), C.c_float(smax), p(cov), p(sh),
-                                                          p(scales), p(rot), _lib.current_stream()),
-                   "fs_gaussian_head_forward_sh")
+        _lib.launch("fs_gaussian_head_forward_sh", M, d_sh, p(raw), p(depths), p(extrinsics), p(mult), stride, p(sh_mask),
+                    C.c_float(smin), C.c_float(smax), p(cov), p(sh), p(scales), p(rot))
         ctx.save_for_backward(raw, depths, extrinsics, mult, sh_mask)
         ctx.cfg = (smin, smax, stride)
         ctx.set_materialize_grads(False)
@@ -102,11 +98,8 @@ class _Head(torch.autograd.Function):
         c = lambda t: None if t is None else t.contiguous()
         p = _lib.ptr
         gc_, gs_, gsc_, gr_ = c(g_cov), c(g_sh), c(g_scales), c(g_rot)   # (kept alive until the launch is queued)
-        _lib.check(_lib.lib().fs_gaussian_head_backward_sh(M, sh_mask.numel(), p(raw), p(depths), p(extrinsics), p(mult),
-                                                           stride, p(sh_mask), C.c_float(smin), C.c_float(smax), p(gc_),
-                                                           p(gs_), p(gsc_), p(gr_), p(g_raw), p(g_dep), p(g_E),
-                                                           _lib.current_stream()),
-                   "fs_gaussian_head_backward_sh")
+        _lib.launch("fs_gaussian_head_backward_sh", M, sh_mask.numel(), p(raw), p(depths), p(extrinsics), p(mult), stride,
+                    p(sh_mask), C.c_float(smin), C.c_float(smax), p(gc_), p(gs_), p(gsc_), p(gr_), p(g_raw), p(g_dep), p(g_E))
         return g_raw, g_dep, g_E, None, None, None, None
 
 
@@ -120,8 +113,7 @@ class _LatentsPack(torch.autograd.Function):
         lat = torch.empty(N, P, 64, dtype=torch.float32, device=head.device)
         dens = torch.empty(N, P, dtype=torch.float32, device=head.device)
         p = _lib.ptr
-        _lib.check(_lib.lib().fs_latents_pack_forward(N, P, 64, p(head), p(skip), p(lat), p(dens), _lib.current_stream()),
-                   "fs_latents_pack_forward")
+        _lib.launch("fs_latents_pack_forward", N, P, 64, p(head), p(skip), p(lat), p(dens))
         ctx.shapes = (head.shape, skip.shape)
         return lat, dens
 
@@ -137,8 +129,7 @@ class _LatentsPack(torch.autograd.Function):
         gl = None if g_lat is None else g_lat.float().contiguous()
         gd = None if g_dens is None else g_dens.float().contiguous()
         p = _lib.ptr
-        _lib.check(_lib.lib().fs_latents_pack_backward(hs[0], hs[2] * hs[3], 64, p(gl), p(gd), p(g_head), p(g_skip),
-                                                       _lib.current_stream()), "fs_latents_pack_backward")
+        _lib.launch("fs_latents_pack_backward", hs[0], hs[2] * hs[3], 64, p(gl), p(gd), p(g_head), p(g_skip))
         return g_head, g_skip
 
 
@@ -170,8 +161,8 @@ class _SkipLatents(torch.autograd.Function):
         need_w = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
         mask = torch.empty(L.fs_skip_latents_saved_bytes(N, h, w), dtype=torch.uint8, device=dev) if need_w else None
         p = _lib.ptr
-        _lib.check(L.fs_skip_latents_forward(N, h, w, 3, 64, 7, p(head), p(images), p(weight), p(bias), p(lat), p(dens), p(mask),
-                                             _lib.current_stream()), "fs_skip_latents_forward")
+        _lib.launch("fs_skip_latents_forward", N, h, w, 3, 64, 7, p(head), p(images), p(weight), p(bias), p(lat), p(dens),
+                    p(mask))
         if need_w:
             ctx.save_for_backward(images, mask)
         ctx.dims = (N, h, w)
@@ -194,8 +185,8 @@ class _SkipLatents(torch.autograd.Function):
         gl = None if g_lat is None else g_lat.float().contiguous()
         gd = None if g_dens is None else g_dens.float().contiguous()
         p = _lib.ptr
-        _lib.check(L.fs_skip_latents_backward(N, h, w, 3, 64, 7, p(images), p(mask), p(gl), p(gd), p(g_head), p(g_weight),
-                                              p(g_bias), p(scratch), _lib.current_stream()), "fs_skip_latents_backward")
+        _lib.launch("fs_skip_latents_backward", N, h, w, 3, 64, 7, p(images), p(mask), p(gl), p(gd), p(g_head), p(g_weight),
+                    p(g_bias), p(scratch))
         return g_head, None, g_weight, g_bias
 
 

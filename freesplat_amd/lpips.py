@@ -67,8 +67,7 @@ class _Prepare(torch.autograd.Function):
         B, C, H, W = in0.shape
         out = torch.empty(2 * B, C, H, W, device=in0.device)
         p = _lib.ptr
-        _lib.check(_lib.lib().fs_lpips_prepare_forward(p(in0), p(in1), p(shift), p(scale), B, C, H, W, int(normalize), p(out),
-                                                       _lib.current_stream()), "fs_lpips_prepare_forward")
+        _lib.launch("fs_lpips_prepare_forward", p(in0), p(in1), p(shift), p(scale), B, C, H, W, int(normalize), p(out))
         ctx.save_for_backward(scale)
         ctx.normalize = int(normalize)
         return out
@@ -83,8 +82,7 @@ class _Prepare(torch.autograd.Function):
         g0 = torch.empty(B, C, H, W, device=g_out.device) if ctx.needs_input_grad[0] else None
         g1 = torch.empty(B, C, H, W, device=g_out.device) if ctx.needs_input_grad[1] else None
         p = _lib.ptr
-        _lib.check(_lib.lib().fs_lpips_prepare_backward(p(g_out), p(scale), B, C, H, W, ctx.normalize, p(g0), p(g1),
-                                                        _lib.current_stream()), "fs_lpips_prepare_backward")
+        _lib.launch("fs_lpips_prepare_backward", p(g_out), p(scale), B, C, H, W, ctx.normalize, p(g0), p(g1))
         return g0, g1, None, None, None
 
 
@@ -95,8 +93,7 @@ def _layer_forward(f0: Tensor, f1: Tensor, w: Tensor, dist: Tensor) -> Tensor:
     saved = torch.empty(L.fs_lpips_saved_bytes(B, C, H, W) // 4, device=f0.device)
     scratch = torch.empty(L.fs_lpips_scratch_bytes(B, C, H, W), dtype=torch.uint8, device=f0.device)
     p = _lib.ptr
-    _lib.check(L.fs_lpips_layer_forward(p(f0), p(f1), p(w), B, C, H, W, p(dist), p(saved), p(scratch), _lib.current_stream()),
-               "fs_lpips_layer_forward")
+    _lib.launch("fs_lpips_layer_forward", p(f0), p(f1), p(w), B, C, H, W, p(dist), p(saved), p(scratch))
     return saved
 
 
@@ -104,8 +101,7 @@ def _layer_backward(g_dist: Tensor, f0: Tensor, f1: Tensor, w: Tensor, saved: Te
                     g_f1: Optional[Tensor]) -> None:
     B, C, H, W = f0.shape
     p = _lib.ptr
-    _lib.check(_lib.lib().fs_lpips_layer_backward(p(g_dist), p(f0), p(f1), p(w), p(saved), B, C, H, W, p(g_f0), p(g_f1),
-                                                  _lib.current_stream()), "fs_lpips_layer_backward")
+    _lib.launch("fs_lpips_layer_backward", p(g_dist), p(f0), p(f1), p(w), p(saved), B, C, H, W, p(g_f0), p(g_f1))
 
 
 class _Head(torch.autograd.Function):

@@ -49,8 +49,7 @@ def _image_metrics(gt: Tensor, pred: Tensor, return_map: bool):
     mse = torch.empty(B, dtype=torch.float64, device=dev)
     smap = torch.empty(B, C, H - WIN + 1, W - WIN + 1, device=dev) if return_map else None
     p = _lib.ptr
-    _lib.check(L.fs_image_metrics(B, C, H, W, p(gt), p(pred), p(ssim), p(mse), p(smap), p(scratch), _lib.current_stream()),
-               "fs_image_metrics")
+    _lib.launch("fs_image_metrics", B, C, H, W, p(gt), p(pred), p(ssim), p(mse), p(smap), p(scratch))
     return ssim, mse, smap
 
 
@@ -97,8 +96,7 @@ def depth_metrics(gt: Tensor, pred: Tensor) -> dict:
     L = _lib.lib()
     scratch = torch.empty(L.fs_depth_metrics_scratch_bytes(n, HW), dtype=torch.uint8, device=g.device)
     out = torch.empty(6, n, dtype=torch.float64, device=g.device)
-    _lib.check(L.fs_depth_metrics(n, HW, _lib.ptr(g), _lib.ptr(p), DEPTH_THRESHOLD, _lib.ptr(out), _lib.ptr(scratch),
-                                  _lib.current_stream()), "fs_depth_metrics")
+    _lib.launch("fs_depth_metrics", n, HW, _lib.ptr(g), _lib.ptr(p), DEPTH_THRESHOLD, _lib.ptr(out), _lib.ptr(scratch))
     n_valid, n_nonnan, s_abs, s_rel, n25, n10 = out
     return {"abs_diff": s_abs / n_nonnan, "abs_rel": s_rel / n_nonnan, "delta_25": n25 / n_valid, "delta_10": n10 / n_valid}
 

@@ -150,8 +150,8 @@ def _launch_forward(depth, gt, alpha, src, idx, pairs, K, S_pool, scalars, resid
     scratch = torch.empty(L.fs_mvdepth_scratch_bytes(B, K, H, W), dtype=torch.uint8, device=dev)
     total, cnt = (torch.empty(B, K, dtype=torch.float64, device=dev) for _ in range(2))
     p = _lib.ptr
-    _lib.check(L.fs_mv_depth_forward(B, K, H, W, Hs, Ws, S_pool, p(depth), p(gt), p(alpha), p(src), p(idx), p(pairs), *scalars,
-                                     p(total), p(cnt), p(residual), p(scratch), _lib.current_stream()), "fs_mv_depth_forward")
+    _lib.launch("fs_mv_depth_forward", B, K, H, W, Hs, Ws, S_pool, p(depth), p(gt), p(alpha), p(src), p(idx), p(pairs), *scalars,
+                p(total), p(cnt), p(residual), p(scratch))
     return total, cnt
 
 
@@ -182,9 +182,8 @@ class _MVDepth(torch.autograd.Function):
         B, H, W = depth.shape
         Hs, Ws = src.shape[-2:]
         p = _lib.ptr
-        _lib.check(_lib.lib().fs_mv_depth_backward(B, K, H, W, Hs, Ws, S_pool, p(depth), p(gt), p(alpha), p(src), p(idx), p(pairs),
-                                                   *scalars, p(g_sum), p(g_depth), p(g_alpha), _lib.current_stream()),
-                   "fs_mv_depth_backward")
+        _lib.launch("fs_mv_depth_backward", B, K, H, W, Hs, Ws, S_pool, p(depth), p(gt), p(alpha), p(src), p(idx), p(pairs),
+                    *scalars, p(g_sum), p(g_depth), p(g_alpha))
         return (g_depth, None, g_alpha) + (None,) * 7
 
 
@@ -199,8 +198,7 @@ class _SIDepth(torch.autograd.Function):
         scratch = torch.empty(L.fs_mvdepth_scratch_bytes(B, 0, H, W), dtype=torch.uint8, device=dev)
         s1, s2, n = (torch.empty(B, dtype=torch.float64, device=dev) for _ in range(3))
         p = _lib.ptr
-        _lib.check(L.fs_si_depth_forward(B, H, W, p(depth), p(gt), p(alpha), *scalars, p(s1), p(s2), p(n), p(scratch),
-                                         _lib.current_stream()), "fs_si_depth_forward")
+        _lib.launch("fs_si_depth_forward", B, H, W, p(depth), p(gt), p(alpha), *scalars, p(s1), p(s2), p(n), p(scratch))
         ctx.scalars = scalars
         ctx.has_alpha = alpha is not None
         ctx.set_materialize_grads(False)
@@ -219,8 +217,8 @@ class _SIDepth(torch.autograd.Function):
         B, H, W = depth.shape
         g_s1, g_s2 = (torch.zeros(B, device=depth.device) if g is None else g for g in cots)
         p = _lib.ptr
-        _lib.check(_lib.lib().fs_si_depth_backward(B, H, W, p(depth), p(gt), p(alpha), *ctx.scalars, p(g_s1), p(g_s2), p(g_depth),
-                                                   p(g_alpha), _lib.current_stream()), "fs_si_depth_backward")
+        _lib.launch("fs_si_depth_backward", B, H, W, p(depth), p(gt), p(alpha), *ctx.scalars, p(g_s1), p(g_s2), p(g_depth),
+                    p(g_alpha))
         return g_depth, None, g_alpha, None, None
 
 

@@ -85,8 +85,7 @@ class _DepthNormals(torch.autograd.Function):
         B, H, W = depth.shape
         out = torch.empty(B, 3, H, W, device=depth.device)
         p = _lib.ptr
-        _lib.check(_lib.lib().fs_depth_normals_forward(B, H, W, p(depth), p(alpha), p(intr), *scalars, p(out), _lib.current_stream()),
-                   "fs_depth_normals_forward")
+        _lib.launch("fs_depth_normals_forward", B, H, W, p(depth), p(alpha), p(intr), *scalars, p(out))
         ctx.scalars = scalars
         ctx.has_alpha = alpha is not None
         ctx.set_materialize_grads(False)
@@ -103,8 +102,7 @@ class _DepthNormals(torch.autograd.Function):
         alpha, (g,), g_depth, g_alpha = _args.backward_buffers(ctx, 2, g)
         B, H, W = depth.shape
         p = _lib.ptr
-        _lib.check(_lib.lib().fs_depth_normals_backward(B, H, W, p(depth), p(alpha), p(intr), *ctx.scalars, p(g), p(g_depth),
-                                                        p(g_alpha), _lib.current_stream()), "fs_depth_normals_backward")
+        _lib.launch("fs_depth_normals_backward", B, H, W, p(depth), p(alpha), p(intr), *ctx.scalars, p(g), p(g_depth), p(g_alpha))
         return g_depth, g_alpha, None, None, None
 
 
@@ -120,8 +118,8 @@ class _NormalsLoss(torch.autograd.Function):
         scratch = torch.empty(L.fs_normals_scratch_bytes(B, H, W), dtype=torch.uint8, device=dev)
         total, cnt = (torch.empty(B, dtype=torch.float64, device=dev) for _ in range(2))
         p = _lib.ptr
-        _lib.check(L.fs_normals_loss_forward(B, H, W, p(depth), p(alpha), p(intr), p(gt_depth), p(gt_normals), *scalars, p(total),
-                                             p(cnt), p(scratch), _lib.current_stream()), "fs_normals_loss_forward")
+        _lib.launch("fs_normals_loss_forward", B, H, W, p(depth), p(alpha), p(intr), p(gt_depth), p(gt_normals), *scalars,
+                    p(total), p(cnt), p(scratch))
         ctx.scalars = scalars
         ctx.has_alpha, ctx.from_depth = alpha is not None, gt_depth is not None
         ctx.set_materialize_grads(False)
@@ -141,9 +139,8 @@ class _NormalsLoss(torch.autograd.Function):
         gt_depth, gt_normals = (gt, None) if ctx.from_depth else (None, gt)
         B, H, W = depth.shape
         p = _lib.ptr
-        _lib.check(_lib.lib().fs_normals_loss_backward(B, H, W, p(depth), p(alpha), p(intr), p(gt_depth), p(gt_normals), *ctx.scalars,
-                                                       p(g_sum), p(g_depth), p(g_alpha), _lib.current_stream()),
-                   "fs_normals_loss_backward")
+        _lib.launch("fs_normals_loss_backward", B, H, W, p(depth), p(alpha), p(intr), p(gt_depth), p(gt_normals), *ctx.scalars,
+                    p(g_sum), p(g_depth), p(g_alpha))
         return g_depth, g_alpha, None, None, None, None, None
 
 

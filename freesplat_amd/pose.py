@@ -61,8 +61,8 @@ def _tangent(N: int, M: int, V: int, flags: int, ids, values, grads) -> Tensor:
         raise ValueError(f"{_P}N = {N} Gaussians and {V} rows: the rows must number 1 - {_lib.SIM3_MAX_ROWS}")
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     p = _lib.ptr
-    _lib.check(L.fs_sim3_tangent(N, M, V, flags, p(ids), *[p(a) for a in values], *[p(g) for g in grads], p(out), p(scratch), nbytes,
-                                 _lib.current_stream()), "fs_sim3_tangent")
+    _lib.launch("fs_sim3_tangent", N, M, V, flags, p(ids), *[p(a) for a in values], *[p(g) for g in grads], p(out), p(scratch),
+                nbytes)
     return out
 
 

@@ -68,18 +68,13 @@ def _gru_params(gru: "GRU") -> list:
     return out
 
 
-def _call(name: str, *args) -> None:
-    """The library's `name` on the current stream (its last argument), checked."""
-    _lib.check(getattr(_lib.lib(), name)(*args, _lib.current_stream()), name)
-
-
 def _call_backward(name: str, args: tuple, P: int, det_scratch) -> None:
     """`name`, or with a scratch (the deterministic mode) `name`_det, which takes the view's pixel count and that scratch too:
     tied fused rows then add into the view's pixels in row order."""
     if det_scratch is None:
-        _call(name, *args)
+        _lib.launch(name, *args)
     else:
-        _call(name + "_det", *args, P, _lib.ptr(det_scratch))
+        _lib.launch(name + "_det", *args, P, _lib.ptr(det_scratch))
 
 
 # ---- the GRU and its operands ------------------------------------------------------------------------------------------
@@ -236,12 +231,12 @@ def gru_backward(params: list, tables: Tensor, operand_stream: Tensor, cat: Tens
     g_fused = g_fused.contiguous()
     if saved is not None:
         side, act, stream_t = saved
-        _call("fs_ptf_gru_backward_saved", n, p(cat), p(stream_t), p(act), p(g_fused), p(dcat), p(side))
+        _lib.launch("fs_ptf_gru_backward_saved", n, p(cat), p(stream_t), p(act), p(g_fused), p(dcat), p(side))
     else:
         side = torch.empty(n, L.fs_ptf_gru_side_cols(), dtype=torch.float32, device=dev)
-        _call("fs_ptf_gru_backward", n, p(cat), p(tables), p(operand_stream), p(g_fused), p(dcat), p(side))
+        _lib.launch("fs_ptf_gru_backward", n, p(cat), p(tables), p(operand_stream), p(g_fused), p(dcat), p(side))
     ws = torch.empty(L.fs_ptf_gru_weight_grads_bytes(n), dtype=torch.uint8, device=dev)
-    _call("fs_ptf_gru_weight_grads", n, p(cat), p(side), p(grads), p(ws))
+    _lib.launch("fs_ptf_gru_weight_grads", n, p(cat), p(side), p(grads), p(ws))
     return dcat, gru_grad_views(grads)
 
 
@@ -256,7 +251,7 @@ class _GruRows(torch.autograd.Function):
         tab = gru_tables(gru)
         out = torch.empty(n, 64, device=cat.device)
         if n:
-            _call("fs_ptf_gru_forward", n, _lib.ptr(cat), _lib.ptr(tab), _lib.ptr(out))
+            _lib.launch("fs_ptf_gru_forward", n, _lib.ptr(cat), _lib.ptr(tab), _lib.ptr(out))
         ctx.gru = gru
         ctx.save_for_backward(cat)
         return out
@@ -358,8 +353,8 @@ def match_view(xyz: Tensor, w2c: Tensor, kpix: Tensor, depth_i: Tensor, h: int, 
     counts = torch.empty(4, dtype=torch.int32, device=dev)
     p = _lib.ptr
     w2c_, kpix_, depth_ = (t.detach().float().contiguous() for t in (w2c, kpix, depth_i))  # alive until the launch is queued
-    _call("fs_ptf_match", M, h, w, p(xyz), p(w2c_), p(kpix_), p(depth_), C.c_float(depth_thres), p(scratch), p(keep), p(fuse),
-          p(fpix), p(app), p(counts))
+    _lib.launch("fs_ptf_match", M, h, w, p(xyz), p(w2c_), p(kpix_), p(depth_), C.c_float(depth_thres), p(scratch), p(keep),
+                p(fuse), p(fpix), p(app), p(counts))
     nk, nf, na, _ = counts.tolist()
     return keep[:nk], fuse[:nf], fpix[:nf], app[:na]
 
@@ -374,7 +369,7 @@ def world_to_camera(Es: Tensor) -> Tensor:
     V = Es.shape[0]
     src = Es.reshape(V, 16).contiguous()
     out = torch.empty_like(src)
-    _call("fs_invert_4x4", V, _lib.ptr(src), _lib.ptr(out))
+    _lib.launch("fs_invert_4x4", V, _lib.ptr(src), _lib.ptr(out))
     return out
 
 
@@ -439,8 +434,8 @@ def _fuse_gaussians_fused(gru, gaussians, coords, densities, weight_emb, depths,
             _fold_scratch.pop(next(iter(_fold_scratch)))
         scratch = _fold_scratch[key] = torch.empty(L.fs_ptf_fold_bytes(V, h, w), dtype=torch.uint8, device=dev)
     # (w2c = NULL: the library inverts the extrinsics itself, with the kernel world_to_camera() uses -- one call less)
-    _lib.check(L.fs_ptf_fold(V, h, w, p(lat), p(xs), p(rho), p(om), p(dep), p(Es), None, p(Kn), C.c_float(depth_thres),
-                             p(tables), p(scratch), ptrs[0], ptrs[-1], p(counts), C.c_void_p(stream)), "fs_ptf_fold")
+    _lib.call("fs_ptf_fold", V, h, w, p(lat), p(xs), p(rho), p(om), p(dep), p(Es), None, p(Kn), C.c_float(depth_thres),
+              p(tables), p(scratch), ptrs[0], ptrs[-1], p(counts), C.c_void_p(stream))
     global LAST_FOLD_COUNTS
     LAST_FOLD_COUNTS = counts
     last = counts[V - 1, 3]
@@ -468,7 +463,7 @@ class _PtfFold(torch.autograd.Function):
         w2c = world_to_camera(Es)
         kpix = torch.empty(V, 4, dtype=torch.float32, device=dev)
         E0 = torch.empty(P, 16, dtype=torch.float32, device=dev)
-        _call("fs_ptf_cameras", V, h, w, p(Es), p(Kn), p(kpix), p(E0))
+        _lib.launch("fs_ptf_cameras", V, h, w, p(Es), p(Kn), p(kpix), p(E0))
         counts = torch.empty(V, 4, dtype=torch.int32, device=dev)
         state = (lat[0], xs[0], rho[0], om[0], E0, dep[0])         # G, X, R, O, E, D of the state after view 0
         states, scratches, saves = [state], [None], [None]
@@ -487,10 +482,10 @@ class _PtfFold(torch.autograd.Function):
                 side = torch.empty(nf_max, L.fs_ptf_gru_side_cols(), dtype=torch.float32, device=dev)
                 act = torch.empty(-(-nf_max // 16) * 16, L.fs_ptf_gru_act_cols(), dtype=torch.float32, device=dev)   # (whole 16-pair groups)
                 cat = torch.empty(nf_max, 176, dtype=torch.float32, device=dev)
-                _call("fs_ptf_fold_step_save", *args, p(side), p(act), p(cat))
+                _lib.launch("fs_ptf_fold_step_save", *args, p(side), p(act), p(cat))
                 saves.append((side, act, cat))
             else:
-                _call("fs_ptf_fold_step", *args)
+                _lib.launch("fs_ptf_fold_step", *args)
                 saves.append(None)
             state = out
             states.append(out)
@@ -552,7 +547,7 @@ class _PtfFold(torch.autograd.Function):
             M_in = cnt[i - 1][3]
             G, X, R, O, E, D = ctx.states[i - 1]
             lists = (C.c_void_p * 4)()
-            _lib.check(L.fs_ptf_fold_step_lists(i * P, h, w, p(ctx.scratches[i]), lists), "fs_ptf_fold_step_lists")
+            _lib.call("fs_ptf_fold_step_lists", i * P, h, w, p(ctx.scratches[i]), lists)
             keep, fuse, fpix, app = (C.c_void_p(v) for v in lists)
             if i == 1:
                 # the state before view 1 IS view 0 (every row of it kept or fused): its gradient is written straight
@@ -571,7 +566,7 @@ class _PtfFold(torch.autograd.Function):
                     cat = sv[2][:nf]                       # (the forward kept the gathered + encoded rows)
                 else:
                     cat = torch.empty(nf, 176, dtype=torch.float32, device=dev)
-                    _call("fs_ptf_gru_inputs", nf, fuse, fpix, p(G), p(R), p(O), p(lat[i]), p(rho[i]), p(om[i]), p(cat))
+                    _lib.launch("fs_ptf_gru_inputs", nf, fuse, fpix, p(G), p(R), p(O), p(lat[i]), p(rho[i]), p(om[i]), p(cat))
                 g_fused = g_out[0][nk: nk + nf] if g_out[0] is not None else z(nf, 64)
                 if g_flat is None:
                     g_flat = z(L.fs_ptf_gru_grad_floats())

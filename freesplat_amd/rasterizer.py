@@ -118,7 +118,7 @@ def _state(device: torch.device) -> _DeviceState:
 
 def _buffer_sizes(N: int, H: int, W: int, cap: int):
     out = (C.c_size_t * 4)()
-    _lib.check(_lib.lib().fs_raster_buffer_sizes(N, H, W, cap, out), "fs_raster_buffer_sizes")
+    _lib.call("fs_raster_buffer_sizes", N, H, W, cap, out)
     return [int(x) for x in out]
 
 
@@ -170,10 +170,9 @@ def _launch_forward(dims: _lib.RasterDims, means3D, cov3D, shs, colors, opacitie
                      torch.empty(2, dtype=torch.int32, device=dev), cap, bg, view, proj, campos, tanfov, scale)
     color, depth, alpha = out if out is not None else _images((), H, W, dev)
     p = _lib.ptr
-    _lib.check(_lib.lib().fs_raster_forward(
-        C.byref(dims), p(means3D), p(cov3D), p(shs), p(colors), p(opacities), p(bg), p(view), p(proj),
-        p(campos), p(tanfov), p(scale), p(rs.geom), p(rs.binning), p(rs.image), p(scratch), cap,
-        p(color), p(depth), p(alpha), p(rs.radii), p(rs.counters), _lib.current_stream()), "fs_raster_forward")
+    _lib.launch("fs_raster_forward", C.byref(dims), p(means3D), p(cov3D), p(shs), p(colors), p(opacities), p(bg), p(view),
+                p(proj), p(campos), p(tanfov), p(scale), p(rs.geom), p(rs.binning), p(rs.image), p(scratch), cap, p(color),
+                p(depth), p(alpha), p(rs.radii), p(rs.counters))
     return rs, color, depth, alpha
 
 
@@ -224,10 +223,9 @@ def rasterize_forward_views(dims: _lib.RasterDims, means3D, cov3D, shs, colors, 
     scratch = _u8(max(_lib.lib().fs_raster_scratch_slots(v, ns), 1) * buf.sz[3], dev)
     p = _lib.ptr
     if v > 0:
-        _lib.check(_lib.lib().fs_raster_forward_views(
-            C.byref(dims), v, p(means3D), p(cov3D), p(shs), p(colors), p(opacities), p(bgs), p(views), p(fulls), p(campos),
-            p(tanfov), p(scale), p(buf.geom), p(buf.binning), p(buf.image), p(scratch), (C.c_size_t * 4)(*buf.sz), cap, p(color),
-            p(depth), p(alpha), p(buf.radii), p(buf.counters), ns, handles, _lib.current_stream()), "fs_raster_forward_views")
+        _lib.launch("fs_raster_forward_views", C.byref(dims), v, p(means3D), p(cov3D), p(shs), p(colors), p(opacities), p(bgs),
+                    p(views), p(fulls), p(campos), p(tanfov), p(scale), p(buf.geom), p(buf.binning), p(buf.image), p(scratch),
+                    (C.c_size_t * 4)(*buf.sz), cap, p(color), p(depth), p(alpha), p(buf.radii), p(buf.counters), ns, handles)
     return buf, color, depth, alpha
 
 
@@ -351,11 +349,10 @@ def rasterize_backward(rs: RasterState, means3D, cov3D, shs, colors, opacities, 
         scratch = torch.empty(max(N, 1) * 12, dtype=torch.float32, device=dev)
     g_color, g_depth, g_alpha = _cotangents(g_color, g_depth, g_alpha, (3, d.H, d.W), dev)
     p = _lib.ptr
-    _lib.check(_lib.lib().fs_raster_backward_alpha(
-        C.byref(d), p(means3D), p(cov3D), p(shs), p(colors), p(opacities), p(rs.bg), p(rs.view), p(rs.proj),
-        p(rs.campos), p(rs.tanfov), p(rs.scale), p(rs.geom), p(rs.binning), p(rs.image), p(rs.counters), p(g_color),
-        p(g_depth), p(g_alpha), p(scratch), p(out["means3D"]), p(out["means2D"]), p(out["cov3D"]), p(out["shs"]), p(out["colors"]),
-        p(out["opacities"]), 1 if accumulate else 0, _lib.current_stream()), "fs_raster_backward_alpha")
+    _lib.launch("fs_raster_backward_alpha", C.byref(d), p(means3D), p(cov3D), p(shs), p(colors), p(opacities), p(rs.bg),
+                p(rs.view), p(rs.proj), p(rs.campos), p(rs.tanfov), p(rs.scale), p(rs.geom), p(rs.binning), p(rs.image),
+                p(rs.counters), p(g_color), p(g_depth), p(g_alpha), p(scratch), p(out["means3D"]), p(out["means2D"]),
+                p(out["cov3D"]), p(out["shs"]), p(out["colors"]), p(out["opacities"]), 1 if accumulate else 0)
     return out
 
 
@@ -381,9 +378,9 @@ def rasterize_backward_views(buf: ViewBuffers, means3D, cov3D, shs, colors, opac
             p(out["opacities"]), 0, ns, handles, _lib.current_stream()]
     name = "fs_raster_backward_views" + ("" if row_chunks is None else "_rows") + ("" if g_alpha is None else "_alpha")
     if row_chunks is None:
-        _lib.check(getattr(_lib.lib(), name)(*args), name)
+        _lib.call(name, *args)
     for ci, (c0, c1) in enumerate(row_chunks or ()):
-        _lib.check(getattr(_lib.lib(), name)(*args, c0, c1 - c0, 1 if ci == 0 else 0), name)
+        _lib.call(name, *args, c0, c1 - c0, 1 if ci == 0 else 0)
         if chunk_ready is not None:
             chunk_ready(c0, c1, out)
     return out

@@ -122,8 +122,7 @@ class GaussianAdam:
 
     def _activate(self) -> None:
         p = _lib.ptr
-        _lib.check(_lib.lib().fs_gaussian_activate(self.N, p(self._raw[1]), p(self._raw[3]), p(self._scales), p(self._opacities),
-                                                   _lib.current_stream()), "fs_gaussian_activate")
+        _lib.launch("fs_gaussian_activate", self.N, p(self._raw[1]), p(self._raw[3]), p(self._scales), p(self._opacities))
 
     def zero_grad(self) -> None:
         for t in self.leaves():
@@ -161,10 +160,9 @@ class GaussianAdam:
             raise ValueError("freesplat_amd.refine: step() without any gradient (call backward() first)")
         p = _lib.ptr
         with torch.no_grad():
-            _lib.check(_lib.lib().fs_gaussian_adam_step(self.N, self.M, self._tables[0], _table(grads), self._tables[1],
-                                                        self._tables[2], p(visible), p(self.lr), p(self.step_count),
-                                                        self.betas[0], self.betas[1], self.eps, p(self._scales),
-                                                        p(self._opacities), _lib.current_stream()), "fs_gaussian_adam_step")
+            _lib.launch("fs_gaussian_adam_step", self.N, self.M, self._tables[0], _table(grads), self._tables[1], self._tables[2],
+                        p(visible), p(self.lr), p(self.step_count), self.betas[0], self.betas[1], self.eps, p(self._scales),
+                        p(self._opacities))
         self.zero_grad()
 
     # ---- adaptive density control ----------------------------------------------------------------------------------------
@@ -189,8 +187,7 @@ class GaussianAdam:
         if g.dtype != torch.float32 or not g.is_contiguous():
             g = g.float().contiguous()
         p = _lib.ptr
-        _lib.check(_lib.lib().fs_density_accumulate(self.N, p(g), p(radii), p(self.grad_accum), p(self.denom), p(self.max_radii),
-                                                    _lib.current_stream()), "fs_density_accumulate")
+        _lib.launch("fs_density_accumulate", self.N, p(g), p(radii), p(self.grad_accum), p(self.denom), p(self.max_radii))
         self.viewspace.grad = None
 
     def _plan(self, thresholds):
@@ -203,9 +200,8 @@ class GaussianAdam:
         src = torch.empty(2 * N, dtype=torch.int32, device=dev)              # uint32 in the library
         totals = torch.empty(4, dtype=torch.int32, device=dev)
         scratch = torch.empty(int(L.fs_density_plan_scratch_bytes(N)), dtype=torch.uint8, device=dev)
-        _lib.check(L.fs_density_plan(N, p(self.grad_accum), p(self.denom), p(self.max_radii), p(self._scales), p(self._opacities),
-                                     *thresholds, p(kind), p(offset), p(src), p(totals), p(scratch), _lib.current_stream()),
-                   "fs_density_plan")
+        _lib.launch("fs_density_plan", N, p(self.grad_accum), p(self.denom), p(self.max_radii), p(self._scales),
+                    p(self._opacities), *thresholds, p(kind), p(offset), p(src), p(totals), p(scratch))
         return kind, offset, src, [int(x) for x in totals.tolist()]
 
     def densify(self, extent, grad_threshold=2e-4, min_opacity=0.005, percent_dense=0.01, max_screen_size=None, prune_big=False,
@@ -248,9 +244,8 @@ class GaussianAdam:
         scales = torch.empty(n_out, 3, dtype=torch.float32, device=dev)
         opacities = torch.empty(n_out, 1, dtype=torch.float32, device=dev)
         with torch.no_grad():
-            _lib.check(_lib.lib().fs_density_apply(self.N, self.M, n_out, p(src), *self._tables, *[_table(ts) for ts in new],
-                                                   p(scales), p(opacities), seed & 0xFFFFFFFF, _lib.current_stream()),
-                       "fs_density_apply")
+            _lib.launch("fs_density_apply", self.N, self.M, n_out, p(src), *self._tables, *[_table(ts) for ts in new], p(scales),
+                        p(opacities), seed & 0xFFFFFFFF)
         self.N = n_out
         self._raw, self.exp_avg, self.exp_avg_sq = new
         self._scales, self._opacities = scales, opacities
@@ -265,9 +260,8 @@ class GaussianAdam:
             raise ValueError(f"freesplat_amd.refine: max_opacity must lie inside (0, 1), got {max_opacity}")
         p = _lib.ptr
         with torch.no_grad():
-            _lib.check(_lib.lib().fs_density_reset_opacity(self.N, float(max_opacity), p(self._raw[3]), p(self.exp_avg[3]),
-                                                           p(self.exp_avg_sq[3]), p(self._opacities), _lib.current_stream()),
-                       "fs_density_reset_opacity")
+            _lib.launch("fs_density_reset_opacity", self.N, float(max_opacity), p(self._raw[3]), p(self.exp_avg[3]),
+                        p(self.exp_avg_sq[3]), p(self._opacities))
 
     def transform_(self, transform) -> None:
         """Move the scene by the similarity `transform` (a 4 x 4 [s R | t] or a tuple (s, R, t), as
@@ -285,9 +279,8 @@ class GaussianAdam:
         p = _lib.ptr
         means, rot, shs = self._raw[0], self._raw[2], self._raw[4]
         with torch.no_grad():
-            _lib.check(_lib.lib().fs_gaussians_transform_forward(self.N, self.M, 1, 0, p(table), None, p(means), None, p(rot), None,
-                                                                 p(shs), p(means), None, p(rot), None, p(shs),
-                                                                 _lib.current_stream()), "fs_gaussians_transform_forward")
+            _lib.launch("fs_gaussians_transform_forward", self.N, self.M, 1, 0, p(table), None, p(means), None, p(rot), None,
+                        p(shs), p(means), None, p(rot), None, p(shs))
             self._raw[1].add_(torch.log(table[0, _lib.TRANSFORM_S]))
             for t in self.exp_avg + self.exp_avg_sq + [self.step_count, self.grad_accum, self.denom, self.max_radii]:
                 t.zero_()

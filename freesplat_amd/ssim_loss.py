@@ -69,8 +69,7 @@ class _SsimL1(torch.autograd.Function):
         scratch = torch.empty(L.fs_ssim_loss_scratch_bytes(B, C, H, W, flags), dtype=torch.uint8, device=dev)
         out = torch.empty(2, B, dtype=torch.float64, device=dev)
         p = _lib.ptr
-        _lib.check(L.fs_ssim_loss_forward(B, C, H, W, flags, p(pred), p(gt), p(out[0]), p(out[1]), p(saved), p(scratch),
-                                          _lib.current_stream()), "fs_ssim_loss_forward")
+        _lib.launch("fs_ssim_loss_forward", B, C, H, W, flags, p(pred), p(gt), p(out[0]), p(out[1]), p(saved), p(scratch))
         ctx.flags = flags
         ctx.set_materialize_grads(False)
         if saved is not None:
@@ -88,8 +87,7 @@ class _SsimL1(torch.autograd.Function):
         g_l1 = None if g_l1 is None else g_l1.float().contiguous()
         g_pred = torch.empty(B, C, H, W, device=pred.device)
         p = _lib.ptr
-        _lib.check(_lib.lib().fs_ssim_loss_backward(B, C, H, W, ctx.flags, p(pred), p(gt), p(g_ssim), p(g_l1), p(saved),
-                                                    p(g_pred), None, _lib.current_stream()), "fs_ssim_loss_backward")
+        _lib.launch("fs_ssim_loss_backward", B, C, H, W, ctx.flags, p(pred), p(gt), p(g_ssim), p(g_l1), p(saved), p(g_pred), None)
         return g_pred, None, None, None
 
 

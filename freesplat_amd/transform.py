@@ -176,7 +176,7 @@ def prepare_table(xf: Tensor) -> Tensor:
     """xf [V, 3, 4] float32 on the device, rows (s R | t) -> the library's table [V, 100] (fs_transform_prepare)."""
     V = xf.shape[0]
     table = torch.empty(V, _lib.TRANSFORM_TABLE_FLOATS, dtype=torch.float32, device=xf.device)
-    _lib.check(_lib.lib().fs_transform_prepare(V, _lib.ptr(xf), _lib.ptr(table), _lib.current_stream()), "fs_transform_prepare")
+    _lib.launch("fs_transform_prepare", V, _lib.ptr(xf), _lib.ptr(table))
     return table
 
 
@@ -237,9 +237,8 @@ class _Transform(torch.autograd.Function):
         ins = [None if a is None else a.contiguous() for a in arrays]
         outs = [None if a is None else torch.empty_like(a) for a in ins]
         p = _lib.ptr
-        _lib.check(_lib.lib().fs_gaussians_transform_forward(N, M, table.shape[0], flags, p(table), p(ids), *[p(a) for a in ins],
-                                                             *[p(a) for a in outs], _lib.current_stream()),
-                   "fs_gaussians_transform_forward")
+        _lib.launch("fs_gaussians_transform_forward", N, M, table.shape[0], flags, p(table), p(ids), *[p(a) for a in ins],
+                    *[p(a) for a in outs])
         ctx.save_for_backward(table, *([ids] if ids is not None else []), *([a for a in ins if a is not None] if xf is not None else []))
         ctx.cfg = (flags, M, N, ids is not None, [a is not None for a in ins], xf is not None)
         ctx.set_materialize_grads(False)
@@ -258,9 +257,8 @@ class _Transform(torch.autograd.Function):
             return (None,) * 11
         outs = [None if g is None else torch.empty_like(g) for g in gs]
         p = _lib.ptr
-        _lib.check(_lib.lib().fs_gaussians_transform_backward(N, M, table.shape[0], flags, p(table), p(ids), *[p(g) for g in gs],
-                                                              *[p(o) for o in outs], _lib.current_stream()),
-                   "fs_gaussians_transform_backward")
+        _lib.launch("fs_gaussians_transform_backward", N, M, table.shape[0], flags, p(table), p(ids), *[p(g) for g in gs],
+                    *[p(o) for o in outs])
         g_xf = None
         if need_xf:
             from . import pose
@@ -278,8 +276,7 @@ class _RotateSH(torch.autograd.Function):
         sh = sh.contiguous()
         out = torch.empty_like(sh)
         p = _lib.ptr
-        _lib.check(_lib.lib().fs_sh_rotate(N, M, table.shape[0], flags, p(sh), p(table), p(ids), p(out), _lib.current_stream()),
-                   "fs_sh_rotate")
+        _lib.launch("fs_sh_rotate", N, M, table.shape[0], flags, p(sh), p(table), p(ids), p(out))
         ctx.save_for_backward(table, *([ids] if ids is not None else []))
         ctx.cfg = (flags, M, N, ids is not None)
         return out
@@ -293,8 +290,7 @@ class _RotateSH(torch.autograd.Function):
         g = g.float().contiguous()
         out = torch.empty_like(g)
         p = _lib.ptr
-        _lib.check(_lib.lib().fs_sh_rotate(N, M, table.shape[0], flags ^ _lib.TRANSFORM_SH_TRANSPOSE, p(g), p(table), p(ids), p(out),
-                                           _lib.current_stream()), "fs_sh_rotate")
+        _lib.launch("fs_sh_rotate", N, M, table.shape[0], flags ^ _lib.TRANSFORM_SH_TRANSPOSE, p(g), p(table), p(ids), p(out))
         return out, None, None, None, None, None
 
 

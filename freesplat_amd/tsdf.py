@@ -40,7 +40,7 @@ _NAME = "freesplat_amd.tsdf"
 def mt_table() -> np.ndarray:
     """The (tet, case) -> triangles table that ships with the library: uint8 [6, 16, 7] = (count, 6 edge codes)."""
     buf = (C.c_uint8 * (6 * 16 * 7))()
-    _lib.check(_lib.lib().fs_tsdf_mt_table(buf), "fs_tsdf_mt_table")
+    _lib.call("fs_tsdf_mt_table", buf)
     return np.frombuffer(buf, np.uint8).reshape(6, 16, 7).copy()
 
 
@@ -168,17 +168,16 @@ class TSDFVolume:
         w2c = world_to_cam(extrinsics, self.device)
         if w2c.shape[0] != V:
             raise ValueError(f"{_NAME}: extrinsics must be [{V}, 4, 4], got {w2c.shape[0]} matrices")
-        L, p = _lib.lib(), _lib.ptr
+        p = _lib.ptr
         X, Y, Z = self.dims
         for v0 in range(0, V, MAX_VIEWS):
             v1 = min(V, v0 + MAX_VIEWS)
             dv, kv, wv = d[v0:v1], k[v0:v1], w2c[v0:v1]               # (leading slices of contiguous tensors: contiguous)
             iv = None if im is None else im[v0:v1]
             av = None if a is None else a[v0:v1]
-            _lib.check(L.fs_tsdf_integrate(X, Y, Z, *self.origin, self.voxel_size, self.trunc, self.max_weight, p(self.tsdf),
-                                           p(self.weight), p(self.color), v1 - v0, H, W, p(wv), p(kv), p(dv), p(av), p(iv), near,
-                                           min_depth, max_depth, alpha_min, alpha_floor, int(_flags), _lib.current_stream()),
-                       "fs_tsdf_integrate")
+            _lib.launch("fs_tsdf_integrate", X, Y, Z, *self.origin, self.voxel_size, self.trunc, self.max_weight, p(self.tsdf),
+                        p(self.weight), p(self.color), v1 - v0, H, W, p(wv), p(kv), p(dv), p(av), p(iv), near, min_depth,
+                        max_depth, alpha_min, alpha_floor, int(_flags))
 
     # ---- extract --------------------------------------------------------------------------------------------------------------
 
@@ -211,13 +210,13 @@ def extract_mesh(tsdf: Tensor, weight: Tensor, color: Tensor | None, origin, vox
         raise ValueError(f"{_NAME}: a volume of {X} x {Y} x {Z} grid points is beyond 2^31 - 1")
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=f.device)
     total = torch.empty(1, dtype=torch.int64, device=f.device)
-    _lib.check(L.fs_tsdf_mesh_plan(X, Y, Z, p(f), p(w), min_weight, p(total), p(scratch), _lib.current_stream()), "fs_tsdf_mesh_plan")
+    _lib.launch("fs_tsdf_mesh_plan", X, Y, Z, p(f), p(w), min_weight, p(total), p(scratch))
     T = int(total.item())                                           # the extraction's one host synchronisation
     vertices = torch.empty(T, 3, 3, device=f.device)
     colors = None if c is None else torch.empty(T, 3, 3, device=f.device)
     if T:
-        _lib.check(L.fs_tsdf_mesh_emit(X, Y, Z, *origin, voxel_size, p(f), p(w), p(c), min_weight, p(scratch), T, p(vertices),
-                                       p(colors), _lib.current_stream()), "fs_tsdf_mesh_emit")
+        _lib.launch("fs_tsdf_mesh_emit", X, Y, Z, *origin, voxel_size, p(f), p(w), p(c), min_weight, p(scratch), T, p(vertices),
+                    p(colors))
     return vertices, colors
 
 

@@ -1,26 +1,91 @@
-"""CPU checks of the drop-in boundary: libfreesplat_hip.so loads without a GPU and exports every
-symbol include/freesplat_amd.h declares (no compute calls here)."""
+"""CPU checks of the drop-in boundary: libfreesplat_hip.so loads without a GPU, and every header under include/ agrees with
+its record in _lib.HEADERS and with the built library (no compute calls here)."""
 import ctypes
+import itertools
 import os
 import re
 
 import pytest
 
+from freesplat_amd import _lib
+from util_abi import INCLUDE, declared_names, header_text
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _declared():
-    text = open(os.path.join(ROOT, "include", "freesplat_amd.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(fs_[a-z0-9_A-Z]+)\s*\(", text)))
+def _bare_library():
+    if not os.path.exists(_lib.LIB_PATH):
+        _lib.build()
+    return ctypes.CDLL(_lib.LIB_PATH)
+
+
+def test_the_registry_names_every_header_once_with_the_known_sizes_and_revisions():
+    files = [h.file for h in _lib.HEADERS]
+    assert sorted(files) == sorted(f for f in os.listdir(INCLUDE) if f.startswith("freesplat_amd") and f.endswith(".h"))
+    assert len(set(files)) == len(files) == 11
+    assert [len(h.signatures) for h in _lib.HEADERS] == [93, 5, 3, 6, 5, 6, 5, 6, 5, 4, 6]
+    assert tuple(h.revision for h in _lib.HEADERS) == (9, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1)
+    pairs = list(itertools.combinations(_lib.HEADERS, 2))
+    assert len(pairs) == 55
+    for a, b in pairs:
+        assert not set(a.signatures) & set(b.signatures), (a.file, b.file)
+    # the module attributes that tests, benchmarks and the integration notes read are the registry's own objects
+    tables = ("SIGNATURES", "LOSS_SIGNATURES", "OPTIM_SIGNATURES", "DENSITY_SIGNATURES", "DEPTHLOSS_SIGNATURES", "NORMALS_SIGNATURES",
+              "EXPOSURE_SIGNATURES", "MVDEPTH_SIGNATURES", "TRANSFORM_SIGNATURES", "POSE_SIGNATURES", "TSDF_SIGNATURES")
+    versions = ("ABI_VERSION", "LOSS_API_VERSION", "OPTIM_API_VERSION", "DENSITY_API_VERSION", "DEPTHLOSS_API_VERSION",
+                "NORMALS_API_VERSION", "EXPOSURE_API_VERSION", "MVDEPTH_API_VERSION", "TRANSFORM_API_VERSION", "POSE_API_VERSION",
+                "TSDF_API_VERSION")
+    for h, table, version in zip(_lib.HEADERS, tables, versions):
+        assert h.signatures is getattr(_lib, table) and h.revision == getattr(_lib, version), h.file
+
+
+@pytest.mark.parametrize("h", _lib.HEADERS, ids=lambda h: h.file)
+def test_every_header_is_exported_bound_and_at_its_revision(h):
+    """What each feature's host test asserts of its own header, for every header: the declared names are exported by the bare
+    library and are exactly the table's; the header defines its revision macro, and the library answers that value through
+    the bare handle and through the binding."""
+    L = _bare_library()
+    names = declared_names(h.file)
+    assert names and h.version_fn in names
+    for n in names:
+        assert hasattr(L, n), f"{n} declared in include/{h.file} but not exported"
+    assert set(names) == set(h.signatures)
+    assert re.search(rf"#define\s+{h.macro}\s+{h.revision}\b", header_text(h.file))
+    assert getattr(L, h.version_fn)() == h.revision == getattr(_lib.lib(), h.version_fn)()
+
+
+# lib()'s refusal of a library at another revision, as the binding worded it before the registry (here: the library is at
+# `got`, the binding is made to expect one more)
+MISMATCH = {
+    "freesplat_amd.h": "{lib} has ABI revision 9, this binding expects 10 (include/freesplat_amd.h FS_ABI_VERSION): rebuild the library",
+    "freesplat_amd_loss.h": "{lib} has loss API revision 1, this binding expects 2 (include/freesplat_amd_loss.h FS_LOSS_API_VERSION): rebuild the library",
+    "freesplat_amd_optim.h": "{lib} has optimizer API revision 1, this binding expects 2 (include/freesplat_amd_optim.h FS_OPTIM_API_VERSION): rebuild the library",
+    "freesplat_amd_density.h": "{lib} has density API revision 1, this binding expects 2 (include/freesplat_amd_density.h FS_DENSITY_API_VERSION): rebuild the library",
+    "freesplat_amd_depthloss.h": "{lib} has depth-loss API revision 1, this binding expects 2 (include/freesplat_amd_depthloss.h FS_DEPTHLOSS_API_VERSION): rebuild the library",
+    "freesplat_amd_normals.h": "{lib} has normals API revision 1, this binding expects 2 (include/freesplat_amd_normals.h FS_NORMALS_API_VERSION): rebuild the library",
+    "freesplat_amd_exposure.h": "{lib} has exposure API revision 1, this binding expects 2 (include/freesplat_amd_exposure.h FS_EXPOSURE_API_VERSION): rebuild the library",
+    "freesplat_amd_mvdepth.h": "{lib} has multi-view depth API revision 1, this binding expects 2 (include/freesplat_amd_mvdepth.h FS_MVDEPTH_API_VERSION): rebuild the library",
+    "freesplat_amd_transform.h": "{lib} has transform API revision 1, this binding expects 2 (include/freesplat_amd_transform.h FS_TRANSFORM_API_VERSION): rebuild the library",
+    "freesplat_amd_pose.h": "{lib} has pose API revision 1, this binding expects 2 (include/freesplat_amd_pose.h FS_POSE_API_VERSION): rebuild the library",
+    "freesplat_amd_tsdf.h": "{lib} has TSDF API revision 1, this binding expects 2 (include/freesplat_amd_tsdf.h FS_TSDF_API_VERSION): rebuild the library",
+}
+
+
+@pytest.mark.parametrize("i", range(11), ids=lambda i: _lib.HEADERS[i].file)
+def test_a_library_at_another_revision_is_refused_and_not_cached(i, monkeypatch):
+    _bare_library()
+    h = _lib.HEADERS[i]
+    monkeypatch.setattr(_lib, "HEADERS", _lib.HEADERS[:i] + (h._replace(revision=h.revision + 1),) + _lib.HEADERS[i + 1:])
+    monkeypatch.setattr(_lib, "_lib", None)
+    with pytest.raises(_lib.FreeSplatHipError) as e:
+        _lib.lib()
+    assert str(e.value) == MISMATCH[h.file].format(lib=_lib.LIB_PATH)
+    assert _lib._lib is None
 
 
 def test_header_symbols_exported_and_bound():
-    from freesplat_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    L = ctypes.CDLL(_lib.LIB_PATH)
-    names = _declared()
+    L = _bare_library()
+    names = declared_names("freesplat_amd.h")
     assert "fs_raster_forward" in names and "fs_raster_backward" in names
     for n in names:
         assert hasattr(L, n), f"{n} declared in include/freesplat_amd.h but not exported"

@@ -12,6 +12,7 @@ import torch
 
 import metrics_ref as R
 import ssim_loss_ref as SR
+from util_abi import declared_names
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = [(11, 11), (13, 40), (70, 300)]
@@ -22,12 +23,6 @@ def _pair(B, C_, H, W, seed):
     gt = torch.rand(B, C_, H, W, generator=g, dtype=torch.float64)
     pred = (gt + 0.1 * torch.randn(B, C_, H, W, generator=g, dtype=torch.float64)).clamp(-0.2, 1.2)
     return pred, gt
-
-
-def _names(header):
-    text = open(os.path.join(ROOT, "include", header)).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(fs_[a-z0-9_A-Z]+)\s*\(", text)))
 
 
 @pytest.mark.parametrize("H,W", SHAPES)
@@ -74,7 +69,7 @@ def test_loss_header_is_exported_and_bound():
     if not os.path.exists(_lib.LIB_PATH):
         _lib.build()
     L = C.CDLL(_lib.LIB_PATH)
-    names = _names("freesplat_amd_loss.h")
+    names = declared_names("freesplat_amd_loss.h")
     assert "fs_ssim_loss_forward" in names and "fs_ssim_loss_backward" in names and len(names) == 5
     for n in names:
         assert hasattr(L, n), f"{n} declared in include/freesplat_amd_loss.h but not exported"
@@ -92,7 +87,7 @@ def test_main_header_keeps_its_symbol_set():
     """The new entry points live in their own header: include/freesplat_amd.h declares the names it declared before
     (their count and the digest of the sorted list), and FS_ABI_VERSION stays 9."""
     from freesplat_amd import _lib
-    names = _names("freesplat_amd.h")
+    names = declared_names("freesplat_amd.h")
     assert set(names) == set(_lib.SIGNATURES) and not any("ssim_loss" in n or "loss_api" in n for n in names)
     assert len(names) == 93
     assert hashlib.sha256("\n".join(names).encode()).hexdigest() == "590e07f0e577c48904722252d8732a99cfa85cacaed1070a8f78789024ebb521"
