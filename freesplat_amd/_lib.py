@@ -1,4 +1,4 @@
-"""ctypes binding of libfreesplat_hip.so (C ABI: the headers under include/, one record each in HEADERS below).
+"""ctypes binding of libfreesplat_hip.so (C ABI: the headers under include/, one record each in HEADERS or EXTENSION_HEADERS below).
 
 The product path has NO fallback: if the HIP library is missing or a call fails this module
 raises.  `build()` compiles the library in-tree with hipcc for gfx950.
@@ -37,6 +37,7 @@ MVDEPTH_API_VERSION = 1
 TRANSFORM_API_VERSION = 1
 POSE_API_VERSION = 1
 TSDF_API_VERSION = 1
+RAYCAST_API_VERSION = 1
 
 RASTER_TILE_CULL = 1
 RASTER_SH_FP16 = 2
@@ -71,6 +72,10 @@ TSDF_MAX_VIEWS = 64
 TSDF_BRICK = (32, 8, 4)      # grid points (x, y, z) one workgroup of fs_tsdf_integrate owns
 TSDF_MESH_RUN = 256          # consecutive cubes one workgroup of the extraction owns
 TSDF_NO_BRICK_SKIP = 1
+
+RAYCAST_TILE = 16            # pixels (x and y) one workgroup of fs_tsdf_raycast owns
+RAYCAST_MAX_REFINE = 32
+RAYCAST_MAX_STEPS = 1 << 20
 
 
 def build(force: bool = False) -> str:
@@ -275,6 +280,12 @@ TSDF_SIGNATURES = {
     "fs_tsdf_mesh_emit": (C.c_int, [C.c_int32] * 3 + [C.c_float] * 4 + [_VP] * 3 + [C.c_float, _VP, C.c_int64] + [_VP] * 3),
 }
 
+RAYCAST_SIGNATURES = {
+    "fs_raycast_api_version": (C.c_int, []),
+    "fs_tsdf_raycast": (C.c_int, [C.c_int32] * 3 + [C.c_float] * 5 + [_VP] * 3 + [C.c_int32] * 3 + [_VP] * 2 + [C.c_float] * 5
+                        + [C.c_int32] * 2 + [_VP] * 5),
+}
+
 
 class Header(NamedTuple):
     file: str          # under include/
@@ -309,6 +320,14 @@ HEADERS = (
     Header("freesplat_amd_tsdf.h", "FS_TSDF_API_VERSION", "fs_tsdf_api_version", TSDF_API_VERSION, "TSDF API", TSDF_SIGNATURES),
 )
 
+# Headers added after those eleven: include/freesplat_ext_<x>.h, the same records, bound and checked by lib() after HEADERS.
+# (The eleven above, their table sizes and their revisions are pinned by tests/test_abi.py, a file that does not change;
+# tests/test_abi_extensions.py holds every record here to its header and to the built library in the same way.)
+EXTENSION_HEADERS = (
+    Header("freesplat_ext_raycast.h", "FS_RAYCAST_API_VERSION", "fs_raycast_api_version", RAYCAST_API_VERSION, "ray-cast API",
+           RAYCAST_SIGNATURES),
+)
+
 
 def lib():
     global _lib
@@ -323,7 +342,7 @@ def lib():
         # device is detected"
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
-        for h in HEADERS:
+        for h in HEADERS + EXTENSION_HEADERS:
             for name, (res, args) in h.signatures.items():
                 fn = getattr(L, name)  # AttributeError if the library lacks a declared symbol
                 fn.restype = res

@@ -15,14 +15,19 @@ those of DESIGN.md "TSDF fusion":
 `intrinsics` = (fx, fy, cx, cy) in pixels, integer pixel coordinates being pixel centres (see normals_loss.py); the caller folds
 its own convention into cx, cy.  `extrinsics` are camera-to-world [V, 4, 4], as render_views takes them.
 
-Integration is an evaluation artefact: no autograd, no backward.  Device tensors only: there is no CPU / eager path.  integrate
-makes no host synchronisation when `extrinsics` is a device tensor and is capturable in a graph; extract_mesh reads one number
-(the triangle count) back.
+  raycast  per view and pixel a ray marched through the volume in z-depth (include/freesplat_ext_raycast.h, csrc/tsdf_raycast.hip,
+           DESIGN.md "TSDF ray casting"): depth [V, H, W] (0 = no hit, the rasterizer's hole), camera-space normals [V, 3, H, W] in
+           depth_normals' convention (NaN = missing, what normals_loss(gt_normals=...) skips), colour, march samples per ray
+
+Integration and ray casting are evaluation artefacts: no autograd, no backward.  Device tensors only: there is no CPU / eager
+path.  integrate and raycast make no host synchronisation when `extrinsics` is a device tensor and are capturable in a graph;
+extract_mesh reads one number (the triangle count) back.
 """
 from __future__ import annotations
 
 import ctypes as C
 import math
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -185,6 +190,18 @@ class TSDFVolume:
         """The triangle soup (vertices [T, 3, 3], colors [T, 3, 3] | None) of the zero level set over the observed cubes."""
         return extract_mesh(self.tsdf, self.weight, self.color, self.origin, self.voxel_size, min_weight)
 
+    # ---- ray cast -------------------------------------------------------------------------------------------------------------
+
+    def raycast(self, intrinsics, extrinsics, hw, *, min_depth: float = 0.0, max_depth: float = math.inf, min_weight: float = 1.0,
+                step_min: float = 0.5, relax: float = 0.8, refine: int = 4, max_steps: int | None = None, normals: bool = True,
+                color: bool | None = None, return_steps: bool = False) -> "RayCast":
+        """The volume seen from V cameras: RayCast(depth [V, H, W], normals [V, 3, H, W] | None, color [V, 3, H, W] | None,
+        steps [V, H, W] int32 | None).  color = None: iff the volume has colour.  The keywords are those of the module-level
+        raycast (whose colour switch is `color_out`, `color` being the volume's planes there)."""
+        return raycast(self.tsdf, self.weight, self.color, self.origin, self.voxel_size, self.trunc, intrinsics, extrinsics, hw,
+                       min_depth=min_depth, max_depth=max_depth, min_weight=min_weight, step_min=step_min, relax=relax,
+                       refine=refine, max_steps=max_steps, normals=normals, color_out=color, return_steps=return_steps)
+
 
 def extract_mesh(tsdf: Tensor, weight: Tensor, color: Tensor | None, origin, voxel_size: float, min_weight: float = 1.0):
     """Marching tetrahedra over tsdf / weight [Z, Y, X] (and color [3, Z, Y, X]): plan, one read of the triangle count, emit."""
@@ -218,6 +235,95 @@ def extract_mesh(tsdf: Tensor, weight: Tensor, color: Tensor | None, origin, vox
         _lib.launch("fs_tsdf_mesh_emit", X, Y, Z, *origin, voxel_size, p(f), p(w), p(c), min_weight, p(scratch), T, p(vertices),
                     p(colors))
     return vertices, colors
+
+
+class RayCast(NamedTuple):
+    depth: Tensor                # [V, H, W] z-depth, 0 where the ray hits nothing
+    normals: Tensor | None       # [V, 3, H, W] camera space, NaN where there is none
+    color: Tensor | None         # [V, 3, H, W], 0 where there is none
+    steps: Tensor | None         # [V, H, W] int32 march samples per ray
+
+
+def cam_rows(extrinsics, device) -> Tensor:
+    """camera-to-world [V, 4, 4] -> its top three rows [V, 3, 4] fp32 on `device`, as given (no inverse).  A host matrix is
+    validated (finite, last row (0, 0, 0, 1)); a device matrix is taken as it is, without a synchronisation."""
+    if not isinstance(extrinsics, Tensor):
+        extrinsics = torch.as_tensor(np.asarray(extrinsics))
+    _args.no_grad_to(extrinsics, "extrinsics", _NAME)
+    E = extrinsics.detach()
+    if E.dim() != 3 or tuple(E.shape[1:]) != (4, 4) or E.shape[0] == 0:
+        raise ValueError(f"{_NAME}: extrinsics must be camera-to-world [V, 4, 4], got {tuple(E.shape)}")
+    if E.device.type != "cuda":
+        E = E.to(torch.float64)
+        last = torch.tensor([0.0, 0.0, 0.0, 1.0], dtype=torch.float64)
+        if not bool(torch.isfinite(E).all()) or not bool((E[:, 3] == last).all()):
+            raise ValueError(f"{_NAME}: extrinsics must be finite with a last row (0, 0, 0, 1)")
+    return E[:, :3, :].to(device=device, dtype=torch.float32).contiguous()
+
+
+def raycast(tsdf: Tensor, weight: Tensor, color: Tensor | None, origin, voxel_size: float, trunc: float, intrinsics, extrinsics,
+            hw, *, min_depth: float = 0.0, max_depth: float = math.inf, min_weight: float = 1.0, step_min: float = 0.5,
+            relax: float = 0.8, refine: int = 4, max_steps: int | None = None, normals: bool = True, color_out: bool | None = None,
+            return_steps: bool = False) -> RayCast:
+    """Ray casts tsdf / weight [Z, Y, X] (and color [3, Z, Y, X]) from V cameras into maps of hw = (H, W) pixels, in one launch.
+    color_out: whether the colour map is made (None: iff `color` is given).  step_min is in voxels, relax the share of the
+    truncated distance a step takes, refine the number of regula-falsi steps on the bracket, max_steps the bound of the march
+    (None: 4 (X + Y + Z))."""
+    for t, what in ((tsdf, "tsdf"), (weight, "weight"), (color, "color"), (intrinsics, "intrinsics")):
+        _args.no_grad_to(t, what, _NAME)
+    try:
+        H, W = (int(x) for x in hw)
+    except (TypeError, ValueError):
+        raise ValueError(f"{_NAME}: hw must be (H, W), got {hw!r}") from None
+    if H <= 0 or W <= 0 or H * W > 2 ** 31 - 1:
+        raise ValueError(f"{_NAME}: hw must be two positive sizes with H * W <= 2^31 - 1, got {(H, W)!r}")
+    voxel_size, trunc = _pos_finite(voxel_size, "voxel_size"), _pos_finite(trunc, "trunc")
+    step_min, relax = _pos_finite(step_min, "step_min"), _pos_finite(relax, "relax")
+    min_depth, max_depth, min_weight = float(min_depth), float(max_depth), float(min_weight)
+    if not min_depth >= 0.0 or math.isnan(max_depth):
+        raise ValueError(f"{_NAME}: min_depth must be >= 0 and max_depth not NaN, got {min_depth!r} and {max_depth!r}")
+    if not min_weight > 0.0:
+        raise ValueError(f"{_NAME}: min_weight must be positive, got {min_weight!r}")
+    origin = tuple(float(o) for o in origin)
+    if len(origin) != 3 or not all(math.isfinite(o) for o in origin):
+        raise ValueError(f"{_NAME}: origin must be three finite numbers, got {origin!r}")
+    if not isinstance(tsdf, Tensor) or not isinstance(weight, Tensor) or tsdf.dim() != 3 or tsdf.numel() == 0 or weight.shape != tsdf.shape:
+        raise ValueError(f"{_NAME}: tsdf and weight must be non-empty [Z, Y, X] tensors of one shape, got "
+                         f"{tuple(getattr(tsdf, 'shape', ()))} and {tuple(getattr(weight, 'shape', ()))}")
+    Z, Y, X = tsdf.shape
+    if color is not None and (not isinstance(color, Tensor) or tuple(color.shape) != (3, Z, Y, X)):
+        raise ValueError(f"{_NAME}: color must be [3, {Z}, {Y}, {X}], got {tuple(getattr(color, 'shape', ()))}")
+    if color_out is None:
+        color_out = color is not None
+    if color_out and color is None:
+        raise ValueError(f"{_NAME}: a colour map needs a volume with colour planes")
+    refine = int(refine)
+    if not 0 <= refine <= _lib.RAYCAST_MAX_REFINE:
+        raise ValueError(f"{_NAME}: refine must be in 0 .. {_lib.RAYCAST_MAX_REFINE}, got {refine}")
+    max_steps = 4 * (X + Y + Z) if max_steps is None else int(max_steps)
+    if not 1 <= max_steps <= _lib.RAYCAST_MAX_STEPS:
+        raise ValueError(f"{_NAME}: max_steps must be in 1 .. 2^20, got {max_steps}")
+    f = _args.device_f32(tsdf, "tsdf", _NAME).detach()
+    w = _args.device_f32(weight, "weight", _NAME).detach()
+    c = None if color is None else _args.device_f32(color, "color", _NAME).detach()
+    if w.device != f.device or (c is not None and c.device != f.device):
+        raise ValueError(f"{_NAME}: tsdf, weight and color must live on one device")
+    rows = cam_rows(extrinsics, f.device)
+    V = rows.shape[0]
+    k = torch.as_tensor(intrinsics).detach().to(device=f.device, dtype=torch.float32)
+    if k.shape == (4,):
+        k = k.expand(V, 4)
+    if tuple(k.shape) != (V, 4):
+        raise ValueError(f"{_NAME}: intrinsics must be [4] or [{V}, 4] = (fx, fy, cx, cy), got {tuple(k.shape)}")
+    k = k.contiguous()
+    depth = torch.empty(V, H, W, device=f.device)
+    nrm = torch.empty(V, 3, H, W, device=f.device) if normals else None
+    col = torch.empty(V, 3, H, W, device=f.device) if color_out else None
+    steps = torch.empty(V, H, W, dtype=torch.int32, device=f.device) if return_steps else None
+    p = _lib.ptr
+    _lib.launch("fs_tsdf_raycast", X, Y, Z, *origin, voxel_size, trunc, p(f), p(w), p(c), V, H, W, p(rows), p(k), min_depth,
+                max_depth, min_weight, step_min, relax, refine, max_steps, p(depth), p(nrm), p(col), p(steps))
+    return RayCast(depth, nrm, col, steps)
 
 
 def weld(vertices: Tensor, colors: Tensor | None = None, drop_degenerate: bool = True):
