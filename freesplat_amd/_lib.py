@@ -1,4 +1,5 @@
-"""ctypes binding of libfreesplat_hip.so (C ABI: the headers under include/, one record each in HEADERS or EXTENSION_HEADERS below).
+"""ctypes binding of libfreesplat_hip.so (C ABI: the headers under include/, one record each in HEADERS, EXTENSION_HEADERS or
+ADDON_HEADERS below).
 
 The product path has NO fallback: if the HIP library is missing or a call fails this module
 raises.  `build()` compiles the library in-tree with hipcc for gfx950.
@@ -38,6 +39,7 @@ TRANSFORM_API_VERSION = 1
 POSE_API_VERSION = 1
 TSDF_API_VERSION = 1
 RAYCAST_API_VERSION = 1
+GEOMETRY_API_VERSION = 1
 
 RASTER_TILE_CULL = 1
 RASTER_SH_FP16 = 2
@@ -76,6 +78,12 @@ TSDF_NO_BRICK_SKIP = 1
 RAYCAST_TILE = 16            # pixels (x and y) one workgroup of fs_tsdf_raycast owns
 RAYCAST_MAX_REFINE = 32
 RAYCAST_MAX_STEPS = 1 << 20
+
+NN_MAX_SIDE = 1024           # cells per side of a nearest-neighbour grid
+NN_MAX_CELLS = 1 << 24
+NN_MAX_THRESHOLDS = 8
+NN_SUM_FIELDS = 3 + NN_MAX_THRESHOLDS
+NN_SUM_FINITE, NN_SUM_WITHIN, NN_SUM_DIST, NN_SUM_TAU = 0, 1, 2, 3
 
 
 def build(force: bool = False) -> str:
@@ -286,6 +294,15 @@ RAYCAST_SIGNATURES = {
                         + [C.c_int32] * 2 + [_VP] * 5),
 }
 
+GEOMETRY_SIGNATURES = {
+    "fs_geometry_api_version": (C.c_int, []),
+    "fs_nn_grid_keys": (C.c_int, [C.c_int32, _VP] + [C.c_float] * 4 + [C.c_int32] * 3 + [_VP, _VP]),
+    "fs_nn_grid_gather": (C.c_int, [C.c_int32] + [_VP] * 4),
+    "fs_nn_query_scratch_bytes": (C.c_size_t, [C.c_int32]),
+    "fs_nn_query": (C.c_int, [C.c_int32, _VP, _VP, C.c_int32, _VP, _VP] + [C.c_float] * 4 + [C.c_int32] * 3
+                    + [C.c_float, C.c_int32, C.POINTER(C.c_float)] + [_VP] * 5),
+}
+
 
 class Header(NamedTuple):
     file: str          # under include/
@@ -328,6 +345,15 @@ EXTENSION_HEADERS = (
            RAYCAST_SIGNATURES),
 )
 
+# Headers added from now on: include/ext/<name>.h (`file` is relative to include/), the same records, bound and checked by lib()
+# after the two tuples above.  Those two are CLOSED: tests/test_abi.py and tests/test_abi_extensions.py pin their files, counts,
+# table sizes and revisions literally, and a test file does not change.  This tuple is open: tests/test_abi_addons.py is
+# parametrised over it and builds what it expects from each record's own fields, so a further record needs no edit to any test.
+ADDON_HEADERS = (
+    Header("ext/geometry.h", "FS_GEOMETRY_API_VERSION", "fs_geometry_api_version", GEOMETRY_API_VERSION, "geometry API",
+           GEOMETRY_SIGNATURES),
+)
+
 
 def lib():
     global _lib
@@ -342,7 +368,7 @@ def lib():
         # device is detected"
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
-        for h in HEADERS + EXTENSION_HEADERS:
+        for h in HEADERS + EXTENSION_HEADERS + ADDON_HEADERS:
             for name, (res, args) in h.signatures.items():
                 fn = getattr(L, name)  # AttributeError if the library lacks a declared symbol
                 fn.restype = res
