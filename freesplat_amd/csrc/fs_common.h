@@ -6,6 +6,7 @@
 // division are the correctly rounded forms hipcc emits by default.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 
 #include "../../include/freesplat_amd.h"
@@ -42,6 +43,10 @@ struct ScopedStage {
 };
 
 __host__ __device__ inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// argument checks of the C entry points (NaN fails both)
+inline bool host_finite(float x) { return fabsf(x) < INFINITY; }
+inline bool host_pos_finite(float x) { return x > 0.0f && x < INFINITY; }
 
 // ---- deterministic exp (x <= 0 on the hot path): the same operation sequence as the CPU checker's exp ----
 constexpr float kExpC1 = 0.9999997019767761f, kExpC2 = 0.4999915063381195f, kExpC3 = 0.1666763573884964f, kExpC4 = 0.04189793020486832f, kExpC5 = 0.008290314115583897f;

@@ -120,7 +120,7 @@ __global__ __launch_bounds__(kSumThreads) void finalize_rows_kernel(int K, int G
 // A thread owns four consecutive floats that start at a multiple of four from the array's base, so whether they can go through
 // one 16-byte access depends on the base address alone.  Which path moved a value changes nothing about its arithmetic.
 
-__device__ __forceinline__ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+__host__ __device__ __forceinline__ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 struct Px4 {
     float v[4];

@@ -2,7 +2,7 @@
 // (include/freesplat_amd_density.h; freesplat_amd.refine.GaussianAdam.accumulate / densify / reset_opacity).
 //
 //   accumulate     one elementwise launch over the view-space gradient norms of the visible rows.
-//   plan           three launches in the form of ptf.hip's compaction: every workgroup classifies kScanBlock = 1024 source rows
+//   plan           three launches, a compaction on fs_scan.h's helpers: every workgroup classifies kScanBlock = 1024 source rows
 //                  (256 threads x 4) and counts their output rows; ONE workgroup scans the block sums (a thread takes a
 //                  contiguous slice of them, so any number of blocks is covered); every workgroup scans its own rows and
 //                  scatters offset[] and the output -> source map src[].  Integer arithmetic only, apart from the single fp32
@@ -23,6 +23,8 @@
 #include <math.h>
 
 #include "../../include/freesplat_amd_density.h"
+#include "fs_reduce.h"
+#include "fs_scan.h"
 #include "gaussian_act.h"
 
 namespace fs {
@@ -32,13 +34,10 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kVec = 4;
 constexpr uint32_t kScanBlock = kThreads * kVec;             // source rows per plan workgroup
-constexpr int kScanThreads = 1024;                           // threads of the block-sum scan
 constexpr uint32_t kChunk = kThreads * kVec;                 // destination floats per apply workgroup and iteration
 constexpr uint32_t kMaxGrid = 2048;                          // 8 workgroups per CU; the rest is grid-strided
 constexpr float kLogSplit = 0.47000363f;                     // logf(1.6f)
 constexpr uint32_t kSplitTag = 0x80000000u;                  // src[o] = (2 i + j) | kSplitTag for the children of a split row
-
-__host__ __device__ inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 // ---------------------------------------------------------------------------------------------------------- accumulate
 
@@ -84,20 +83,6 @@ __device__ __forceinline__ uint32_t classify(const PlanArgs& a, uint32_t i)
 
 __device__ __forceinline__ uint32_t outputs_of(uint32_t kind) { return kind == FS_DENSITY_DROPPED ? 0u : kind == FS_DENSITY_KEPT ? 1u : 2u; }
 
-// 4 consecutive kinds starting at `base`, one per byte; rows past n read as dropped
-__device__ __forceinline__ uint32_t load_kinds(const uint8_t* __restrict__ f, uint32_t base, uint32_t n)
-{
-    uint32_t v = 0;
-    if (base + 3u < n && (((uintptr_t)(f + base)) & 3u) == 0) {
-        v = *reinterpret_cast<const uint32_t*>(f + base);
-    } else {
-#pragma unroll
-        for (uint32_t k = 0; k < 4; ++k)
-            if (base + k < n) v |= (uint32_t)f[base + k] << (8u * k);
-    }
-    return v;
-}
-
 // block_counts: four runs of nb uint32 -- output rows, clones, splits, drops of each workgroup's 1024 source rows
 __global__ __launch_bounds__(kThreads) void density_count_kernel(const PlanArgs a, uint8_t* __restrict__ kind,
                                                                  uint32_t* __restrict__ block_counts)
@@ -114,55 +99,26 @@ __global__ __launch_bounds__(kThreads) void density_count_kernel(const PlanArgs 
         c += (unsigned long long)outputs_of(kd) | ((unsigned long long)(kd == FS_DENSITY_CLONE) << 16) |
              ((unsigned long long)(kd == FS_DENSITY_SPLIT) << 32) | ((unsigned long long)(kd == FS_DENSITY_DROPPED) << 48);
     }
-    if (base + 3u < a.N && (((uintptr_t)(kind + base)) & 3u) == 0) {
-        *reinterpret_cast<uint32_t*>(kind + base) = packed;
-    } else {
-#pragma unroll
-        for (uint32_t k = 0; k < 4; ++k)
-            if (base + k < a.N) kind[base + k] = (uint8_t)(packed >> (8u * k));
-    }
-#pragma unroll
-    for (int s = kWave / 2; s > 0; s >>= 1) c += __shfl_down(c, s, kWave);
+    store_flags4(kind, base, a.N, packed);
+    c = wave_sum<unsigned long long>(c);
     if ((threadIdx.x & (kWave - 1)) == 0) s_w[threadIdx.x / kWave] = c;
     __syncthreads();
     if (threadIdx.x == 0) {
-        const unsigned long long t = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+        const unsigned long long t = waves_total<unsigned long long>(s_w, 1);
 #pragma unroll
         for (uint32_t q = 0; q < 4; ++q) block_counts[q * a.nb + blockIdx.x] = (uint32_t)(t >> (16u * q)) & 0xFFFFu;
     }
 }
 
-// One workgroup: exclusive scan of run 0 in place, sums of all four runs into totals.  A thread takes a contiguous slice of
-// ceil(nb / 1024) entries, so the loop covers any nb.
+// One workgroup: exclusive scan of run 0 in place, sums of all four runs into totals (fs_scan.h's slice_scan).
 __global__ __launch_bounds__(kScanThreads) void density_scan_blocks_kernel(uint32_t nb, uint32_t* __restrict__ block_counts,
                                                                            int32_t* __restrict__ totals)
 {
     __shared__ uint32_t part[kScanThreads];
-    const uint32_t t = threadIdx.x;
-    const uint32_t per = (nb + kScanThreads - 1u) / kScanThreads;
-    const uint32_t lo = min(nb, t * per), hi = min(nb, lo + per);
     for (uint32_t q = 0; q < 4; ++q) {
         uint32_t* a = block_counts + (size_t)q * nb;
-        uint32_t s = 0;
-        for (uint32_t k = lo; k < hi; ++k) s += a[k];
-        part[t] = s;
-        __syncthreads();
-        for (uint32_t off = 1; off < (uint32_t)kScanThreads; off <<= 1) {
-            const uint32_t v = (t >= off) ? part[t - off] : 0u;
-            __syncthreads();
-            part[t] += v;
-            __syncthreads();
-        }
-        if (q == 0) {
-            uint32_t run = part[t] - s;
-            for (uint32_t k = lo; k < hi; ++k) {
-                const uint32_t c = a[k];
-                a[k] = run;
-                run += c;
-            }
-        }
-        if (t == (uint32_t)kScanThreads - 1u) totals[q] = (int32_t)part[kScanThreads - 1];
-        __syncthreads();
+        const uint32_t total = slice_scan<uint32_t>(a, nb, q == 0 ? a : nullptr, part);
+        if (threadIdx.x == kScanThreads - 1) totals[q] = (int32_t)total;
     }
 }
 
@@ -172,28 +128,14 @@ __global__ __launch_bounds__(kThreads) void density_emit_kernel(uint32_t N, cons
 {
     __shared__ uint32_t s_w[kThreads / kWave];
     const uint32_t base = blockIdx.x * kScanBlock + threadIdx.x * kVec;
-    const uint32_t v = load_kinds(kind, base, N);            // rows past N: dropped, no outputs
+    const uint32_t v = load_flags4(kind, base, N);           // rows past N: dropped, no outputs
     uint32_t cnt[4], c = 0;
 #pragma unroll
     for (uint32_t k = 0; k < 4; ++k) {
         cnt[k] = outputs_of((v >> (8u * k)) & 0xFFu);
         c += cnt[k];
     }
-    // exclusive scan of c over the 256 threads: wave inclusive scan, then the wave totals via LDS
-    const uint32_t lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    uint32_t inc = c;
-#pragma unroll
-    for (int s = 1; s < kWave; s <<= 1) {
-        const uint32_t o = __shfl_up(inc, s, kWave);
-        if (lane >= (uint32_t)s) inc += o;
-    }
-    if (lane == kWave - 1) s_w[wave] = inc;
-    __syncthreads();
-    uint32_t wave_off = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < kThreads / kWave; ++k)
-        if (k < wave) wave_off += s_w[k];
-    uint32_t rank = block_offsets[blockIdx.x] + wave_off + inc - c;
+    uint32_t rank = block_offsets[blockIdx.x] + block_excl_scan(c, s_w);
     uint32_t off[4];
 #pragma unroll
     for (uint32_t k = 0; k < 4; ++k) {

@@ -175,11 +175,9 @@ __global__ __launch_bounds__(kSumThreads) void nn_query_kernel(const NnQueryArgs
     }
 }
 
-bool nn_finite(float x) { return fabsf(x) < INFINITY; }
-
 bool nn_grid_ok(float lx, float ly, float lz, float cell, int nx, int ny, int nz)
 {
-    if (!nn_finite(lx) || !nn_finite(ly) || !nn_finite(lz)) return false;
+    if (!host_finite(lx) || !host_finite(ly) || !host_finite(lz)) return false;
     if (!(cell >= 1e-30f && cell <= 1e15f)) return false;                               // (NaN fails)
     if (nx < 1 || ny < 1 || nz < 1 || nx > FS_NN_MAX_SIDE || ny > FS_NN_MAX_SIDE || nz > FS_NN_MAX_SIDE) return false;
     return (long long)nx * ny * nz <= FS_NN_MAX_CELLS;

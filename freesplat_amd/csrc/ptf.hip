@@ -19,6 +19,9 @@
 
 #include <cassert>
 
+#include "fs_reduce.h"
+#include "fs_scan.h"
+
 namespace fs {
 
 constexpr uint32_t kZInit = 0x461C4000u;  // bits of 10000.0f (encoder_freesplat.py:464)
@@ -134,71 +137,29 @@ __global__ __launch_bounds__(256) void ptf_flags_count_kernel(int M, const int32
             v |= (on ? 1u : 0u) << (8 * k);
         }
     }
-    uint8_t* f = second ? app : win;
-    if (base + 3 < n && ((((uintptr_t)(f + base)) & 3) == 0)) {
-        *(uint32_t*)(f + base) = v;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (base + k < n) f[base + k] = (uint8_t)((v >> (8 * k)) & 1u);
-    }
-    uint32_t c = __popc(v);
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) c += __shfl_xor(c, s, 64);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = c;
+    store_flags4(second ? app : win, (uint32_t)base, (uint32_t)n, v);   // every byte of v is 0 or 1
+    const uint32_t c = wave_sum<uint32_t>(__popc(v));
+    if ((threadIdx.x & (kWave - 1)) == 0) s_w[threadIdx.x / kWave] = c;
     __syncthreads();
-    if (threadIdx.x == 0) block_counts[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    if (threadIdx.x == 0) block_counts[blockIdx.x] = waves_total<uint32_t>(s_w, 1);
 }
 
 // ---- order-preserving compaction -----------------------------------------------------------------
-__device__ __forceinline__ uint32_t load4(const uint8_t* __restrict__ f, int base, int n)
-{
-    // 4 consecutive byte flags (0/1) starting at `base`, zero past n
-    uint32_t v = 0;
-    if (base + 3 < n && ((((uintptr_t)(f + base)) & 3) == 0)) {
-        v = *(const uint32_t*)(f + base);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (base + k < n) v |= (uint32_t)f[base + k] << (8 * k);
-    }
-    return v;
-}
-
-// exclusive scan of the two block-count ranges (one workgroup); counts = {n_keep, n_fuse, n_append}
-__global__ __launch_bounds__(1024) void ptf_scan_blocks_kernel(int M, const int32_t* __restrict__ Mp, int nbM, int nbP,
+// exclusive scan of the two block-count ranges in place (one workgroup, fs_scan.h's slice_scan);
+// counts = {n_keep, n_fuse, n_append, size of the next state}
+__global__ __launch_bounds__(kScanThreads) void ptf_scan_blocks_kernel(int M, const int32_t* __restrict__ Mp, int nbM, int nbP,
                                                                uint32_t* __restrict__ block_counts,
                                                                int32_t* __restrict__ counts)
 {
-    __shared__ uint32_t part[1024];
+    __shared__ uint32_t part[kScanThreads];
     if (Mp) M = *Mp;
-    for (int range = 0; range < 2; ++range) {
-        uint32_t* a = block_counts + (range ? nbM : 0);
-        const int n = range ? nbP : nbM;
-        const int t = threadIdx.x;
-        const int per = (n + 1023) / 1024;
-        const int lo = min(n, t * per), hi = min(n, lo + per);
-        uint32_t s = 0;
-        for (int k = lo; k < hi; ++k) s += a[k];
-        part[t] = s;
-        __syncthreads();
-        for (int off = 1; off < 1024; off <<= 1) {
-            const uint32_t v = (t >= off) ? part[t - off] : 0u;
-            __syncthreads();
-            part[t] += v;
-            __syncthreads();
-        }
-        uint32_t run = part[t] - s;
-        for (int k = lo; k < hi; ++k) {
-            const uint32_t c = a[k];
-            a[k] = run;
-            run += c;
-        }
-        if (t == 1023) {
-            if (range == 0) { counts[1] = (int32_t)part[1023]; counts[0] = M - (int32_t)part[1023]; }
-            else { counts[2] = (int32_t)part[1023]; counts[3] = counts[0] + counts[1] + counts[2]; }  // [3]: size of the next state
-        }
-        __syncthreads();
+    const int32_t n_fuse = (int32_t)slice_scan<uint32_t>(block_counts, (uint32_t)nbM, block_counts, part);
+    const int32_t n_append = (int32_t)slice_scan<uint32_t>(block_counts + nbM, (uint32_t)nbP, block_counts + nbM, part);
+    if (threadIdx.x == kScanThreads - 1) {                   // the thread that holds the totals
+        counts[0] = M - n_fuse;
+        counts[1] = n_fuse;
+        counts[2] = n_append;
+        counts[3] = M + n_append;                            // size of the next state
     }
 }
 
@@ -219,7 +180,7 @@ __global__ __launch_bounds__(256) void ptf_emit_kernel(int M, const int32_t* __r
     const int n = second ? P : M;
     const int blk = second ? blockIdx.x - nbM : blockIdx.x;
     const int base = blk * kScanBlock + threadIdx.x * 4;
-    const uint32_t v = load4(f, base, n);
+    const uint32_t v = load_flags4(f, (uint32_t)base, (uint32_t)n);
     if (second) {
         // the z-buffer's last reader (the flags) is done: leave it cleared for the next fold step of this scratch, which
         // then needs no fill launch of its own (fs_ptf_fold)
@@ -227,22 +188,7 @@ __global__ __launch_bounds__(256) void ptf_emit_kernel(int M, const int32_t* __r
         for (int k = 0; k < 4; ++k)
             if (base + k < n) zbuf[base + k] = 0xFFFFFFFFu;
     }
-    const uint32_t c = __popc(v);
-    // exclusive scan of c over the 256 threads: wave inclusive scan, then 4 wave totals via LDS
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t inc = c;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const uint32_t o = __shfl_up(inc, s, 64);
-        if (lane >= s) inc += o;
-    }
-    if (lane == 63) s_w[wave] = inc;
-    __syncthreads();
-    uint32_t wave_off = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        if (k < wave) wave_off += s_w[k];
-    uint32_t rank = block_offsets[blockIdx.x] + wave_off + inc - c;  // set flags before `base`
+    uint32_t rank = block_offsets[blockIdx.x] + block_excl_scan(__popc(v), s_w);  // set flags before `base`
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int e = base + k;
@@ -910,7 +856,7 @@ static int ptf_match_impl(int32_t M, const int32_t* Mp, int32_t h, int32_t w, co
                            pix_of, zbits_of, zbuf);
     hipLaunchKernelGGL(ptf_flags_count_kernel, dim3(nbM + nbP), dim3(256), 0, st, M, Mp, P, nbM, pix_of, zbits_of, zbuf,
                        depth_i, depth_thres, win, app, blocks);
-    hipLaunchKernelGGL(ptf_scan_blocks_kernel, dim3(1), dim3(1024), 0, st, M, Mp, nbM, nbP, blocks, counts);
+    hipLaunchKernelGGL(ptf_scan_blocks_kernel, dim3(1), dim3(kScanThreads), 0, st, M, Mp, nbM, nbP, blocks, counts);
     hipLaunchKernelGGL(ptf_emit_kernel, dim3(nbM + nbP), dim3(256), 0, st, M, Mp, P, nbM, win, app, pix_of, blocks,
                        (long long*)keep_idx, (long long*)fuse_idx, (long long*)fuse_pix, (long long*)append_pix, zbuf);
     FS_CHECK_LAUNCH("ptf_match");

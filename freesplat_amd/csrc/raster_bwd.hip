@@ -14,6 +14,7 @@
 #include <type_traits>
 
 #include "fs_common.h"
+#include "fs_scan.h"
 #include "raster_host.h"
 
 namespace fs {
@@ -712,24 +713,8 @@ __global__ __launch_bounds__(256) void det_count_kernel(int N, int T, const uint
     }
 }
 
-// exclusive scan of cnt[0..N) in place: blocks of 2048 (256 threads x 8), block totals scanned by one workgroup
-__device__ __forceinline__ uint32_t det_block_excl_scan(uint32_t x, uint32_t* lds, uint32_t& total)
-{
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    uint32_t v = x;
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) {
-        const uint32_t o = __shfl_up(v, m, 64);
-        if (lane >= m) v += o;
-    }
-    if (lane == 63) lds[w] = v;
-    __syncthreads();
-    uint32_t off = 0;
-    for (int k = 0; k < w; ++k) off += lds[k];
-    total = lds[0] + lds[1] + lds[2] + lds[3];
-    __syncthreads();
-    return off + v - x;
-}
+// exclusive scan of cnt[0..N) in place: blocks of 2048 (256 threads x 8, fs_scan.h's block_excl_scan), block totals scanned by
+// one workgroup
 __global__ __launch_bounds__(256) void det_scan_blocks_kernel(int N, const uint32_t* __restrict__ cnt, uint32_t* __restrict__ bsum)
 {
     __shared__ uint32_t lds[4];
@@ -738,7 +723,7 @@ __global__ __launch_bounds__(256) void det_scan_blocks_kernel(int N, const uint3
 #pragma unroll
     for (int k = 0; k < 8; ++k) s += (b0 + k < (size_t)N) ? cnt[b0 + k] : 0u;
     uint32_t total;
-    det_block_excl_scan(s, lds, total);
+    block_excl_scan(s, lds, total);
     if (threadIdx.x == 0) bsum[blockIdx.x] = total;
 }
 __global__ __launch_bounds__(256) void det_scan_totals_kernel(int nb, uint32_t* __restrict__ bsum)
@@ -749,9 +734,10 @@ __global__ __launch_bounds__(256) void det_scan_totals_kernel(int nb, uint32_t* 
         const int i = c + threadIdx.x;
         const uint32_t x = i < nb ? bsum[i] : 0u;
         uint32_t total;
-        const uint32_t e = det_block_excl_scan(x, lds, total);
+        const uint32_t e = block_excl_scan(x, lds, total);
         if (i < nb) bsum[i] = carry + e;
         carry += total;
+        __syncthreads();                                     // the next round writes lds again
     }
 }
 __global__ __launch_bounds__(256) void det_scan_apply_kernel(int N, uint32_t* __restrict__ cnt, const uint32_t* __restrict__ bsum)
@@ -761,8 +747,7 @@ __global__ __launch_bounds__(256) void det_scan_apply_kernel(int N, uint32_t* __
     uint32_t x[8], s = 0;
 #pragma unroll
     for (int k = 0; k < 8; ++k) { x[k] = (b0 + k < (size_t)N) ? cnt[b0 + k] : 0u; s += x[k]; }
-    uint32_t total;
-    uint32_t e = bsum[blockIdx.x] + det_block_excl_scan(s, lds, total);
+    uint32_t e = bsum[blockIdx.x] + block_excl_scan(s, lds);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
         if (b0 + k < (size_t)N) cnt[b0 + k] = e;

@@ -12,8 +12,9 @@
 //               otherwise.  Which views can touch the brick is decided first, one lane per view, as a 64-bit ballot that every
 //               wavefront forms for itself (no LDS, no barrier): view_may_touch below, result-neutral by monotonicity.
 //   mesh plan   count: a thread classifies one cube, a workgroup FS_TSDF_MESH_RUN = 256 consecutive cubes; one workgroup scans the
-//               block counts (a thread takes a contiguous slice, so any number of blocks is covered), 64-bit offsets.
-//   mesh emit   a thread derives its cube's cases again, the workgroup scans its 256 counts, the thread writes its triangles.
+//               block counts into 64-bit offsets (fs_scan.h's slice_scan: any number of blocks is covered).
+//   mesh emit   a thread derives its cube's cases again, the workgroup scans its 256 counts (block_excl_scan), the thread
+//               writes its triangles.
 //
 // Numerics: fp32, every operation rounded on its own (-ffp-contract=off), divisions correctly rounded.  No float atomics, no
 // workgroup waits on another: the same bits on every run and stream.
@@ -23,6 +24,7 @@
 
 #include "../../include/freesplat_amd_tsdf.h"
 #include "fs_reduce.h"
+#include "fs_scan.h"
 
 namespace fs {
 
@@ -34,7 +36,6 @@ static_assert(kBX / 4 * kBY * kBZ == kThreads && kBX / 4 * kBY == kWave, "a wave
 static_assert(FS_TSDF_MAX_VIEWS == kWave, "the view list of a brick is one ballot");
 constexpr int kRun = FS_TSDF_MESH_RUN;
 static_assert(kRun == kThreads, "a thread of the extraction owns one cube");
-constexpr int kScanThreads = 1024;
 constexpr long long kMaxPoints = 0x7FFFFFFFll;
 
 // ------------------------------------------------------------------------------------------------------------ integrate
@@ -343,32 +344,14 @@ __global__ __launch_bounds__(kThreads) void tsdf_mesh_count_kernel(const MeshArg
     if (threadIdx.x == 0) block_counts[blockIdx.x] = (uint32_t)waves_total<int>(s_w, 1);
 }
 
-// One workgroup: exclusive 64-bit scan of the block counts, the sum into *total.  A thread takes a contiguous slice of
-// ceil(nb / 1024) entries, so the loop covers any nb (the form of gaussian_density.hip's block scan).
+// One workgroup: exclusive 64-bit scan of the block counts, the sum into *total (fs_scan.h's slice_scan).
 __global__ __launch_bounds__(kScanThreads) void tsdf_mesh_scan_kernel(uint32_t nb, const uint32_t* __restrict__ block_counts,
                                                                       unsigned long long* __restrict__ block_offsets,
                                                                       long long* __restrict__ total)
 {
     __shared__ unsigned long long part[kScanThreads];
-    const uint32_t t = threadIdx.x;
-    const uint32_t per = (nb + kScanThreads - 1u) / kScanThreads;
-    const uint32_t lo = min(nb, t * per), hi = min(nb, lo + per);
-    unsigned long long s = 0;
-    for (uint32_t k = lo; k < hi; ++k) s += block_counts[k];
-    part[t] = s;
-    __syncthreads();
-    for (uint32_t off = 1; off < (uint32_t)kScanThreads; off <<= 1) {
-        const unsigned long long v = (t >= off) ? part[t - off] : 0ull;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    unsigned long long run = part[t] - s;
-    for (uint32_t k = lo; k < hi; ++k) {
-        block_offsets[k] = run;
-        run += block_counts[k];
-    }
-    if (t == (uint32_t)kScanThreads - 1u) *total = (long long)part[kScanThreads - 1];
+    const unsigned long long sum = slice_scan<unsigned long long>(block_counts, nb, block_offsets, part);
+    if (threadIdx.x == kScanThreads - 1) *total = (long long)sum;
 }
 
 // one cut vertex: position and (COLOR) colour of edge code e of cube q
@@ -404,22 +387,9 @@ __global__ __launch_bounds__(kThreads) void tsdf_mesh_emit_kernel(const MeshArgs
     Cube q;
     uint32_t count;
     const uint32_t cases = cube_cases(a, (long long)blockIdx.x * kRun + threadIdx.x, q, count);
-    // exclusive scan of count over the 256 threads: wave inclusive scan, then the wave totals via LDS
-    const uint32_t lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    uint32_t inc = count;
-#pragma unroll
-    for (int s = 1; s < kWave; s <<= 1) {
-        const uint32_t o = __shfl_up(inc, s, kWave);
-        if (lane >= (uint32_t)s) inc += o;
-    }
-    if (lane == kWave - 1) s_w[wave] = inc;
-    __syncthreads();
-    uint32_t wave_off = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < (uint32_t)kSumWaves; ++k)
-        if (k < wave) wave_off += s_w[k];
+    const uint32_t before = block_excl_scan(count, s_w);
     if (count == 0) return;
-    long long tri = (long long)block_offsets[blockIdx.x] + wave_off + inc - count;
+    long long tri = (long long)block_offsets[blockIdx.x] + before;
     for (int t = 0; t < 6; ++t) {
         const uint32_t cs = (cases >> (4 * t)) & 15u;
         const uint32_t n = triangles_of(cs);
@@ -439,9 +409,6 @@ __global__ __launch_bounds__(kThreads) void tsdf_mesh_emit_kernel(const MeshArgs
         }
     }
 }
-
-bool pos_finite(float x) { return x > 0.0f && x < INFINITY; }
-bool is_finite(float x) { return fabsf(x) < INFINITY; }
 
 // 0: fine; else the status
 int check_dims(int32_t X, int32_t Y, int32_t Z)
@@ -482,9 +449,9 @@ FS_API int fs_tsdf_integrate(int32_t X, int32_t Y, int32_t Z, float ox, float oy
     if (X <= 0 || Y <= 0 || Z <= 0 || V <= 0 || H <= 0 || W <= 0) return FS_ERR_INVALID_ARG;
     if (!tsdf || !weight || !world_to_cam || !intrinsics || !depth) return FS_ERR_INVALID_ARG;
     if ((color == nullptr) != (image == nullptr)) return FS_ERR_INVALID_ARG;
-    if (!is_finite(ox) || !is_finite(oy) || !is_finite(oz)) return FS_ERR_INVALID_ARG;
+    if (!host_finite(ox) || !host_finite(oy) || !host_finite(oz)) return FS_ERR_INVALID_ARG;
     if (near != near || min_depth != min_depth || max_depth != max_depth || alpha_min != alpha_min) return FS_ERR_INVALID_ARG;
-    if (!pos_finite(voxel_size) || !pos_finite(trunc) || !pos_finite(max_weight) || !pos_finite(alpha_floor)) return FS_ERR_INVALID_ARG;
+    if (!host_pos_finite(voxel_size) || !host_pos_finite(trunc) || !host_pos_finite(max_weight) || !host_pos_finite(alpha_floor)) return FS_ERR_INVALID_ARG;
     if (flags & ~FS_TSDF_NO_BRICK_SKIP) return FS_ERR_INVALID_ARG;
     if (V > FS_TSDF_MAX_VIEWS) return FS_ERR_UNSUPPORTED;
     if (check_dims(X, Y, Z) != FS_OK || (long long)H * W > kMaxPoints) return FS_ERR_UNSUPPORTED;
@@ -555,7 +522,7 @@ FS_API int fs_tsdf_mesh_emit(int32_t X, int32_t Y, int32_t Z, float ox, float oy
     if (!tsdf || !weight || !scratch) return FS_ERR_INVALID_ARG;
     if ((color == nullptr) != (colors == nullptr) && T > 0) return FS_ERR_INVALID_ARG;
     if (T > 0 && !vertices) return FS_ERR_INVALID_ARG;
-    if (!(min_weight > 0.0f) || !is_finite(ox) || !is_finite(oy) || !is_finite(oz) || !pos_finite(voxel_size)) return FS_ERR_INVALID_ARG;
+    if (!(min_weight > 0.0f) || !host_finite(ox) || !host_finite(oy) || !host_finite(oz) || !host_pos_finite(voxel_size)) return FS_ERR_INVALID_ARG;
     if (check_dims(X, Y, Z) != FS_OK || T > kMaxPoints / 9) return FS_ERR_UNSUPPORTED;
     if (T == 0) return FS_OK;
     MeshArgs a = mesh_args(X, Y, Z, tsdf, weight, color, min_weight);

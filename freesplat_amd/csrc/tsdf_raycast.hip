@@ -206,9 +206,6 @@ __global__ __launch_bounds__(kThreadsRc) void tsdf_raycast_kernel(const RaycastA
     }
 }
 
-bool rc_pos_finite(float x) { return x > 0.0f && x < INFINITY; }
-bool rc_finite(float x) { return fabsf(x) < INFINITY; }
-
 // what a volume without a cell gives: no ray is alive, nothing of the volume is read
 __global__ __launch_bounds__(kThreadsRc) void tsdf_raycast_dead_kernel(long long n1, float* __restrict__ depth, float* __restrict__ normals,
                                                                       float* __restrict__ out_color, int32_t* __restrict__ steps)
@@ -241,8 +238,8 @@ FS_API int fs_tsdf_raycast(int32_t X, int32_t Y, int32_t Z, float ox, float oy, 
     if (X <= 0 || Y <= 0 || Z <= 0 || V <= 0 || H <= 0 || W <= 0) return FS_ERR_INVALID_ARG;
     if (!tsdf || !weight || !cam_to_world || !intrinsics || !depth) return FS_ERR_INVALID_ARG;
     if (out_color && !color) return FS_ERR_INVALID_ARG;
-    if (!rc_finite(ox) || !rc_finite(oy) || !rc_finite(oz)) return FS_ERR_INVALID_ARG;
-    if (!rc_pos_finite(voxel_size) || !rc_pos_finite(trunc) || !rc_pos_finite(step_min) || !rc_pos_finite(relax)) return FS_ERR_INVALID_ARG;
+    if (!host_finite(ox) || !host_finite(oy) || !host_finite(oz)) return FS_ERR_INVALID_ARG;
+    if (!host_pos_finite(voxel_size) || !host_pos_finite(trunc) || !host_pos_finite(step_min) || !host_pos_finite(relax)) return FS_ERR_INVALID_ARG;
     if (!(min_depth >= 0.0f) || max_depth != max_depth || !(min_weight > 0.0f)) return FS_ERR_INVALID_ARG;
     if (refine < 0 || refine > FS_RAYCAST_MAX_REFINE || max_steps < 1 || max_steps > FS_RAYCAST_MAX_STEPS) return FS_ERR_INVALID_ARG;
     if ((long long)X * Y > kMaxIndex || (long long)X * Y * Z > kMaxIndex || (long long)H * W > kMaxIndex) return FS_ERR_UNSUPPORTED;
