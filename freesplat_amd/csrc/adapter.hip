@@ -309,7 +309,8 @@ __global__ __launch_bounds__(kHeadRows<D_SH>) void head_bwd_kernel(long long M, 
     float dot = 0.0f;
 #pragma unroll
     for (int a = 0; a < 4; ++a) dot += dq[a] * rw[3 + a];
-    const float cq = f.nq > 0.0f ? dot / (D * D * f.nq) : 0.0f;
+    // (D * D * nq as one product overflows from |raw_q| = 7e12 on, long before the squares do: the projection term was lost)
+    const float cq = f.nq > 0.0f ? dot / (D * f.nq) / D : 0.0f;
     float gr[NR];
 #pragma unroll
     for (int a = 0; a < 4; ++a) gr[3 + a] = dq[a] / D - cq * rw[3 + a];

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+from adapter_ref import head64
 from util_raster import oracle_forward, small_scene
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -29,24 +30,6 @@ def _load(name):
 def _adapter(degree):
     from freesplat_amd.gaussian_adapter import GaussianAdapter, GaussianAdapterCfg
     return GaussianAdapter(GaussianAdapterCfg(0.5, 15.0, degree))
-
-
-def head64(raw, dep, E, mult, mask, smin=0.5, smax=15.0):
-    """The head (gaussian_adapter.py:151-172, common/gaussians.py:8-44) in torch ops at any d_sh = mask.numel():
-    raw [M, 7 + 3 d_sh] -> cov [M,3,3], sh [M,3,d_sh], scales [M,3], rotations [M,4] (xyzw)."""
-    d_sh = mask.numel()
-    sc = (smin + (smax - smin) * torch.sigmoid(raw[:, :3])) * dep[:, None] * mult
-    q = raw[:, 3:7] / (raw[:, 3:7].norm(dim=-1, keepdim=True) + 1e-8)
-    i, j, k, r = q.unbind(-1)
-    two_s = 2.0 / ((q * q).sum(-1) + 1e-8)
-    R = torch.stack([1 - two_s * (j * j + k * k), two_s * (i * j - k * r), two_s * (i * k + j * r),
-                     two_s * (i * j + k * r), 1 - two_s * (i * i + k * k), two_s * (j * k - i * r),
-                     two_s * (i * k - j * r), two_s * (j * k + i * r), 1 - two_s * (i * i + j * j)], -1).view(-1, 3, 3)
-    Mm = R * sc[:, None, :]
-    Rc = E[:, :3, :3]
-    cov = Rc @ (Mm @ Mm.transpose(-1, -2)) @ Rc.transpose(-1, -2)
-    sh = raw[:, 7:].reshape(-1, 3, d_sh) * mask
-    return cov, sh, sc, q
 
 
 # ------------------------------------------------------------------------------------------------------------------ CPU
