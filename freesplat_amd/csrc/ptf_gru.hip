@@ -146,9 +146,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FS_GRU_BWD1
         for (int blk = 0; blk < 4; ++blk) { rr[blk] = ld4(ac + (0 * 4 + blk) * 256); zz[blk] = ld4(ac + (1 * 4 + blk) * 256); }
     } else {
     {
+        // The three FIRST layers add their bias to the finished sum (as ptf_gru16_kernel does, bit for bit): an accumulator that
+        // starts at the bias rounds every k-step at the bias's magnitude -- 13 u on rows whose products are small beside it,
+        // where the sum rounded once is good to 1 u (tests/test_ptf_gru_edges_hip.py, the tiny class).
         f32x4 r1[4], z1[4];
 #pragma unroll
-        for (int blk = 0; blk < 4; ++blk) { r1[blk] = ld4(bias + 0 * 64 + 16 * blk + ao); z1[blk] = ld4(bias + 1 * 64 + 16 * blk + ao); }
+        for (int blk = 0; blk < 4; ++blk) { r1[blk] = f32x4{0.0f, 0.0f, 0.0f, 0.0f}; z1[blk] = f32x4{0.0f, 0.0f, 0.0f, 0.0f}; }
+        f32x4 b1r[4], b1z[4];   // the biases, fetched four k-steps (32 MFMAs) before the sums are finished: most of xh is dead by then
         {
             float xh[44];       // this quarter's 44 features of the input row: k-step s, quarter g <-> feature 44 g + s
 #pragma unroll
@@ -158,6 +162,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FS_GRU_BWD1
             }
 #pragma unroll
             for (int s = 0; s < 44; ++s) {
+                if (s == 40) {
+#pragma unroll
+                    for (int blk = 0; blk < 4; ++blk) { b1r[blk] = ld4(bias + 0 * 64 + 16 * blk + ao); b1z[blk] = ld4(bias + 1 * 64 + 16 * blk + ao); }
+                }
 #pragma unroll
                 for (int ob = 0; ob < 4; ++ob) r1[ob] = FS_MFMA16(FS_AOP(s * 8 + ob), xh[s], r1[ob]);
 #pragma unroll
@@ -165,6 +173,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FS_GRU_BWD1
             }
         }
         constexpr int p1 = 44 * 8;
+#pragma unroll
+        for (int blk = 0; blk < 4; ++blk) { r1[blk] += b1r[blk]; z1[blk] += b1z[blk]; }
 #pragma unroll
         for (int blk = 0; blk < 4; ++blk)
 #pragma unroll
@@ -195,7 +205,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FS_GRU_BWD1
     }
     {   // mlp_n layer 1: [r * hid (64) | x (64) | xe (24)]
 #pragma unroll
-        for (int blk = 0; blk < 4; ++blk) n1[blk] = ld4(bias + 4 * 64 + 16 * blk + ao);
+        for (int blk = 0; blk < 4; ++blk) n1[blk] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
         f32x4 h0[4];   // r * hid, stored for the weight gradient of mlp_n layer 1
 #pragma unroll
         for (int blk = 0; blk < 4; ++blk)
@@ -215,10 +225,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FS_GRU_BWD1
             const float2 v = ((const float2*)(row + 88 + 22 * g))[k];
             xt[2 * k] = v.x; xt[2 * k + 1] = v.y;
         }
+        f32x4 b1n[4];
 #pragma unroll
-        for (int s = 0; s < 22; ++s)
+        for (int s = 0; s < 22; ++s) {
+            if (s == 14) {
+#pragma unroll
+                for (int blk = 0; blk < 4; ++blk) b1n[blk] = ld4(bias + 4 * 64 + 16 * blk + ao);
+            }
 #pragma unroll
             for (int ob = 0; ob < 4; ++ob) n1[ob] = FS_MFMA16(FS_AOP(p2 + 64 + s * 4 + ob), xt[s], n1[ob]);
+        }
+#pragma unroll
+        for (int blk = 0; blk < 4; ++blk) n1[blk] += b1n[blk];
 #pragma unroll
         for (int blk = 0; blk < 4; ++blk)
 #pragma unroll
@@ -449,16 +467,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FS_GRU_FWD1
         }
     }
 
-    f32x4 r1[4], z1[4];
-#pragma unroll
-    for (int blk = 0; blk < 4; ++blk) { r1[blk] = ld4(bias + 0 * 64 + 16 * blk + ao); z1[blk] = ld4(bias + 1 * 64 + 16 * blk + ao); }
+    // The three FIRST layers add their bias to the finished sum: an accumulator that starts at the bias rounds every k-step at the
+    // bias's magnitude (13 u on rows whose products are small beside it; the sum rounded once is good to 1 u).  The biases are fetched
+    // a few k-steps before the sums are finished, when most of the layer's inputs are dead.
+    const f32x4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
+    f32x4 r1[4] = {zero4, zero4, zero4, zero4}, z1[4] = {zero4, zero4, zero4, zero4};
+    f32x4 b1r[4], b1z[4];
 #pragma unroll
     for (int s = 0; s < 44; ++s) {
+        if (s == 40) {
+#pragma unroll
+            for (int blk = 0; blk < 4; ++blk) { b1r[blk] = ld4(bias + 0 * 64 + 16 * blk + ao); b1z[blk] = ld4(bias + 1 * 64 + 16 * blk + ao); }
+        }
 #pragma unroll
         for (int ob = 0; ob < 4; ++ob) r1[ob] = FS_MFMA16(FS_AOP(s * 8 + ob), xh[s], r1[ob]);
 #pragma unroll
         for (int ob = 0; ob < 4; ++ob) z1[ob] = FS_MFMA16(FS_AOP(s * 8 + 4 + ob), xh[s], z1[ob]);
     }
+#pragma unroll
+    for (int blk = 0; blk < 4; ++blk) { r1[blk] += b1r[blk]; z1[blk] += b1z[blk]; }
     constexpr int p1 = 44 * 8;
     if constexpr (SAVE) {
         if (live) {
@@ -483,9 +510,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FS_GRU_FWD1
         for (int ob = 0; ob < 4; ++ob) Z[ob] = FS_MFMA16(FS_AOP(p1 + s * 8 + 4 + ob), bz, Z[ob]);
     }
     constexpr int p2 = p1 + 16 * 8;
-    f32x4 n1[4];
-#pragma unroll
-    for (int blk = 0; blk < 4; ++blk) n1[blk] = ld4(bias + 4 * 64 + 16 * blk + ao);
+    f32x4 n1[4] = {zero4, zero4, zero4, zero4}, b1n[4];
     if constexpr (SAVE) {
 #pragma unroll
         for (int blk = 0; blk < 4; ++blk) {
@@ -524,10 +549,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FS_GRU_FWD1
             }
         }
 #pragma unroll
-        for (int s = 0; s < 22; ++s)
+        for (int s = 0; s < 22; ++s) {
+            if (s == 14) {
+#pragma unroll
+                for (int blk = 0; blk < 4; ++blk) b1n[blk] = ld4(bias + 4 * 64 + 16 * blk + ao);
+            }
 #pragma unroll
             for (int ob = 0; ob < 4; ++ob) n1[ob] = FS_MFMA16(FS_AOP(p2 + 64 + s * 4 + ob), xt[s], n1[ob]);
+        }
     }
+#pragma unroll
+    for (int blk = 0; blk < 4; ++blk) n1[blk] += b1n[blk];
     constexpr int p3 = p2 + 64 + 88;
     if constexpr (SAVE) {
         if (live) {
